@@ -43,6 +43,11 @@ Extra objects on the JSON line:
                 backward (opt-in SISR_GRAPH_OVERLAP=1), measured last under a watchdog; config.grad_exchange names the mode
                 the headline ran.
 Every auxiliary object is measured inside its own try block: an error lands under that object's key as {"error": ...}.
+
+--dump-outputs DIR writes what the headline's last timed step returned (the loss and the SR output) as DIR/loss.npy and
+DIR/out.npy, at most 64 MB in all (an output larger than that is a fixed seeded sample of its elements), and names them under
+"dump_outputs" on the line.  The inputs and the initial weights are seeded, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import json
@@ -97,6 +102,8 @@ WORKLOADS = {
     "qsparnet": ("qsparnet", {"metadata": ["blur_kernel"], "hr_same": True}, 0.0428),
 }
 GRAPH_MAX_BATCH = 8  # --graph auto: per-GPU batches up to this replay forward+backward from a hipGraph
+DUMP_BYTES = 60 * 10 ** 6  # --dump-outputs: array data in all (with the .npy headers well under 64 MB)
+DUMP_SEED = 8              # --dump-outputs: seed of the element sample of an output larger than its share
 
 
 class KernelTimer:
@@ -240,8 +247,32 @@ def launch_ranks(n):
     return child.wait()
 
 
-def measure(sisr, workload, B, steps, warmup, use_graph, rank, world, local, dev, families=False, dp=False):
-    """Build the handler, run warm-up + exactly `steps` timed steps (barrier + sync on both sides, max over ranks)."""
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as path/<name>.npy (float32 / float64), DUMP_BYTES in all.  An array larger than its share
+    of the budget is written as a fixed sample of its elements (flat indices drawn with a fixed seed, ascending), so that two
+    builds given the same arguments can be compared element for element.  -> {name: {"shape", "elements_written"}}"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left, info = DUMP_BYTES, {}
+    order = sorted(arrays, key=lambda k: arrays[k].size)
+    for i, name in enumerate(order):
+        a = np.asarray(arrays[name])
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32)
+        shape = list(a.shape)
+        k = (left // (len(order) - i)) // a.itemsize
+        if k < a.size:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=k, replace=False, shuffle=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+        info[name] = {"shape": shape, "elements_written": int(a.size)}
+    return info
+
+
+def measure(sisr, workload, B, steps, warmup, use_graph, rank, world, local, dev, families=False, dp=False, outputs=False):
+    """Build the handler, run warm-up + exactly `steps` timed steps (barrier + sync on both sides, max over ranks).
+    outputs: res["outputs"] holds host copies of what the last timed step returned (loss, SR output), taken after the clock stopped."""
     name, params, tflop_per_patch = WORKLOADS[workload]
     params = dict(params)
     maps = params.pop("maps", False)
@@ -274,7 +305,7 @@ def measure(sisr, workload, B, steps, warmup, use_graph, rank, world, local, dev
     sync()
     t0 = time.perf_counter()
     for _ in range(steps):
-        loss, _ = h.train_step(x, y, **kw)
+        loss, out = h.train_step(x, y, **kw)
     sync()
     dt = time.perf_counter() - t0
     t = torch.tensor([dt], device=dev)
@@ -283,6 +314,8 @@ def measure(sisr, workload, B, steps, warmup, use_graph, rank, world, local, dev
     dt = float(t.item())
     res = {"value": world * B * steps / dt, "ms_per_step": 1e3 * dt / steps, "loss": float(loss.item()),
            "tflop_per_patch": tflop_per_patch, "width": params.get("num_features", 64), "name": name, "params": params}
+    if outputs:
+        res["outputs"] = {"loss": loss.detach().cpu().numpy(), "out": out.detach().cpu().numpy()}
     if families:  # one extra, untimed, eager step with every kernel alone on the stream
         timer = KernelTimer(sisr.ops, width=res["width"])
         timer.install()
@@ -360,7 +393,13 @@ def main():
     ap.add_argument("--storage", default="0", choices=["0", "act", "all"],
                     help="with --precision bf16: storage of the maps a residual group keeps: 0 = fp32, act = bf16 activations, "
                          "all = bf16 activations and gradient maps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (loss, SR output; rank 0's share) as "
+                         "DIR/<name>.npy, at most 64 MB in all: an output larger than its share is a fixed seeded sample of its "
+                         "elements")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started bare (`python bench.py --gpus N`, the way the reference turns multi-GPU on with a flag and no launcher,
@@ -403,7 +442,14 @@ def main():
     use_graph = args.graph == "on" or (args.graph == "auto" and (B <= GRAPH_MAX_BATCH or WORKLOADS[workload][1].get("hr_same")))
 
     main_res = measure(sisr, workload, B, args.steps, args.warmup, use_graph, rank, world, local, dev,
-                       families=not args.no_kernel_timing and args.precision == "fp32", dp=args.force_dp)
+                       families=not args.no_kernel_timing and args.precision == "fp32", dp=args.force_dp,
+                       outputs=args.dump_outputs is not None)
+    dumped = None
+    if args.dump_outputs is not None:
+        arrays = main_res.pop("outputs")
+        if rank == 0:
+            dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, arrays)}
+        del arrays
     secondary = None
     if not explicit and not args.no_secondary and args.precision == "fp32":
         # N = 1: the north_star family beside BASELINE's configs[1]; N > 1: the weak-scaling point beside config 4
@@ -632,6 +678,8 @@ def main():
                                 "traffic": None,
                                 "secondary": {"bound": "mfma", "achieved": step_tf, "peak": 2500.0, "unit": "TFLOP/s",
                                               "frac": step_tf / 2500.0}}
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if secondary is not None:
             line[secondary[0]] = secondary[1]
         line.update(extras)

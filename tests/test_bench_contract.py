@@ -36,6 +36,42 @@ def test_bench_line_has_the_contract_fields():
 
 
 @pytest.mark.gpu
+def test_bench_dumps_the_last_timed_steps_outputs(tmp_path):
+    """--dump-outputs DIR: the loss and SR output of the last timed step as float .npy files, named on the JSON line."""
+    import numpy as np
+    d = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--batch", "2", "--workload", "edsr", "--no-cpu-baseline", "--no-kernel-timing", "--dump-outputs", str(d)],
+                         capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    assert line["dump_outputs"]["arrays"] == {"loss": {"shape": [], "elements_written": 1},
+                                              "out": {"shape": [2, 3, 512, 512], "elements_written": 2 * 3 * 512 * 512}}
+    loss, sr = np.load(d / "loss.npy"), np.load(d / "out.npy")
+    assert loss.dtype == np.float32 and sr.dtype == np.float32 and sr.shape == (2, 3, 512, 512)
+    assert np.isfinite(sr).all() and abs(float(loss) - line["config"]["final_loss"]) < 1e-7
+
+
+def test_dump_outputs_keeps_to_its_budget_with_a_fixed_sample(tmp_path):
+    """A large output is written as the same seeded element sample every time; small arrays whole; 64 MB in all."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(0)
+    arrays = {"loss": np.array(0.25, np.float32), "out": rng.random((20, 3, 512, 512), dtype=np.float32),
+              "stat": rng.random(7)}
+    info = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 * 10 ** 6
+    assert info["loss"] == {"shape": [], "elements_written": 1} and info["stat"]["elements_written"] == 7
+    assert 0 < info["out"]["elements_written"] < arrays["out"].size
+    a, b = np.load(tmp_path / "a" / "out.npy"), np.load(tmp_path / "b" / "out.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, b)
+    assert np.isin(a[:1000], arrays["out"]).all()
+    assert np.load(tmp_path / "a" / "stat.npy").dtype == np.float64 and np.load(tmp_path / "a" / "loss.npy").shape == ()
+
+
+@pytest.mark.gpu
 def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher and no WORLD_SIZE: bench.py spawns its two ranks as a child
     torch.distributed.run (never exec) and relays rank 0's single JSON line.  Rehearsed on the one GPU of this box: both ranks
