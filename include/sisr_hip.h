@@ -94,7 +94,10 @@ size_t sisr_ca_tail_bytes(void);
  * 8 / 9 / 10: the caller asserts structural zeros in the packed weight (SFTMD's merged convs) and the kernel skips them:
  *   8  64 -> 128 block-diagonal (output chunk q contracts input channels 32q .. 32q+31 only), plain epilogue;
  *   9  128 -> 64 whose input channels >= 80 are zero (second chunk: first 16 channels only), LeakyReLU epilogue;
- *  10  128 -> 64, the transpose of 8 (input chunk c feeds output channels 32c .. 32c+31 only), LeakyReLU' mask, no bias. */
+ *  10  128 -> 64, the transpose of 8 (input chunk c feeds output channels 32c .. 32c+31 only), LeakyReLU' mask, no bias.
+ * 11 / 12 (64 -> 64 only): the Winograd F(2x2,3x3) weights follow the direct packing (wpacked + 36864 floats, written by
+ *   sisr_pack_conv3x3_many for jobs with r | 0x100); 11 behaves as 0 but runs the Winograd form of the persistent kernel
+ *   from more than 8 x 128^2 output pixels per launch on (SISR_CONV_WINOGRAD=0: never), 12 as 7 with the Winograd form forced. */
 /* gate_add / gate_out / dot (all nullable; 64 -> 64, x and y in one layout) fuse the gated-residual chain of
  * RCAB / QRCAB stacks (ref: advanced/architectures.py:68-71, :107-110) into the neighbouring convs:
  *   gate_add + gate_out : the conv reads  x * in_scale[b,c] + gate_add  (the previous block's `res * y + x`) and

@@ -1050,6 +1050,271 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_p4_kernel(ConvParams p, in
   }
 }
 
+// ------------------------------------------------------------------ Winograd F(2x2,3x3) form of the persistent kernel
+// Same tile (4 x 32 output pixels = 2 x 16 Winograd tiles of 2 x 2), halo image, tile walk, next-tile prefetch and
+// prologue (commit) as conv3x3_c64_p4_kernel; the K loop is 16 GEMMs, one per transform point xi = (xr, xc):
+// M[xi][tile][co] = sum_ci V[xi][tile][ci] U[xi][ci][co], V = B^T d B (input 4 x 4 patch), U = G g G^T (packed behind the
+// direct weights by pack_conv3x3_many_kernel, layout [xi 16][G 4][q 4][co 64][e 4] for ci = 16 G + 4 q + e), and the
+// output 2 x 2 block is A^T M A.  4/9 of the direct form's MFMAs; multiplies stay exact fp32, the transforms add a few
+// fp32 roundings (only 0, +-1 and 1/2 coefficients).
+//   wave w: output channels [16w, 16w + 16) of all 32 Winograd tiles, v_mfma_f32_16x16x4_f32 with two M-blocks (tile
+//           rows) sharing each B fragment: lane (n = l & 15, q = l >> 4) accumulates tiles (mb, 4q + reg) x channel 16w + n,
+//           the same (tile, co) for every xi, so the output transform stays in registers (folded once per xr row)
+//   V chunk: per (xr, ci half) the workgroup transforms the halo ONCE into LDS, [xc 4][tile 32][32 ci] (16 KB, 16-B piece
+//           k of tile t at slot k ^ ((t >> 1) & 7): conflict-free ds_read_b128 of the A fragments), 64 MFMAs per wave
+//           between barriers
+//   epilogue: p4's arithmetic per output pixel (bias added after the transform), stores and partial sums masked to the
+//           image; GAP / DOT partials in p4's slot layout (one per (2-row strip, 32 columns)).
+#define W4_VCHUNK (4 * 32 * 32)  // floats
+template <bool AFFINE, bool MASK, bool RES, bool GATE, bool DOT>
+__global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, int total_tiles, const float* __restrict__ wu) {
+  constexpr int THv = 4, HHv = 6;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* const vbuf = lds + HALO_H * HALO_W * 64;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = lane & 15, q = lane >> 4;
+  const int H = p.H, W = p.W;
+  const int co = wave * 16 + n;
+  const float bv = p.bias ? p.bias[co * p.bias_n] : 0.f;
+  const sisr_rsrc_t rw = sisr_rsrc(wu);
+  const unsigned boff = (unsigned)(q * 64 + co) * 16u;
+
+  const int G = gridDim.x;
+  int t_begin = blockIdx.x, t_end = total_tiles, t_step = G;
+  if ((G & 7) == 0) {
+    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3, per = (total_tiles + 7) >> 3;
+    t_begin = xcd * per + idx;
+    t_end = min(total_tiles, (xcd + 1) * per);
+    t_step = G >> 3;
+  }
+  auto decode = [&](int tile, int& b, int& h0, int& w0) {
+    const int tw = tile % p.tiles_w;
+    const int t2 = tile / p.tiles_w;
+    b = t2 / p.tiles_h;
+    h0 = (t2 - b * p.tiles_h) * THv;
+    w0 = tw * TW;
+  };
+  // halo staging: conv3x3_c64_p4_kernel's issue / commit
+  const int c4 = tid & 15, pcol = tid >> 4;
+  f32x4 v[HHv][3];
+  auto issue = [&](int tile) {
+    int b, h0, w0;
+    decode(tile, b, h0, w0);
+    const sisr_rsrc_t rx = sisr_rsrc(p.x + (long)b * p.xv.sB);
+#pragma unroll
+    for (int r = 0; r < HHv; ++r) {
+      const unsigned ro = (unsigned)(min(max(h0 - 1 + r, 0), H - 1) * (int)p.xv.sH) * 4u;
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        if (k < 2 || pcol < 2) {
+          const unsigned go = (unsigned)(min(max(w0 - 1 + pcol + 16 * k, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u;
+          v[r][k] = sisr_buf_load4(rx, go, ro);
+        }
+    }
+  };
+  auto commit = [&](int tile) {
+    int b, h0, w0;
+    decode(tile, b, h0, w0);
+    const bool interior = h0 >= 1 && h0 + THv + 1 <= H && w0 >= 1 && w0 + TW + 1 <= W;
+    f32x4 s4 = {1.f, 1.f, 1.f, 1.f}, t4 = {0.f, 0.f, 0.f, 0.f};
+    if (AFFINE || GATE) s4 = *reinterpret_cast<const f32x4*>(p.in_scale + (long)b * 64 + c4 * 4);
+    if (AFFINE && p.in_shift) t4 = *reinterpret_cast<const f32x4*>(p.in_shift + (long)b * 64 + c4 * 4);
+    const sisr_rsrc_t ro_ = sisr_rsrc(GATE ? p.gate_out + (long)b * p.xv.sB : p.y);
+    f32x4 u[GATE ? HHv : 1][3];
+    if (GATE) {
+      const sisr_rsrc_t ru = sisr_rsrc(p.gate_add + (long)b * p.xv.sB);
+#pragma unroll
+      for (int r = 0; r < HHv; ++r) {
+        const unsigned ro = (unsigned)(min(max(h0 - 1 + r, 0), H - 1) * (int)p.xv.sH) * 4u;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          if (k < 2 || pcol < 2)
+            u[r][k] = sisr_buf_load4(ru, (unsigned)(min(max(w0 - 1 + pcol + 16 * k, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u, ro);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < HHv; ++r) {
+      const int gh = h0 - 1 + r;
+      const bool rok = gh >= 0 && gh < H;
+      const bool rown = r >= 1 && r <= THv && gh < H;
+      const unsigned ro = (unsigned)(min(max(gh, 0), H - 1) * (int)p.xv.sH) * 4u;
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        if (k < 2 || pcol < 2) {
+          const int col = pcol + 16 * k, gw = w0 - 1 + col;
+          const bool cok = gw >= 0 && gw < W && col < HALO_W;
+          f32x4 t = v[r][k];
+          if (AFFINE) t = t * s4 + t4;
+          if (GATE) {
+            t = sisr_mul_add4(t, s4, u[r][k]);
+            if (rown && cok && col >= 1 && col <= TW)
+              SISR_Y_STORE4(t, ro_, (unsigned)(min(max(gw, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u, ro);
+          }
+          if (!interior) t = sisr_keep_if(t, rok && cok);
+          *reinterpret_cast<f32x4*>(lds + r * (HALO_W * 64) + col * 64 + ((c4 ^ (col & 15)) << 2)) = t;
+        }
+    }
+  };
+
+  // input transform map: thread (Winograd tile vt = tr * 16 + tc, 16-B channel piece vc of the current ci half)
+  const int vt = tid >> 3, vc = tid & 7;
+  const int vtr = vt >> 4, vtc = vt & 15;
+  const unsigned vw_off = (unsigned)(vt * 32 + ((vc ^ ((vt >> 1) & 7)) << 2));
+  // A fragments: tile mb * 16 + n, pieces 4g + q of the ci half
+  unsigned aoff[2][2];
+#pragma unroll
+  for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      const int t = mb * 16 + n;
+      aoff[mb][g] = (unsigned)(t * 32 + (((4 * g + q) ^ ((t >> 1) & 7)) << 2));
+    }
+
+  if (t_begin < t_end) {
+    issue(t_begin);
+    commit(t_begin);
+  }
+  __syncthreads();
+  for (int tile = t_begin; tile < t_end; tile += t_step) {
+    const bool has_next = tile + t_step < t_end;
+    int b, h0, w0;
+    decode(tile, b, h0, w0);
+    // step s = ((xr * 2 + hf) * 4 + xc) * 2 + g: B fragment U[xi = 4 xr + xc][G = 2 hf + g], 4 KB apart per (xi, G)
+#define W4_BOFF(s) ((unsigned)((((((s) >> 4) * 4 + (((s) >> 1) & 3)) * 4) + (((s) >> 3) & 1) * 2 + ((s) & 1)) * 4096))
+    f32x4 bq[8];
+#pragma unroll
+    for (int s = 0; s < 6; ++s) bq[s] = sisr_buf_load4(rw, boff, W4_BOFF(s));
+    if (GATE && has_next) issue(tile + t_step);
+    f32x4 y[2][2][2];  // [mb][out row i][out col j], registers = the lane's four tiles 4q + reg
+    f32x4 acc[4][2];   // [xc][mb] of the current xr
+#pragma unroll
+    for (int xc = 0; xc < 4; ++xc) acc[xc][0] = acc[xc][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int xr = 0; xr < 4; ++xr) {
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        // ---- V chunk (xr, ci half hf) from the halo: rows, then columns, of B^T d B
+        if (xr | hf) __syncthreads();  // every wave is done reading the previous chunk
+        // the next tile's halo is requested two chunks before this one's is last read (fewer registers held across the
+        // K loop than p4's whole-tile lead) and written to LDS right after that.  GATE keeps p4's schedule: its commit
+        // also fetches the skip map, which does not fit beside the K loop's registers
+        if (!GATE && xr == 3 && hf == 0 && has_next) issue(tile + t_step);
+        {
+          const int ra = xr == 0 ? 0 : (xr == 3 ? 3 : 2), rb = xr == 0 ? 2 : 1;  // row combine d[ra] -+ d[rb]
+          const int c = hf * 8 + vc;
+          f32x4 rr[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int col = 2 * vtc + j;
+            const float* base = lds + col * 64 + ((c ^ (col & 15)) << 2);
+            const f32x4 da = *reinterpret_cast<const f32x4*>(base + (2 * vtr + ra) * (HALO_W * 64));
+            const f32x4 db = *reinterpret_cast<const f32x4*>(base + (2 * vtr + rb) * (HALO_W * 64));
+            // xr 0: d0 - d2, 1: d1 + d2, 2: d2 - d1, 3: d1 - d3  (ra, rb) = (0,2) (2,1) (2,1) (3,1)
+            rr[j] = xr == 0 ? da - db : (xr == 1 ? db + da : (xr == 2 ? da - db : db - da));
+          }
+          float* vw = vbuf + vw_off;
+          *reinterpret_cast<f32x4*>(vw + 0 * 1024) = rr[0] - rr[2];
+          *reinterpret_cast<f32x4*>(vw + 1 * 1024) = rr[1] + rr[2];
+          *reinterpret_cast<f32x4*>(vw + 2 * 1024) = rr[2] - rr[1];
+          *reinterpret_cast<f32x4*>(vw + 3 * 1024) = rr[1] - rr[3];
+        }
+        __syncthreads();
+        if (!GATE && xr == 3 && hf == 1 && has_next) commit(tile + t_step);  // the halo is free: no wave reads it again
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- 4 transform points x 32 input channels: 64 MFMAs per wave
+#pragma unroll
+        for (int xc = 0; xc < 4; ++xc)
+#pragma unroll
+          for (int g = 0; g < 2; ++g) {
+            const int s = ((xr * 2 + hf) * 4 + xc) * 2 + g;
+            if (s + 6 < 64) bq[(s + 6) & 7] = sisr_buf_load4(rw, boff, W4_BOFF(s + 6));
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(vbuf + xc * 1024 + aoff[0][g]);
+            const f32x4 a1 = *reinterpret_cast<const f32x4*>(vbuf + xc * 1024 + aoff[1][g]);
+            const f32x4 bb = bq[s & 7];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              acc[xc][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[e], bb[e], acc[xc][0], 0, 0, 0);
+              acc[xc][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[e], bb[e], acc[xc][1], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+      }
+      // ---- fold row xr of A^T M A: T = (m0 + m1 + m2, m1 - m2 - m3); y0 += T (xr 0..2), y1 += T (1), -= T (2, 3)
+#pragma unroll
+      for (int mb = 0; mb < 2; ++mb) {
+        const f32x4 t0 = acc[0][mb] + acc[1][mb] + acc[2][mb];
+        const f32x4 t1 = acc[1][mb] - acc[2][mb] - acc[3][mb];
+        if (xr == 0) { y[mb][0][0] = t0; y[mb][0][1] = t1; }
+        if (xr == 1) { y[mb][0][0] += t0; y[mb][0][1] += t1; y[mb][1][0] = t0; y[mb][1][1] = t1; }
+        if (xr == 2) { y[mb][0][0] += t0; y[mb][0][1] += t1; y[mb][1][0] -= t0; y[mb][1][1] -= t1; }
+        if (xr == 3) { y[mb][1][0] -= t0; y[mb][1][1] -= t1; }
+      }
+#pragma unroll
+      for (int xc = 0; xc < 4; ++xc) acc[xc][0] = acc[xc][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+#undef W4_BOFF
+    __syncthreads();  // every wave is done with this tile's V chunk (and the halo); but for GATE the next halo is in LDS
+    // ---- epilogue: pixel (h0 + 2 mb + i, w0 + 8 q + 2 reg + j), channel co
+    {
+      float os = p.alpha;
+      if (p.out_scale) os *= p.out_scale[(long)b * 64 + co];
+      const bool scaled = p.out_scale != nullptr || p.alpha != 1.0f;
+      const sisr_rsrc_t ry = sisr_rsrc(p.y + (long)b * p.yv.sB);
+      const sisr_rsrc_t rmk = sisr_rsrc(MASK ? p.mask + (long)b * p.yv.sB : p.y);
+      const sisr_rsrc_t rrs = sisr_rsrc(RES ? p.res + (long)b * p.yv.sB : p.y);
+      const sisr_rsrc_t rdt = sisr_rsrc(DOT ? p.dot + (long)b * p.yv.sB : p.y);
+      float gsum[2];
+#pragma unroll
+      for (int mb = 0; mb < 2; ++mb) {
+        float mk[2][2][4], rs[2][2][4], dt[2][2][4];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int row = min(h0 + 2 * mb + i, H - 1), col = min(w0 + 8 * q + 2 * r + j, W - 1);
+              const unsigned vo = (unsigned)(col * (int)p.yv.sW + co) * 4u, so = (unsigned)(row * (int)p.yv.sH) * 4u;
+              if (MASK) mk[i][j][r] = sisr_buf_load1(rmk, vo, so);
+              if (RES) rs[i][j][r] = sisr_buf_load1(rrs, vo, so);
+              if (DOT) dt[i][j][r] = sisr_buf_load1(rdt, vo, so);
+            }
+        float gs = 0.f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              float a = y[mb][i][j][r] + bv;
+              if (p.relu) a = fmaxf(a, 0.f);
+              if (scaled) a *= os;
+              if (MASK) a = mk[i][j][r] > 0.f ? a : 0.f;
+              if (RES) a += rs[i][j][r];
+              const int row = h0 + 2 * mb + i, col = w0 + 8 * q + 2 * r + j;
+              if (row < H && col < W) {
+                SISR_Y_STORE1(a, ry, (unsigned)(col * (int)p.yv.sW + co) * 4u, (unsigned)(row * (int)p.yv.sH) * 4u);
+                gs = DOT ? __builtin_fmaf(a, dt[i][j][r], gs) : gs + a;
+              }
+            }
+        gs += __shfl_xor(gs, 16);
+        gsum[mb] = gs + __shfl_xor(gs, 32);
+      }
+      if (p.gap && q == 0) {
+        const long parts = (long)p.tiles_w * ((H + 3) / 4) * 2;
+        const int th = h0 / THv, tw = w0 / TW;
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb) p.gap[(((long)b * parts) + (th * p.tiles_w + tw) * 2 + mb) * 64 + co] = gsum[mb];
+      }
+    }
+    if (GATE && has_next) {
+      commit(tile + t_step);
+      __syncthreads();
+    }
+  }
+}
+
 // ------------------------------------------------------------------ bf16 matrix-core kernel (fp32 in HBM)
 // Same tile / wave geometry, View addressing and epilogue as the fp32 kernels, but the contraction runs on
 // v_mfma_f32_32x32x16_bf16 (16x the fp32 MFMA rate): activations are rounded to bf16 (RNE, v_cvt_pk_bf16_f32)
@@ -2257,9 +2522,13 @@ struct PackJob {
   const float* w;
   void* pf;
   void* pd;
-  int cout, cin, r, first_block;
+  int cout, cin, r, first_block;  // r | SISR_PACK_WINOGRAD: see below
   int co_real, ci_real;  // > 0: w is (co_real, ci_real, 3, 3) and is packed as its zero-padded (cout, cin, 3, 3) twin (SPARNet)
 };
+// fp32 64 -> 64 jobs (r = 1) with this flag also write the Winograd F(2x2,3x3) weights U = G g G^T of both orders right
+// behind the direct packings (pf + 36864, pd + 36864; layout: conv3x3_c64_w4_kernel), from 16 more blocks of the job.
+#define SISR_PACK_WINOGRAD 0x100
+#define SISR_WINO_FLOATS (16 * 64 * 64)
 
 template <int MODE>  // 0 fp32, 1 bf16, 2 bf16x3 (three planes `total` elements apart)
 __global__ __launch_bounds__(256) void pack_conv3x3_many_kernel(const PackJob* __restrict__ jobs, int n_jobs) {
@@ -2275,7 +2544,7 @@ __global__ __launch_bounds__(256) void pack_conv3x3_many_kernel(const PackJob* _
   __syncthreads();
   const PackJob jb = jobs[job_s];
   const float* __restrict__ wsrc = jb.w;
-  const int cout = jb.cout, cin = jb.cin, r = jb.r;
+  const int cout = jb.cout, cin = jb.cin, r = jb.r & 0xff;
   const int cor = jb.co_real > 0 ? jb.co_real : cout, cir = jb.ci_real > 0 ? jb.ci_real : cin;
   // element (o, i, tap) of the (zero-padded) weight; the index expression the packings below were written with
   struct Src {
@@ -2286,6 +2555,30 @@ __global__ __launch_bounds__(256) void pack_conv3x3_many_kernel(const PackJob* _
   const Src w{wsrc, cor, cir};
   const long total = (long)cout * cin * 9;
   const long idx = (long)(blockIdx.x - jb.first_block) * 256 + threadIdx.x;
+  if (MODE == 0 && (jb.r & SISR_PACK_WINOGRAD) && idx >= (total + 255) / 256 * 256) {
+    // thread k = (G * 4 + q) * 256 + co * 4 + e writes U[xi][ci][co] at xi * 4096 + k, ci = 16 G + 4 q + e (lanes store
+    // consecutive words);
+    // U[xr][xc] = sum G[xr][kh] g[kh][kw] G[xc][kw] (columns first), G = {{1, 0, 0}, {1/2, 1/2, 1/2}, {1/2, -1/2, 1/2}, {0, 0, 1}};
+    // dgrad: g = the flipped, role-swapped weight
+    const long k = idx - (total + 255) / 256 * 256;
+    if (k >= 64 * 64 || cout != 64 || cin != 64) return;
+    const int co = (k >> 2) & 63, ci = (int)(k >> 8) * 4 + (k & 3);
+    const long u0 = k;
+    auto gmul = [](int x, float a, float b, float c) {  // row x of G times (a, b, c)
+      return x == 0 ? a : (x == 3 ? c : (x == 1 ? 0.5f * (a + b + c) : 0.5f * (a - b + c)));
+    };
+    for (int dir = 0; dir < 2; ++dir) {
+      float g9[9];
+      for (int t = 0; t < 9; ++t) g9[t] = dir == 0 ? w.at(co, ci, t) : w.at(ci, co, 8 - t);
+      float* dst = static_cast<float*>(dir == 0 ? jb.pf : jb.pd) + total + u0;
+      for (int xc = 0; xc < 4; ++xc) {
+        float rk[3];
+        for (int kh = 0; kh < 3; ++kh) rk[kh] = gmul(xc, g9[3 * kh], g9[3 * kh + 1], g9[3 * kh + 2]);
+        for (int xr = 0; xr < 4; ++xr) dst[(long)(4 * xr + xc) * 4096] = gmul(xr, rk[0], rk[1], rk[2]);
+      }
+    }
+    return;
+  }
   if (idx >= total) return;
   const int rr = r * r;
   const int oc = cout >> 6, ic = cin >> 6;
@@ -2383,6 +2676,18 @@ static inline bool sisr_use_persistent(int variant, long nblk) {
   if (e && e[0] == '0') return false;
   return nblk >= 1024;
 }
+// The Winograd form (conv3x3_c64_w4_kernel) replaces the persistent one where the caller asserts that the packed weight
+// carries the transform (select 11: where it pays, 12: forced, with the persistent form forced as by 7), from more than
+// 8 x 128^2 output pixels per launch up: below that, sample lanes, gate heads and batched weight gradients split or merge
+// batches, and both sides of those splits must run one kernel.  SISR_CONV_WINOGRAD=0 switches it off per call.
+#define SISR_WINO_MIN_PIXELS (8L * 128 * 128)
+static inline bool sisr_use_winograd(bool avail, bool force, long pixels) {
+  if (!avail) return false;
+  if (force) return true;
+  const char* e = getenv("SISR_CONV_WINOGRAD");
+  if (e && e[0] == '0') return false;
+  return pixels > SISR_WINO_MIN_PIXELS;
+}
 static inline long sisr_small_grid_blocks() {
   const char* e = getenv("SISR_CONV_TILE_ROWS");
   if (e && e[0] == '4') return 200;
@@ -2419,6 +2724,12 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
                                 const float* gate_add, float* gate_out, const float* dot, int B, int H, int W, int cin,
                                 int cout, const void* ca_tail, int select, void* stream) {
   if (!x || !wpacked || !y || !xview || !yview || B <= 0 || H <= 0 || W <= 0) return SISR_ERR_ARG;
+  // 11 / 12: the Winograd weights follow the direct packing (64 -> 64 only); otherwise as 0 / 7
+  const bool wino_avail = select == 11 || select == 12, wino_force = select == 12;
+  if (wino_avail) {
+    if (cin != 64 || cout != 64) return SISR_ERR_ARG;
+    select = wino_force ? 7 : 0;
+  }
   const sisr_ca_tail_host* tail = static_cast<const sisr_ca_tail_host*>(ca_tail);
   const sisr_ca_tail_host* head = nullptr;
   if (tail && tail->head) {  // gate head: computed by this launch's workgroups from the previous launch's partial sums
@@ -2544,6 +2855,19 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
     if (!head && !tail && sisr_use_persistent(variant, nblk)) {
       const dim3 gp((unsigned)(nblk < 512 ? nblk : 512));
       const size_t lbp = HALO_H * HALO_W * 64 * sizeof(float);
+      if (sisr_use_winograd(wino_avail, wino_force, (long)B * H * W)) {
+        const size_t lbw = lbp + W4_VCHUNK * sizeof(float);
+        const float* wu = wpacked + 64 * 64 * 9;
+#define W4X(RS, GT, DT)                                                                                       \
+  do {                                                                                                        \
+    SISR_ALLOW_LDS((conv3x3_c64_w4_kernel<false, false, RS, GT, DT>), lbw);                                   \
+    hipLaunchKernelGGL((conv3x3_c64_w4_kernel<false, false, RS, GT, DT>), gp, dim3(256), lbw, st, p, (int)nblk, wu); \
+  } while (0)
+        if (gate) { if (rs) W4X(true, true, false); else W4X(false, true, false); }
+        else      { if (rs) W4X(true, false, true); else W4X(false, false, true); }
+#undef W4X
+        return sisr_check_launch();
+      }
 #define P4X(RS, GT, DT) hipLaunchKernelGGL((conv3x3_c64_p4_kernel<false, false, RS, GT, DT>), gp, dim3(256), lbp, st, p, (int)nblk)
       if (gate) { if (rs) P4X(true, true, false); else P4X(false, true, false); }
       else      { if (rs) P4X(true, false, true); else P4X(false, false, true); }
@@ -2609,6 +2933,21 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
       // persistent form (plain 64 -> 64 maps): see conv3x3_c64_p4_kernel
       const dim3 gp((unsigned)(nblk < 512 ? nblk : 512));
       const size_t lbp = HALO_H * HALO_W * 64 * sizeof(float);
+      if (sisr_use_winograd(wino_avail, wino_force, (long)B * H * W)) {
+        const size_t lbw = lbp + W4_VCHUNK * sizeof(float);
+        const float* wu = wpacked + 64 * 64 * 9;
+#define W4K(AF, MK, RS)                                                                                       \
+  do {                                                                                                        \
+    SISR_ALLOW_LDS((conv3x3_c64_w4_kernel<AF, MK, RS, false, false>), lbw);                                   \
+    hipLaunchKernelGGL((conv3x3_c64_w4_kernel<AF, MK, RS, false, false>), gp, dim3(256), lbw, st, p, (int)nblk, wu); \
+  } while (0)
+        if (aff) W4K(true, true, false);
+        else if (msk) W4K(false, true, false);
+        else if (rs) W4K(false, false, true);
+        else W4K(false, false, false);
+#undef W4K
+        return sisr_check_launch();
+      }
 #define P4K(AF, MK, RS) hipLaunchKernelGGL((conv3x3_c64_p4_kernel<AF, MK, RS, false, false>), gp, dim3(256), lbp, st, p, (int)nblk)
       if (aff) P4K(true, true, false);
       else if (msk) P4K(false, true, false);

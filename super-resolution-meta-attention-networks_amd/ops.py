@@ -218,6 +218,11 @@ def _wptr(packed):
 _STEP_PACKS = {}
 
 
+_PACK_WINOGRAD = 0x100  # PackJob.r flag (conv3x3_mfma.hip: SISR_PACK_WINOGRAD)
+WINOGRAD_FLOATS = 16 * 64 * 64  # transformed 64 -> 64 weight, behind the 64 * 64 * 9 direct packing
+SELECT_WINOGRAD, SELECT_WINOGRAD_FORCE = 11, 12  # `select` codes: the packed weight carries the transform (auto / forced)
+
+
 class _PackPlan:
     def __init__(self, weights, device):
         import numpy as np
@@ -228,7 +233,11 @@ class _PackPlan:
         # a weight whose channel counts are not multiples of 64 (SPARNet) is packed as its zero-padded twin, same launch
         padded = [(_pad64(w.shape[0]), _pad64(w.shape[1])) for w, _ in self.items]
         numel = [co * ci * 9 for co, ci in padded]
-        total = planes * sum(numel)
+        # fp32 64 -> 64 weights also get their Winograd F(2x2,3x3) transform right behind the direct packing (both orders);
+        # conv_c64 sees it in the slice length and lets the library use the Winograd kernel where it pays
+        wino = [PRECISION == "fp32" and r == 1 and p == (64, 64) == tuple(w.shape[:2]) for (w, r), p in zip(self.items, padded)]
+        extra = [WINOGRAD_FLOATS if k else 0 for k in wino]
+        total = planes * sum(numel) + sum(extra)
         dt = torch.float32 if PRECISION == "fp32" else torch.bfloat16
         self.fwd = torch.empty(total, device=device, dtype=dt)
         self.dgrad = torch.empty(total, device=device, dtype=dt)
@@ -240,13 +249,13 @@ class _PackPlan:
         off = blocks = 0
         self.slices = []
         for k, (w, r) in enumerate(self.items):
-            n = planes * numel[k]
+            n = planes * numel[k] + extra[k]
             real = (w.shape[0], w.shape[1]) if padded[k] != (w.shape[0], w.shape[1]) else (0, 0)
             jobs[k] = (w.data_ptr(), self.fwd.data_ptr() + off * esz, self.dgrad.data_ptr() + off * esz, padded[k][0],
-                       padded[k][1], r, blocks, real[0], real[1])
+                       padded[k][1], r | (_PACK_WINOGRAD if wino[k] else 0), blocks, real[0], real[1])
             self.slices.append((self.fwd[off:off + n], self.dgrad[off:off + n]))
             off += n
-            blocks += (numel[k] + 255) // 256
+            blocks += (numel[k] + 255) // 256 + (16 if wino[k] else 0)  # + one thread per (ci, co) for the transform
         self.blocks = blocks
         self.jobs = torch.from_numpy(jobs.view(np.uint8)).to(device)
 
@@ -393,6 +402,8 @@ def conv_c64(x, xview, packed, bias, bias_nq, y, yview, B, H, W, cin, cout, res=
     # the packing decides: a weight packed under one mode runs under it (three bf16 planes = the bf16x3 split)
     if packed.dtype != torch.bfloat16:
         import ctypes
+        if select == 0 and cin == 64 and cout == 64 and packed.numel() == 64 * 64 * 9 + WINOGRAD_FLOATS:
+            select = SELECT_WINOGRAD
         rc = L.sisr_conv3x3_c64(hip.ptr(x), xview, _wptr(packed), hip.ptr(bias), bias_nq[0], bias_nq[1], hip.ptr(y), yview,
                                 hip.ptr(res), hip.ptr(mask), hip.ptr(in_scale), hip.ptr(in_shift), hip.ptr(out_scale),
                                 float(alpha), int(relu), hip.ptr(gap), hip.ptr(gate_add), hip.ptr(gate_out), hip.ptr(dot), B,
@@ -1929,7 +1940,7 @@ def _padded_packs(weight, cop, cip, need_dgrad):
     """(forward packing, input-gradient packing | None) of `weight` zero-padded to (cop, cip, 3, 3): the step-level packing
     when the handler has run pack_all (the padding is part of that one launch), else pad + pack here."""
     hit = _step_pack(weight, 1)
-    if hit is not None and hit[0].numel() == cop * cip * 9:
+    if hit is not None and hit[0].numel() - cop * cip * 9 in (0, WINOGRAD_FLOATS):  # the Winograd transform may follow
         return hit[0], (hit[1] if need_dgrad else None)
     wp = _pad_oihw(weight, cop, cip)
     if need_dgrad:
