@@ -64,25 +64,22 @@ int sisr_conv3x3_c64(const float* x, const int64_t* xview, const float* wpacked,
                      const float* in_scale, const float* in_shift, const float* out_scale, float alpha, int relu,
                      float* gap_partial, const float* gate_add, float* gate_out, const float* dot, int B, int H,
                      int W, int cin, int cout, const void* ca_tail, int select, void* stream);
-/* ca_tail (nullable HOST pointer to a sisr_ca_tail, copied into the launch; 64 -> 64 only): the workgroup that finishes a
- * sample last turns the partial sums this launch writes into the channel-attention gate (backward = 0: the forward gate
- * from gap_partial -- sisr_ca_gate_fwd's outputs) or into the gate's backward (backward = 1: from the `dot` partial sums
- * -- sisr_ca_gate_bwd's outputs; the last sample's finisher sums the parameter gradients over the batch).  Same
- * arithmetic and summation order as those two entry points.  counter: B + 1 zero-initialised device words, returned to
- * zero; workspace (backward): B rows of 80 floats (per sample: dz2 [64], then dz1 [hidden <= 16]), so the workspace of a
- * launch over samples b0 .. b1 is rows b0 .. b1 of the whole batch's.
- * head != 0 turns the same record into a gate HEAD: the launch that CONSUMES a gate computes it first -- every workgroup for
- * its own sample, from the partial sums a previous launch wrote (head_part [B][head_parts][64]) -- instead of a gate launch of
- * its own between the two convs: backward = 0 on a gate_add / gate_out launch (in_scale must be g_out: it is filled here, with
- * s_out / hid_out / ca_out), backward = 1 on an in_scale + in_shift + mask launch (in_shift must be `shift`: filled here, with
- * dmul and the workspace; parameter gradients: sisr_ca_gate_bwd_params_batch).  counter and dw / db fields unused. */
+/* ca_tail (nullable HOST pointer to a sisr_ca_tail, copied into the launch; 64 -> 64 fp32, select 0 only): a gate HEAD.  The
+ * launch that CONSUMES a channel-attention gate computes it first -- every workgroup for its own sample, from the partial
+ * sums a previous launch wrote (head_part [B][head_parts][64]) -- instead of a gate launch of its own between the two convs.
+ * Same arithmetic and summation order as sisr_ca_gate_fwd / sisr_ca_gate_bwd.  backward = 0 on a gate_add / gate_out launch
+ * (in_scale must be g_out: it is filled here, with s_out / hid_out / ca_out); backward = 1 on an in_scale + in_shift + mask
+ * launch (in_shift must be `shift`: filled here, with dmul and the workspace, B rows of 80 floats: per sample dz2 [64],
+ * then dz1 [hidden <= 16]; parameter gradients: sisr_ca_gate_bwd_params_batch).  head must be nonzero (a record with
+ * head = 0 is refused with SISR_ERR_UNSUPPORTED); counter, s and dw1 .. db2 are unused.  The record keeps its layout
+ * (sisr_ca_tail_bytes). */
 typedef struct {
   int backward, hidden;
   float inv_hw;
   const float *w1, *b1, *w2, *b2, *mul; /* gate parameters (b1, b2 unused backward), optional second factor [B][64] */
-  const float *s, *hid, *ca;            /* backward: what the forward kept */
+  const float *s, *hid, *ca;            /* backward: what the forward kept (s unused) */
   float *s_out, *hid_out, *ca_out, *g_out;       /* forward outputs */
-  float *shift, *dmul, *dw1, *db1, *dw2, *db2;   /* backward outputs */
+  float *shift, *dmul, *dw1, *db1, *dw2, *db2;   /* backward outputs (dw1 .. db2 unused) */
   float* workspace;
   unsigned* counter;
   const float* head_part;

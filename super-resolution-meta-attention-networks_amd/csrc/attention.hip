@@ -22,7 +22,7 @@ __global__ __launch_bounds__(256) void ca_gate_fwd_kernel(const float* __restric
                                                           float* __restrict__ hid_out, float* __restrict__ ca_out,
                                                           float* __restrict__ g_out) {
   __shared__ __attribute__((aligned(16))) float red[16 * 64];
-  ca_gate_fwd_sample<false>(part, parts, inv_hw, blockIdx.x, w1, b1, w2, b2, R, mul, s_out, hid_out, ca_out, g_out, red);
+  ca_gate_fwd_sample(part, parts, inv_hw, blockIdx.x, w1, b1, w2, b2, R, mul, s_out, hid_out, ca_out, g_out, red);
 }
 
 // ---------------------------------------------------------------- CA gate backward
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void ca_gate_bwd_kernel(const float* __restric
                                                           unsigned* counter, int B) {
   __shared__ __attribute__((aligned(16))) float red[16 * 64];
   __shared__ int is_last;
-  ca_gate_bwd_sample<false>(dgpart, parts, inv_hw, blockIdx.x, w1, w2, R, hid, ca_in, mul, shift, dmul, dz2_out, dz1_out, red);
+  ca_gate_bwd_sample(dgpart, parts, inv_hw, blockIdx.x, w1, w2, R, hid, ca_in, mul, shift, dmul, dz2_out, dz1_out, red);
   if (!dw1) return;  // parameter gradients deferred to sisr_ca_gate_bwd_params_batch (dz2 / dz1 stay in the workspace)
   __threadfence();  // this block's dz2 / dz1 are visible device-wide before it is counted
   __syncthreads();

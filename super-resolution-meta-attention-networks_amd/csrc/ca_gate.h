@@ -1,5 +1,5 @@
-// Channel-attention gate arithmetic shared by the stand-alone gate kernels (attention.hip) and by the conv kernels'
-// last-arriving-workgroup tails (conv3x3_mfma.hip): one code path, one summation order, identical bits either way.
+// Channel-attention gate arithmetic shared by the stand-alone gate kernels (attention.hip) and by the conv kernels' gate
+// heads (conv3x3_mfma.hip): one code path, one summation order, identical bits either way.
 //   forward  (ref: advanced/architectures.py:13-32):  s = mean_hw(t); h = relu(W1 s + b1); ca = sigmoid(W2 h + b2); g = ca [* mul]
 //   backward: see ca_gate_bwd_sample / ca_gate_bwd_params
 #pragma once
@@ -41,39 +41,6 @@ __device__ __forceinline__ float block_sum_parts(const float* __restrict__ pp, i
 }
 
 
-// ---- forward for ONE sample b, executed by a whole 256-thread workgroup.  red: 16 * 64 floats of LDS.
-// part: that sample's [parts][64] partial sums.  NT: read the partials with cache-bypassing loads (they were written by
-// other workgroups of the SAME launch).
-template <bool NT>
-__device__ __forceinline__ float block_sum_parts_t(const float* __restrict__ pp, int parts, float* red) {
-  const int c4 = threadIdx.x & 15, grp = threadIdx.x >> 4;
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  int k = grp;
-  for (; k + 15 * 16 < parts; k += 16 * 16) {
-    f32x4 t[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const f32x4* q = reinterpret_cast<const f32x4*>(pp + (long)(k + 16 * u) * 64 + c4 * 4);
-      t[u] = NT ? __builtin_nontemporal_load(q) : *q;
-    }
-#pragma unroll
-    for (int u = 0; u < 16; ++u) s += t[u];
-  }
-  for (; k < parts; k += 16) {
-    const f32x4* q = reinterpret_cast<const f32x4*>(pp + (long)k * 64 + c4 * 4);
-    s += NT ? __builtin_nontemporal_load(q) : *q;
-  }
-  *reinterpret_cast<f32x4*>(red + grp * 64 + c4 * 4) = s;
-  __syncthreads();
-  float r = 0.f;
-  if (threadIdx.x < 64) {
-    r = red[threadIdx.x];
-#pragma unroll
-    for (int g = 1; g < 16; ++g) r += red[g * 64 + threadIdx.x];
-  }
-  return r;
-}
-
 // Four wave sums at once: the same six exchange steps per value, interleaved (a wave sum is six dependent cross-lane
 // exchanges; the gate's hidden units are independent of each other).  Bit-identical to four calls of wave_sum.
 __device__ __forceinline__ void wave_sum4(float (&v)[4]) {
@@ -87,9 +54,10 @@ __device__ __forceinline__ void wave_sum4(float (&v)[4]) {
   }
 }
 
-// g_lds (optional, 64 floats of LDS outside `red`): the gate is left there too, for a caller that consumes it in the same
-// launch (the conv kernels' gate heads: no store -> load round trip through L2 on the serial path).
-template <bool NT>
+// ---- forward for ONE sample b, executed by a whole 256-thread workgroup.  red: 16 * 64 floats of LDS.
+// part: the [B][parts][64] partial sums.  g_lds (optional, 64 floats of LDS outside `red`): the gate is left there too, for a
+// caller that consumes it in the same launch (the conv kernels' gate heads: no store -> load round trip through L2 on the
+// serial path).
 __device__ __forceinline__ void ca_gate_fwd_sample(const float* __restrict__ part, int parts, float inv_hw, int b,
                                                    const float* __restrict__ w1, const float* __restrict__ b1,
                                                    const float* __restrict__ w2, const float* __restrict__ b2, int R,
@@ -112,7 +80,7 @@ __device__ __forceinline__ void ca_gate_fwd_sample(const float* __restrict__ par
     b2c = b2[c];
     if (mul) mc = mul[b * 64 + c];
   }
-  float s = block_sum_parts_t<NT>(part + (long)b * parts * 64, parts, red);
+  float s = block_sum_parts(part + (long)b * parts * 64, parts, red);
   if (threadIdx.x >= 64) return;
   s *= inv_hw;
   s_out[b * 64 + c] = s;
@@ -154,10 +122,8 @@ __device__ __forceinline__ void ca_gate_fwd_sample(const float* __restrict__ par
 // ---- backward, per sample (whole workgroup):  dg = sum of the partials of sum_hw dOut*t;  dca = dg*mul;
 //   dz2 = dca*ca*(1-ca); dh = W2^T dz2; dz1 = dh*[hid>0]; ds = W1^T dz1  ->  shift[b][c] = ds*inv_hw (the GAP backward
 //   broadcast, consumed as the dgrad / wgrad prologue shift), dmul = dg*ca, and dz2 / dz1 into the workspace: one row of
-//   CA_WS_ROW = 80 floats per sample, dz2 in its first 64, dz1 (R <= 16) behind them -- rows, so that a launch over a range of
-//   samples (a sample lane) writes a plain slice of the whole batch's workspace.  dz1_out = dz2_out + 64.
+//   CA_WS_ROW = 80 floats per sample, dz2 in its first 64, dz1 (R <= 16) behind them.  dz1_out = dz2_out + 64.
 #define CA_WS_ROW 80
-template <bool NT>
 __device__ __forceinline__ void ca_gate_bwd_sample(const float* __restrict__ dgpart, int parts, float inv_hw, int b,
                                                    const float* __restrict__ w1, const float* __restrict__ w2, int R,
                                                    const float* __restrict__ hid, const float* __restrict__ ca_in,
@@ -179,7 +145,7 @@ __device__ __forceinline__ void ca_gate_bwd_sample(const float* __restrict__ dgp
     cac = ca_in[b * 64 + c];
     if (mul) mc = mul[b * 64 + c];
   }
-  const float dg = block_sum_parts_t<NT>(dgpart + (long)b * parts * 64, parts, red);
+  const float dg = block_sum_parts(dgpart + (long)b * parts * 64, parts, red);
   if (threadIdx.x < 64) {
     const float ca = pre ? cac : ca_in[b * 64 + c];
     float dca = dg;

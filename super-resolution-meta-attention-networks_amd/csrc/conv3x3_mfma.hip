@@ -65,28 +65,23 @@ struct ConvParams {
   int bias_n, bias_q;
   int B, H, W, cin_chunks, cout_chunks, relu, tiles_w, tiles_h;
   int mask_leaky;  // relu: 0 none, 1 ReLU, 2 LeakyReLU(0.2); mask_leaky: the mask is LeakyReLU's derivative, not ReLU's
-  // Channel-attention tails (64 -> 64, fp32 kernels): the workgroup that finishes a sample LAST (device-scope counter,
-  // returned to zero) turns the GAP partial sums this launch wrote into the gate (forward: `gap` of a plain conv), or the
-  // DOT partial sums into the gate's backward (per sample; the last sample's finisher then sums the parameter gradients
-  // over the batch).  Same arithmetic and summation order as ca_gate_fwd / ca_gate_bwd (ca_gate.h): which workgroup
-  // does it does not change a bit.  Saves one launch on the serial chain per block and direction.
+  // Gate HEADS (template HEAD of conv3x3_c64_v4_kernel, 64 -> 64 fp32): the CONSUMER of a channel-attention gate computes
+  // it -- every workgroup, for its own sample, from the partial sums the previous launch wrote -- instead of a launch of its
+  // own on the serial chain.  Same arithmetic and summation order as ca_gate_fwd / ca_gate_bwd (ca_gate.h).  fwd_gate: the
+  // gate's operands and outputs (HEAD 1); bwd_gate: the per-sample part of its backward (HEAD 2; the parameter gradients
+  // are summed by a launch of their own).
   struct {
     const float *w1, *b1, *w2, *b2, *mul;
     float *s, *hid, *ca, *g;
-    unsigned* counter;  // [B]
     float inv_hw;
     int R;
-  } fwd_tail;  // active when g != nullptr
+  } fwd_gate;
   struct {
-    const float *w1, *w2, *s, *hid, *ca, *mul;
-    float *shift, *dmul, *dz2, *dz1, *dw1, *db1, *dw2, *db2;
-    unsigned* counter;  // [B + 1]: per sample, then one for the batch
+    const float *w1, *w2, *hid, *ca, *mul;
+    float *shift, *dmul, *dz2, *dz1;
     float inv_hw;
     int R;
-  } bwd_tail;  // active when shift != nullptr
-  // Gate HEADS (template HEAD of conv3x3_c64_v4_kernel): the CONSUMER of a gate computes it -- every workgroup, for its own
-  // sample, from the partial sums the previous launch wrote -- instead of a launch of its own on the serial chain.  The field
-  // blocks above carry the operands (fwd_tail: HEAD 1, bwd_tail: HEAD 2; counters and parameter-gradient fields unused).
+  } bwd_gate;
   const float* head_part;  // [B][head_parts][64]
   int head_parts;
   // Generalised input geometry (template GEO of conv3x3_c64_v4_kernel; all zero elsewhere).  Output pixel (h, w) of the H x W
@@ -389,15 +384,15 @@ __global__ __launch_bounds__(256, KSEL == 3 ? 2 : (MT == 1 ? (GATE ? SISR_GATE_W
   const unsigned boff = hh * 256 + co * 4;
 
   if constexpr (HEAD == 1) {
-    ca_gate_fwd_sample<false>(p.head_part, p.head_parts, p.fwd_tail.inv_hw, b, p.fwd_tail.w1, p.fwd_tail.b1, p.fwd_tail.w2,
-                              p.fwd_tail.b2, p.fwd_tail.R, p.fwd_tail.mul, p.fwd_tail.s, p.fwd_tail.hid, p.fwd_tail.ca,
-                              p.fwd_tail.g, lds, lds + HHv * HWv * 64);
+    ca_gate_fwd_sample(p.head_part, p.head_parts, p.fwd_gate.inv_hw, b, p.fwd_gate.w1, p.fwd_gate.b1, p.fwd_gate.w2,
+                       p.fwd_gate.b2, p.fwd_gate.R, p.fwd_gate.mul, p.fwd_gate.s, p.fwd_gate.hid, p.fwd_gate.ca,
+                       p.fwd_gate.g, lds, lds + HHv * HWv * 64);
     __syncthreads();  // g (= p.in_scale of this launch): 64 floats of LDS behind the halo (launched with SISR_HEAD_LDS more
                       // bytes) hand it to the staging below -- no store -> load round trip; the scratch is free again
   } else if constexpr (HEAD == 2) {
-    ca_gate_bwd_sample<false>(p.head_part, p.head_parts, p.bwd_tail.inv_hw, b, p.bwd_tail.w1, p.bwd_tail.w2, p.bwd_tail.R,
-                              p.bwd_tail.hid, p.bwd_tail.ca, p.bwd_tail.mul, p.bwd_tail.shift, p.bwd_tail.dmul,
-                              p.bwd_tail.dz2, p.bwd_tail.dz1, lds, lds + HHv * HWv * 64);
+    ca_gate_bwd_sample(p.head_part, p.head_parts, p.bwd_gate.inv_hw, b, p.bwd_gate.w1, p.bwd_gate.w2, p.bwd_gate.R,
+                       p.bwd_gate.hid, p.bwd_gate.ca, p.bwd_gate.mul, p.bwd_gate.shift, p.bwd_gate.dmul,
+                       p.bwd_gate.dz2, p.bwd_gate.dz1, lds, lds + HHv * HWv * 64);
     __syncthreads();  // shift (= p.in_shift of this launch), handed over the same way
   }
   int c_begin = 0;
@@ -768,38 +763,6 @@ __global__ __launch_bounds__(256, KSEL == 3 ? 2 : (MT == 1 ? (GATE ? SISR_GATE_W
     }
   }
 #endif
-  if (HEAD == 0 && (p.fwd_tail.g || p.bwd_tail.shift)) {  // uniform
-    const long parts = (long)p.tiles_w * ((H + 3) / 4) * 2;
-    const unsigned per_sample = gridDim.x / (unsigned)p.B;  // workgroups of one sample (cout_chunks == 1 here)
-    unsigned* cnt = p.fwd_tail.g ? p.fwd_tail.counter : p.bwd_tail.counter;
-    int* flag = reinterpret_cast<int*>(lds);
-    float* red = lds + 64;
-    __threadfence();  // this workgroup's partial sums are visible device-wide before it is counted
-    __syncthreads();  // ... and every wave is done with the halo / strip exchange in LDS
-    if (tid == 0) flag[0] = atomicAdd(cnt + b, 1u) == per_sample - 1;
-    __syncthreads();
-    if (!flag[0]) return;
-    __threadfence();
-    if (tid == 0) cnt[b] = 0u;
-    if (p.fwd_tail.g) {
-      ca_gate_fwd_sample<true>(p.gap, (int)parts, p.fwd_tail.inv_hw, b, p.fwd_tail.w1, p.fwd_tail.b1, p.fwd_tail.w2,
-                               p.fwd_tail.b2, p.fwd_tail.R, p.fwd_tail.mul, p.fwd_tail.s, p.fwd_tail.hid, p.fwd_tail.ca,
-                               p.fwd_tail.g, red);
-    } else {
-      ca_gate_bwd_sample<true>(p.gap, (int)parts, p.bwd_tail.inv_hw, b, p.bwd_tail.w1, p.bwd_tail.w2, p.bwd_tail.R,
-                               p.bwd_tail.hid, p.bwd_tail.ca, p.bwd_tail.mul, p.bwd_tail.shift, p.bwd_tail.dmul,
-                               p.bwd_tail.dz2, p.bwd_tail.dz1, red);
-      __threadfence();  // this sample's dz2 / dz1 before it is counted on the batch counter
-      __syncthreads();
-      if (tid == 0) flag[0] = atomicAdd(cnt + p.B, 1u) == (unsigned)(p.B - 1);
-      __syncthreads();
-      if (!flag[0]) return;
-      __threadfence();
-      if (tid == 0) cnt[p.B] = 0u;
-      ca_gate_bwd_params(p.bwd_tail.dz2, p.bwd_tail.dz1, p.bwd_tail.hid, p.bwd_tail.s, p.bwd_tail.R, p.B, p.bwd_tail.dw1,
-                         p.bwd_tail.db1, p.bwd_tail.dw2, p.bwd_tail.db2);
-    }
-  }
 }
 
 // ------------------------------------------------------------------ persistent form of the fp32 kernel (round 3)
@@ -812,7 +775,7 @@ __global__ __launch_bounds__(256, KSEL == 3 ? 2 : (MT == 1 ? (GATE ? SISR_GATE_W
 // once per launch and its only non-MFMA time per tile is epilogue + LDS writes, which the other resident workgroup's K loop
 // covers.  Same tile geometry, LDS image, K loop, prologue / epilogue arithmetic and summation order as the per-tile kernel:
 // bit-identical results.  64 -> 64 maps only (one input chunk); grids too small to give every workgroup two tiles, gate
-// heads / tails, LeakyReLU and the sparse selections stay on the per-tile kernel.
+// heads, LeakyReLU and the sparse selections stay on the per-tile kernel.
 template <bool AFFINE, bool MASK, bool RES, bool GATE, bool DOT>
 __global__ __launch_bounds__(256, 2) void conv3x3_c64_p4_kernel(ConvParams p, int total_tiles) {
   constexpr int MT = 2, THv = 4, HHv = 6;
@@ -2678,8 +2641,8 @@ static inline bool sisr_use_persistent(int variant, long nblk) {
 }
 // The Winograd form (conv3x3_c64_w4_kernel) replaces the persistent one where the caller asserts that the packed weight
 // carries the transform (select 11: where it pays, 12: forced, with the persistent form forced as by 7), from more than
-// 8 x 128^2 output pixels per launch up: below that, sample lanes, gate heads and batched weight gradients split or merge
-// batches, and both sides of those splits must run one kernel.  SISR_CONV_WINOGRAD=0 switches it off per call.
+// 8 x 128^2 output pixels per launch up: below that, gate heads and batched weight gradients change how a batch is
+// launched, and both forms must run one kernel.  SISR_CONV_WINOGRAD=0 switches it off per call.
 #define SISR_WINO_MIN_PIXELS (8L * 128 * 128)
 static inline bool sisr_use_winograd(bool avail, bool force, long pixels) {
   if (!avail) return false;
@@ -2695,7 +2658,8 @@ static inline long sisr_small_grid_blocks() {
   if (const char* n = getenv("SISR_CONV_SMALL_BLOCKS")) return atol(n);
   return 0x7fffffffL;
 }
-// Host-side description of a channel-attention tail (include/sisr_hip.h: sisr_ca_tail).
+// Host-side description of a gate head (include/sisr_hip.h: sisr_ca_tail; head must be nonzero, `s`, dw1..db2 and
+// `counter` are unused).
 struct sisr_ca_tail_host {
   int backward, hidden;
   float inv_hw;
@@ -2730,27 +2694,15 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
     if (cin != 64 || cout != 64) return SISR_ERR_ARG;
     select = wino_force ? 7 : 0;
   }
-  const sisr_ca_tail_host* tail = static_cast<const sisr_ca_tail_host*>(ca_tail);
-  const sisr_ca_tail_host* head = nullptr;
-  if (tail && tail->head) {  // gate head: computed by this launch's workgroups from the previous launch's partial sums
-    head = tail;
-    tail = nullptr;
-    if (cin != 64 || cout != 64 || !head->head_part || head->head_parts <= 0 || head->hidden < 1 || head->hidden > 16 || select != 0)
+  const sisr_ca_tail_host* head = static_cast<const sisr_ca_tail_host*>(ca_tail);
+  if (head) {  // gate head: computed by this launch's workgroups from the previous launch's partial sums
+    if (!head->head || cin != 64 || cout != 64 || !head->head_part || head->head_parts <= 0 || head->hidden < 1 ||
+        head->hidden > 16 || select != 0)
       return SISR_ERR_UNSUPPORTED;
     if (head->backward ? (!mask || !in_scale || in_shift != head->shift || !head->w1 || !head->w2 || !head->hid || !head->ca ||
                           !head->shift || !head->workspace || (head->mul && !head->dmul) || gate_add || dot)
                        : (!gate_add || !gate_out || in_scale != head->g_out || !head->w1 || !head->b1 || !head->w2 || !head->b2 ||
                           !head->s_out || !head->hid_out || !head->ca_out || !head->g_out))
-      return SISR_ERR_ARG;
-  }
-  if (tail) {  // only on the issue-lean 64 -> 64 kernels, from the partial sums this launch writes
-    if (cin != 64 || cout != 64 || !gap_partial || !tail->counter || tail->hidden < 1 || tail->hidden > 16 || select == 2)
-      return SISR_ERR_UNSUPPORTED;
-    if (tail->backward ? (!dot || !tail->w1 || !tail->w2 || !tail->s || !tail->hid || !tail->ca || !tail->shift ||
-                          !tail->dw1 || !tail->db1 || !tail->dw2 || !tail->db2 || !tail->workspace ||
-                          (tail->mul && !tail->dmul))
-                       : (dot || gate_add || mask || res || in_scale || out_scale || !tail->w1 || !tail->b1 || !tail->w2 ||
-                          !tail->b2 || !tail->s_out || !tail->hid_out || !tail->ca_out || !tail->g_out))
       return SISR_ERR_ARG;
   }
   // select (per call; the library keeps no state): 0 / 4 = issue-lean kernel, tile height by grid size, general kernel
@@ -2808,33 +2760,21 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
   p.relu = relu & 3;
   p.mask_leaky = (relu & 4) != 0;
   const bool leaky = p.relu == 2 || p.mask_leaky;
-  if (leaky && (tail || gate_add || gate_out || dot || in_scale || in_shift || (p.relu == 2 && (mask || res)) ||
+  if (leaky && (gate_add || gate_out || dot || in_scale || in_shift || (p.relu == 2 && (mask || res)) ||
                 (p.mask_leaky && res)))
     return SISR_ERR_UNSUPPORTED;
-  if (tail && !tail->backward) {
-    p.fwd_tail.w1 = tail->w1; p.fwd_tail.b1 = tail->b1; p.fwd_tail.w2 = tail->w2; p.fwd_tail.b2 = tail->b2;
-    p.fwd_tail.mul = tail->mul; p.fwd_tail.s = tail->s_out; p.fwd_tail.hid = tail->hid_out; p.fwd_tail.ca = tail->ca_out;
-    p.fwd_tail.g = tail->g_out; p.fwd_tail.counter = tail->counter; p.fwd_tail.inv_hw = tail->inv_hw;
-    p.fwd_tail.R = tail->hidden;
-  } else if (tail) {
-    p.bwd_tail.w1 = tail->w1; p.bwd_tail.w2 = tail->w2; p.bwd_tail.s = tail->s; p.bwd_tail.hid = tail->hid;
-    p.bwd_tail.ca = tail->ca; p.bwd_tail.mul = tail->mul; p.bwd_tail.shift = tail->shift; p.bwd_tail.dmul = tail->dmul;
-    p.bwd_tail.dz2 = tail->workspace; p.bwd_tail.dz1 = tail->workspace + 64;
-    p.bwd_tail.dw1 = tail->dw1; p.bwd_tail.db1 = tail->db1; p.bwd_tail.dw2 = tail->dw2; p.bwd_tail.db2 = tail->db2;
-    p.bwd_tail.counter = tail->counter; p.bwd_tail.inv_hw = tail->inv_hw; p.bwd_tail.R = tail->hidden;
-  }
   if (head) {
     p.head_part = head->head_part;
     p.head_parts = head->head_parts;
     if (!head->backward) {
-      p.fwd_tail.w1 = head->w1; p.fwd_tail.b1 = head->b1; p.fwd_tail.w2 = head->w2; p.fwd_tail.b2 = head->b2;
-      p.fwd_tail.mul = head->mul; p.fwd_tail.s = head->s_out; p.fwd_tail.hid = head->hid_out; p.fwd_tail.ca = head->ca_out;
-      p.fwd_tail.g = head->g_out; p.fwd_tail.inv_hw = head->inv_hw; p.fwd_tail.R = head->hidden;
+      p.fwd_gate.w1 = head->w1; p.fwd_gate.b1 = head->b1; p.fwd_gate.w2 = head->w2; p.fwd_gate.b2 = head->b2;
+      p.fwd_gate.mul = head->mul; p.fwd_gate.s = head->s_out; p.fwd_gate.hid = head->hid_out; p.fwd_gate.ca = head->ca_out;
+      p.fwd_gate.g = head->g_out; p.fwd_gate.inv_hw = head->inv_hw; p.fwd_gate.R = head->hidden;
     } else {
-      p.bwd_tail.w1 = head->w1; p.bwd_tail.w2 = head->w2; p.bwd_tail.hid = head->hid; p.bwd_tail.ca = head->ca;
-      p.bwd_tail.mul = head->mul; p.bwd_tail.shift = head->shift; p.bwd_tail.dmul = head->dmul;
-      p.bwd_tail.dz2 = head->workspace; p.bwd_tail.dz1 = head->workspace + 64;
-      p.bwd_tail.inv_hw = head->inv_hw; p.bwd_tail.R = head->hidden;
+      p.bwd_gate.w1 = head->w1; p.bwd_gate.w2 = head->w2; p.bwd_gate.hid = head->hid; p.bwd_gate.ca = head->ca;
+      p.bwd_gate.mul = head->mul; p.bwd_gate.shift = head->shift; p.bwd_gate.dmul = head->dmul;
+      p.bwd_gate.dz2 = head->workspace; p.bwd_gate.dz1 = head->workspace + 64;
+      p.bwd_gate.inv_hw = head->inv_hw; p.bwd_gate.R = head->hidden;
     }
   }
   p.tiles_w = (W + TW - 1) / TW;
@@ -2852,7 +2792,7 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
     if (memcmp(xview, yview, 6 * sizeof(int64_t)) != 0) return SISR_ERR_UNSUPPORTED;  // skip / dot share one layout
     hipStream_t st = (hipStream_t)stream;
     const bool rs = res != nullptr;
-    if (!head && !tail && sisr_use_persistent(variant, nblk)) {
+    if (!head && sisr_use_persistent(variant, nblk)) {
       const dim3 gp((unsigned)(nblk < 512 ? nblk : 512));
       const size_t lbp = HALO_H * HALO_W * 64 * sizeof(float);
       if (sisr_use_winograd(wino_avail, wino_force, (long)B * H * W)) {
@@ -2928,7 +2868,7 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
 #undef V4K
       return sisr_check_launch();
     }
-    if (!(in_shift && !in_scale) && !(aff && !msk) && !(msk && rs) && !leaky && !head && !tail && cin == 64 && cout == 64 &&
+    if (!(in_shift && !in_scale) && !(aff && !msk) && !(msk && rs) && !leaky && !head && cin == 64 && cout == 64 &&
         memcmp(xview, yview, 6 * sizeof(int64_t)) == 0 && p.xv.clo == 64 && p.xv.chi == 0 && sisr_use_persistent(variant, nblk)) {
       // persistent form (plain 64 -> 64 maps): see conv3x3_c64_p4_kernel
       const dim3 gp((unsigned)(nblk < 512 ? nblk : 512));
@@ -2997,12 +2937,12 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
         hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, false, 2>), grid, dim3(256), lb, st, p);
       return sisr_check_launch();
     }
-    if (tail || head) return SISR_ERR_UNSUPPORTED;  // the general kernel has neither tails nor heads
+    if (head) return SISR_ERR_UNSUPPORTED;  // the general kernel has no heads
     const size_t lb = HALO_H * HALO_W * 64 * sizeof(float);
     hipLaunchKernelGGL(conv3x3_c64_kernel<0>, grid, dim3(256), lb, st, p);
     return sisr_check_launch();
   }
-  if (tail || head) return SISR_ERR_UNSUPPORTED;
+  if (head) return SISR_ERR_UNSUPPORTED;
   const size_t lb = HALO_H * HALO_W * 64 * sizeof(float);
 #ifdef SISR_DIAG
   if (variant == 13)

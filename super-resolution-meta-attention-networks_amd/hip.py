@@ -207,26 +207,12 @@ class WgradGeoJob(ctypes.Structure):
 
 
 class CaTail(ctypes.Structure):
-    """Host mirror of sisr_ca_tail (include/sisr_hip.h): the channel-attention gate computed by the last-arriving
-    workgroup of the conv launch that writes its partial sums."""
+    """Host mirror of sisr_ca_tail (include/sisr_hip.h): a gate head -- the channel-attention gate, or the per-sample part
+    of its backward, computed by the conv launch that consumes it (head = 1; counter, s and dw1..db2 are unused)."""
     _fields_ = [("backward", c_int), ("hidden", c_int), ("inv_hw", c_float)] + \
                [(n, c_void_p) for n in ("w1", "b1", "w2", "b2", "mul", "s", "hid", "ca", "s_out", "hid_out", "ca_out", "g_out",
                                         "shift", "dmul", "dw1", "db1", "dw2", "db2", "workspace", "counter", "head_part")] + \
                [("head_parts", c_int), ("head", c_int)]
-
-
-_tail_counters = {}
-
-
-def tail_counter(device, B):
-    """Zero-initialised device words the tails count workgroups on (B per-sample words + one for the batch; every launch
-    returns them to zero; one set per device and batch size: tails only run on the stream that drives the pass)."""
-    key = (device.index, B)
-    c = _tail_counters.get(key)
-    if c is None:
-        c = torch.zeros(B + 1, device=device, dtype=torch.int32)
-        _tail_counters[key] = c
-    return c.data_ptr()
 
 
 class HipLibraryMissing(ImportError):

@@ -39,9 +39,6 @@ CL = torch.channels_last
 # stream once, at the end of the backward pass (autograd engine callback), before anything reads the grads.
 # (Measured +5 % at 16 tiles per GPU when introduced; neutral at 32 with the current kernels -- see DESIGN.md §3.)
 WGRAD_SIDE_STREAM = os.environ.get("SISR_WGRAD_SIDE_STREAM", "1") != "0"
-# weight gradients as parallel branches of a captured backward: measured SLOWER than one serial stream at 4 tiles per
-# GPU (QRCAN, one-rank RCCL world: 48.0 vs 51.5 patches/s -- every cross-branch edge costs a barrier packet), so off
-GRAPH_FORK = os.environ.get("SISR_GRAPH_FORK", "0") != "0"
 IN_BACKWARD = False  # set while a conv operator's backward runs (bench.py times forward launches only)
 _side_streams = {}
 _join_pending = set()
@@ -77,40 +74,6 @@ def _on_side(device, after_event, fn, tensors):
         torch.autograd.Variable._execution_engine.queue_callback(lambda: _join_side(device))
 
 
-_side_groups = {}  # device index -> [(fn, tensors)] waiting for their group's fork
-
-
-def _on_side_grouped(device, fn, tensors, group):
-    """_on_side for many small launches: every cross-stream edge costs a barrier packet (a parallel branch per launch was
-    measured slower than no branch at all), so the launches wait and go to the side stream `group` at a time behind ONE
-    event; what is left goes out, and the side stream is joined, when the backward pass ends."""
-    lst = _side_groups.get(device.index)
-    if lst is None:
-        lst = _side_groups[device.index] = []
-        torch.autograd.Variable._execution_engine.queue_callback(lambda: _flush_side_group(device, final=True))
-    lst.append((fn, tensors))
-    if len(lst) >= group:
-        _flush_side_group(device)
-
-
-def _flush_side_group(device, final=False):
-    lst = _side_groups.get(device.index)
-    if final:
-        _side_groups.pop(device.index, None)
-    elif lst is not None:
-        _side_groups[device.index] = []
-    if lst:
-        ev = torch.cuda.Event()
-        ev.record()
-
-        def run():
-            for fn, _ in lst:
-                fn()
-        _on_side(device, ev, run, [t for _, ts in lst for t in ts])
-    if final:
-        _join_side(device)
-
-
 def _cl(x):
     return x if x.is_contiguous(memory_format=CL) else x.contiguous(memory_format=CL)
 
@@ -139,7 +102,7 @@ def _grad_buf_or(p, n, device):
     return _grad_buf(p) if p is not None else torch.empty(n, device=device)
 
 
-def _side_ok(*weights, pixels=None, fork=False):
+def _side_ok(*weights, pixels=None):
     """pixels (B * H * W of the launches): inside a deferred_wgrads() block small weight gradients are queued for batched
     launches on the main stream instead (a queue flushed from the side stream would read operands the allocator only tracks
     on the main stream).
@@ -152,9 +115,8 @@ def _side_ok(*weights, pixels=None, fork=False):
         return False
     if _DEFERRED is not None and pixels is not None and PRECISION == "fp32" and pixels <= BATCH_WGRAD_MAX_PIXELS:
         return False
-    # under hipGraph capture the fork / join would become graph edges (SISR_GRAPH_FORK=1); default: one stream.  fork=True: a
-    # caller whose launches leave most of the chip idle (SPARNet's small maps) asks for the branch under capture as well
-    return GRAPH_FORK or fork or not torch.cuda.is_current_stream_capturing()
+    # under hipGraph capture the fork / join would become graph edges (measured slower than one stream): one stream there
+    return not torch.cuda.is_current_stream_capturing()
 
 
 _gate_ws_cache = {}
@@ -187,15 +149,6 @@ def _vec(B, C, device):
 # Process-wide; packed weights are rebuilt every step, so switching between steps is safe.
 PRECISION = os.environ.get("SISR_PRECISION", "fp32")
 X3_WGRAD = os.environ.get("SISR_X3_WGRAD", "1") != "0"  # bf16x3 mode: weight gradients split too (0: exact fp32 kernel)
-# Channel-attention gate (and its backward) computed by the last-arriving workgroup of the conv launch that produces its
-# partial sums, instead of by a launch of its own on the serial chain ("1" always, "auto" = launches of at most
-# CA_TAIL_MAX_BLOCKS workgroups, "0" never).  Bit-identical, but MEASURED SLOWER on MI355X (QRCAN B = 4: 43.7 vs 58.2
-# patches/s; RCAN B = 32: 50.6 vs 75.0): the device-scope release every workgroup needs before it is counted
-# (__threadfence = L2 write-back on a part whose 8 XCDs have private L2s) flushes the conv's freshly written output
-# lines and stalls the wave, which costs far more than the 6-14 us launch it saves.  Default off; kept as the measured
-# negative (profiles/r02_ca_tail.json).
-CA_TAIL = os.environ.get("SISR_CA_TAIL", "0")
-CA_TAIL_MAX_BLOCKS = 1024
 FUSED_GROUPS = os.environ.get("SISR_FUSED_GROUPS", "1") != "0"  # group-level autograd node for CA block stacks
 
 
@@ -397,7 +350,9 @@ def pack_pair(w, shuffle=1):
 
 def conv_c64(x, xview, packed, bias, bias_nq, y, yview, B, H, W, cin, cout, res=None, mask=None, in_scale=None,
              in_shift=None, out_scale=None, alpha=1.0, relu=False, gap=None, gate_add=None, gate_out=None, dot=None,
-             select=0, ca_tail=None):
+             select=0, ca_head=None):
+    """ca_head: an fp32 gate head (hip.CaTail with head = 1): the channel-attention gate, or the per-sample part of its
+    backward, computed by this conv from the partial sums it consumes."""
     L = hip.lib()
     # the packing decides: a weight packed under one mode runs under it (three bf16 planes = the bf16x3 split)
     if packed.dtype != torch.bfloat16:
@@ -407,12 +362,12 @@ def conv_c64(x, xview, packed, bias, bias_nq, y, yview, B, H, W, cin, cout, res=
         rc = L.sisr_conv3x3_c64(hip.ptr(x), xview, _wptr(packed), hip.ptr(bias), bias_nq[0], bias_nq[1], hip.ptr(y), yview,
                                 hip.ptr(res), hip.ptr(mask), hip.ptr(in_scale), hip.ptr(in_shift), hip.ptr(out_scale),
                                 float(alpha), int(relu), hip.ptr(gap), hip.ptr(gate_add), hip.ptr(gate_out), hip.ptr(dot), B,
-                                H, W, cin, cout, ctypes.addressof(ca_tail) if ca_tail is not None else None, int(select),
+                                H, W, cin, cout, ctypes.addressof(ca_head) if ca_head is not None else None, int(select),
                                 hip.stream())
         hip.check(rc, "sisr_conv3x3_c64")
         return
-    if ca_tail is not None:
-        raise RuntimeError("channel-attention tails exist on the fp32 conv kernels only")
+    if ca_head is not None:
+        raise RuntimeError("gate heads exist on the fp32 conv kernels only")
     if packed.numel() == 3 * cin * cout * 9:
         fn, name = L.sisr_conv3x3_c64_x3, "sisr_conv3x3_c64_x3"
     else:
@@ -658,32 +613,6 @@ class WgradGeoQueue:
 
 def gap_parts(H, W):
     return hip.lib().sisr_conv3x3_c64_gap_parts(H, W)
-
-
-def _use_ca_tail(B, H, W):
-    if PRECISION != "fp32" or CA_TAIL == "0":
-        return False
-    return CA_TAIL == "1" or B * ((H + 3) // 4) * ((W + 31) // 32) <= CA_TAIL_MAX_BLOCKS
-
-
-def _tail_fwd(B, H, W, R, caw1c, cab1, caw2c, cab2, mm, sv, hid, ca, g, dev):
-    t = hip.CaTail()
-    t.backward, t.hidden, t.inv_hw = 0, R, 1.0 / (H * W)
-    t.w1, t.b1, t.w2, t.b2, t.mul = hip.ptr(caw1c), hip.ptr_c(cab1), hip.ptr(caw2c), hip.ptr_c(cab2), hip.ptr(mm)
-    t.s_out, t.hid_out, t.ca_out, t.g_out = hip.ptr(sv), hip.ptr(hid), hip.ptr(ca), hip.ptr(g)
-    t.counter = hip.tail_counter(dev, B)
-    return t
-
-
-def _tail_bwd(B, H, W, R, caw1c, caw2c, s, hid, ca, mm, shift, dmv, dcaw1, dcab1, dcaw2, dcab2, dev):
-    t = hip.CaTail()
-    t.backward, t.hidden, t.inv_hw = 1, R, 1.0 / (H * W)
-    t.w1, t.w2, t.mul = hip.ptr(caw1c), hip.ptr(caw2c), hip.ptr(mm)
-    t.s, t.hid, t.ca = hip.ptr(s), hip.ptr(hid), hip.ptr(ca)
-    t.shift, t.dmul = hip.ptr(shift), hip.ptr(dmv)
-    t.dw1, t.db1, t.dw2, t.db2 = hip.ptr(dcaw1), hip.ptr(dcab1), hip.ptr(dcaw2), hip.ptr(dcab2)
-    t.workspace, t.counter = hip.ptr(_gate_ws(B, dev)), hip.tail_counter(dev, B)
-    return t
 
 
 # ----------------------------------------------------------------------------- conv3x3
@@ -1184,74 +1113,7 @@ class _ResBlock(Function):
             IN_BACKWARD = False
 
 
-# Sample lanes.  The tiles of a minibatch never meet inside a residual group (no batch statistics on the path), so the chain of
-# B-tile launches of a group can run as LANES chains of B / LANES tiles on LANES streams -- parallel branches of the captured
-# step.  At 4 tiles per GPU a single chain fills the chip with ONE round of workgroups that stage, multiply and store in
-# lock-step (43 - 51 us per launch in the step against 31 us of MFMA time); two chains drift out of phase and one's K loops
-# cover the other's staging and stores (tools/lane_probe.py: 38.7 -> 36.7 us per 4-tile link, mask form 40.5 -> 37.6).
-# Used where launches are small AND the step is replayed from a hipGraph (eager launches at these sizes are host-bound and
-# lanes double their number); the weight gradients stay whole-batch launches: the lanes meet before every batch of eight.
-LANES = int(os.environ.get("SISR_LANES", 1))  # measured: no gain inside the replayed step (DESIGN.md 9.1), so one chain by default
-LANES_EAGER = os.environ.get("SISR_LANES_EAGER", "0") != "0"  # tests / probes: lanes outside a capture too
-LANES_MAX_PIXELS = int(os.environ.get("SISR_LANES_MAX_PIXELS", 8 * 128 * 128))
-LANES_INTERLEAVE = os.environ.get("SISR_LANES_INTERLEAVE", "1") != "0"  # issue the lanes' launches block by block, alternating
-_lane_streams = {}
-
-
-def _lane_cuts(B, H, W):
-    """[(b0, b1)] sample ranges of the lanes of a group launch chain ([(0, B)]: one chain on the calling stream)."""
-    if (LANES < 2 or B % LANES or PRECISION != "fp32" or not WgradQueue.wanted(B, H, W) or B * H * W > LANES_MAX_PIXELS
-            or _use_ca_tail(B, H, W) or not (LANES_EAGER or torch.cuda.is_current_stream_capturing())):
-        return [(0, B)]
-    return [(B * k // LANES, B * (k + 1) // LANES) for k in range(LANES)]
-
-
-class _Lanes:
-    """Lane 0 is the calling stream; lanes 1.. are side streams forked from it (fork()) and joined back into it (join()).
-    Every buffer a lane touches is allocated on the calling stream BEFORE the fork and released after the join, so the caching
-    allocator's stream-ordered reuse stays sound."""
-
-    def __init__(self, device, cuts):
-        self.cuts, self.main = cuts, torch.cuda.current_stream(device)
-        pool = _lane_streams.setdefault(device.index, [])
-        while len(pool) < len(cuts) - 1:
-            pool.append(torch.cuda.Stream(device=device))
-        self.side = pool[:len(cuts) - 1]
-
-    def fork(self):
-        for s in self.side:
-            s.wait_stream(self.main)
-
-    def join(self):
-        for s in self.side:
-            self.main.wait_stream(s)
-
-    def run(self, fn):
-        """fn(b0, b1) once per lane, each on its stream.  A generator function is advanced round-robin -- lane 0 up to its
-        first yield, lane 1 up to its first yield, ... -- so that the lanes' launches are issued (and captured) interleaved,
-        block by block, instead of one whole chain after the other."""
-        gens = []
-        for k, (b0, b1) in enumerate(self.cuts):
-            if k == 0:
-                g = fn(b0, b1)
-            else:
-                with torch.cuda.stream(self.side[k - 1]):
-                    g = fn(b0, b1)
-            if hasattr(g, "__next__"):
-                gens.append((k, g))
-        while gens:
-            alive = []
-            for k, g in gens:
-                try:
-                    if k == 0:
-                        next(g)
-                    else:
-                        with torch.cuda.stream(self.side[k - 1]):
-                            next(g)
-                    alive.append((k, g))
-                except StopIteration:
-                    pass
-            gens = alive
+LANES = 1  # bench.py reports this as `sample_lanes`: one launch chain per residual group (sample lanes tied and were removed)
 
 
 class _GatedGroup(Function):
@@ -1266,10 +1128,9 @@ class _GatedGroup(Function):
     halo staging, and the gate gradient  sum(dU_k * t2_k)  is taken by the PREVIOUS backward conv's epilogue while
     it produces dU_k.  Per block that removes two HBM-bound launches (3 + 2 map passes with the MFMA units idle).
 
-    Both passes are written as a chain over a sample range [b0, b1) of buffers allocated for the whole batch: one chain over
-    all samples on the calling stream, or (small launches inside a hipGraph capture, _lane_cuts) one chain per sample lane on
-    parallel streams -- every launch of a lane is the same kernel on a contiguous slice of the batch, so results do not depend
-    on the number of lanes (bit-identical)."""
+    Both passes are one chain of launches over the whole batch on the calling stream.  The channel-attention gate (and its
+    backward) is a launch of its own between two convs, or, while launches are small (GATE_HEADS), a head of the conv that
+    consumes it."""
 
     PER = 9  # w1, b1, w2, b2, caw1, cab1, caw2, cab2, m
 
@@ -1291,20 +1152,18 @@ class _GatedGroup(Function):
         v = hip.view_plain(H, W, 64)
         need = any(ctx.needs_input_grad)
         parts = gap_parts(H, W)
-        tails = has_ca and _use_ca_tail(B, H, W)
-        heads = has_ca and GATE_HEADS and not tails and WgradQueue.wanted(B, H, W) and B * H * W <= GATE_HEADS_MAX_PIXELS
+        heads = has_ca and GATE_HEADS and WgradQueue.wanted(B, H, W) and B * H * W <= GATE_HEADS_MAX_PIXELS
         PER = _GatedGroup.PER
-        lanes = _Lanes(dev, _lane_cuts(B, H, W))
         # bf16 operand mode with bf16 storage: the maps this group keeps (t1, t2, the gated skips) are bf16 in HBM
-        st16 = PRECISION == "bf16" and BF16_STORAGE in ("act", "all") and not tails and not heads
+        st16 = PRECISION == "bf16" and BF16_STORAGE in ("act", "all") and not heads
         new_map = _empty_cl16 if st16 else _empty_cl
         x_in = to_bf16_map(x) if st16 else x  # block 0's input and first skip, in the group's storage format
 
-        def conv(xx, pk, bias, yy, Bl, storage, **kw):
-            if st16:
-                conv_c64s(xx, pk, bias, yy, Bl, H, W, storage, **kw)
+        def conv(xx, pk, bias, yy, storage, head=None, **kw):
+            if st16:  # (no gate heads there)
+                conv_c64s(xx, pk, bias, yy, B, H, W, storage, **kw)
             else:
-                conv_c64(xx, v, pk, bias, (1, 64), yy, v, Bl, H, W, 64, 64, **kw)
+                conv_c64(xx, v, pk, bias, (1, 64), yy, v, B, H, W, 64, 64, ca_head=head, **kw)
 
         def pack(w):
             return pack_pair(w) if need else (pack_weight(w, "fwd"), None)
@@ -1329,7 +1188,7 @@ class _GatedGroup(Function):
                 blk = [d["u"], w1, w2, d["t1"], d["t2"], d["caw1c"], d["caw2c"], d["sv"], d["hid"], d["ca"], d["g"]]
                 if d["mm"] is not None:
                     blk.append(d["mm"])
-                meta.append((len(blk), d["mm"] is not None, tuple(caw1.shape), tuple(caw2.shape)))
+                meta.append((len(blk), d["mm"] is not None))
             else:
                 mm = m.contiguous()
                 # gs = alpha * m: the scale of the gradient entering conv2 (its input gradient and its weight gradient both
@@ -1338,7 +1197,7 @@ class _GatedGroup(Function):
                          u=new_map(B, 64, H, W, dev) if k > 0 else x_in, gap=None, mm=mm, g=mm,
                          gs=mm if alpha == 1.0 else gs_all[k], sv=None, hid=None, ca=None)
                 blk = [d["u"], w1, w2, d["t1"], d["t2"], d["g"], d["gs"]]
-                meta.append((len(blk), True, None, None))
+                meta.append((len(blk), True))
             blks.append(d)
             small.append((b1, b2, caw1, cab1, caw2, cab2))
             tensors += blk
@@ -1347,61 +1206,35 @@ class _GatedGroup(Function):
         wt = wt.contiguous()
         pt, pdt = pack(wt)
         un, out = new_map(B, 64, H, W, dev), _empty_cl(B, 64, H, W, dev)
-        keep = []  # argument records the launches of a lane point into
-        interleave = len(lanes.cuts) > 1 and LANES_INTERLEAVE
 
-        def chain(b0, b1):
-            """The group's forward launches on samples [b0, b1) (a generator: with several lanes it yields after every block)."""
-            sl, Bl = slice(b0, b1), b1 - b0
-            pend = None  # (t2, g, gate head) of the block whose gated skip the next conv builds
-            for k in range(n):
-                d = blks[k]
-                t1, t2, g = d["t1"][sl], d["t2"][sl], d["g"][sl]
-                gap, sv, hid, ca = (d[key][sl] if has_ca else None for key in ("gap", "sv", "hid", "ca"))
-                mm = d["mm"][sl] if d["mm"] is not None else None
-                if pend is None:
-                    conv(x_in[sl], d["p1"], d["b1"], t1, Bl, 3, relu=True)
-                elif st16:
-                    conv(pend[0], d["p1"], d["b1"], t1, Bl, 3, relu=True, in_scale=pend[1], gate_add=blks[k - 1]["u"][sl],
-                         gate_out=d["u"][sl])
-                else:
-                    conv_c64(pend[0], v, d["p1"], d["b1"], (1, 64), t1, v, Bl, H, W, 64, 64, relu=True, in_scale=pend[1],
-                             gate_add=blks[k - 1]["u"][sl], gate_out=d["u"][sl], ca_tail=pend[2])
-                hd = None
-                if not has_ca:  # the gate is the meta-attention vector: nothing to pool, nothing to launch
-                    conv(t1, d["p2"], d["b2"], t2, Bl, 3, alpha=alpha)
-                elif tails:  # the gate is computed by conv2's last-arriving workgroup per sample
-                    conv_c64(t1, v, d["p2"], d["b2"], (1, 64), t2, v, Bl, H, W, 64, 64, gap=gap,
-                             ca_tail=_tail_fwd(Bl, H, W, d["R"], d["caw1c"], d["cb1"], d["caw2c"], d["cb2"], mm, sv, hid, ca, g, dev))
-                elif heads:  # the gate is computed by the conv that consumes it (the next block's conv1, or the group's tail conv)
-                    conv_c64(t1, v, d["p2"], d["b2"], (1, 64), t2, v, Bl, H, W, 64, 64, gap=gap)
-                    hd = hip.CaTail()
+        pend = None  # (t2, g, gate head) of the block whose gated skip the next conv builds
+        for k in range(n):
+            d = blks[k]
+            if pend is None:
+                conv(x_in, d["p1"], d["b1"], d["t1"], 3, relu=True)
+            else:
+                conv(pend[0], d["p1"], d["b1"], d["t1"], 3, head=pend[2], relu=True, in_scale=pend[1],
+                     gate_add=blks[k - 1]["u"], gate_out=d["u"])
+            hd = None
+            if not has_ca:  # the gate is the meta-attention vector: nothing to pool, nothing to launch
+                conv(d["t1"], d["p2"], d["b2"], d["t2"], 3, alpha=alpha)
+            else:
+                conv(d["t1"], d["p2"], d["b2"], d["t2"], 3, gap=d["gap"])
+                if heads:  # the gate is computed by the conv that consumes it (the next block's conv1, or the group's tail conv)
+                    hd = hip.CaTail()  # copied into the launch's arguments: it need not outlive the call
                     hd.backward, hd.hidden, hd.inv_hw, hd.head, hd.head_parts = 0, d["R"], 1.0 / (H * W), 1, parts
                     hd.w1, hd.b1, hd.w2, hd.b2, hd.mul = (hip.ptr(d["caw1c"]), hip.ptr(d["cb1"]), hip.ptr(d["caw2c"]),
-                                                          hip.ptr(d["cb2"]), hip.ptr(mm))
-                    hd.s_out, hd.hid_out, hd.ca_out, hd.g_out = hip.ptr(sv), hip.ptr(hid), hip.ptr(ca), hip.ptr(g)
-                    hd.head_part = hip.ptr(gap)
-                    keep.append(hd)
+                                                          hip.ptr(d["cb2"]), hip.ptr(d["mm"]))
+                    hd.s_out, hd.hid_out, hd.ca_out, hd.g_out = hip.ptr(d["sv"]), hip.ptr(d["hid"]), hip.ptr(d["ca"]), hip.ptr(d["g"])
+                    hd.head_part = hip.ptr(d["gap"])
                 else:
-                    conv(t1, d["p2"], d["b2"], t2, Bl, 3, gap=gap)
-                    hip.check(L.sisr_ca_gate_fwd(hip.ptr(gap), parts, Bl, 1.0 / (H * W), hip.ptr(d["caw1c"]), hip.ptr(d["cb1"]),
-                                                 hip.ptr(d["caw2c"]), hip.ptr(d["cb2"]), 64, d["R"], hip.ptr(mm), hip.ptr(sv),
-                                                 hip.ptr(hid), hip.ptr(ca), hip.ptr(g), hip.stream()), "sisr_ca_gate_fwd")
-                pend = (t2, g, hd)
-                if interleave:
-                    yield
-            if st16:  # bf16 t2 and skips in, the group's output (+ its fp32 input as the residual) in fp32
-                conv(pend[0], pt, bt, out[sl], Bl, 1, in_scale=pend[1], gate_add=blks[n - 1]["u"][sl], gate_out=un[sl], res=x[sl])
-            else:
-                conv_c64(pend[0], v, pt, bt, (1, 64), out[sl], v, Bl, H, W, 64, 64, in_scale=pend[1],
-                         gate_add=blks[n - 1]["u"][sl], gate_out=un[sl], res=x[sl], ca_tail=pend[2])
-
-        lanes.fork()
-        if interleave:
-            lanes.run(chain)
-        else:
-            lanes.run(lambda b0, b1: [None for _ in chain(b0, b1)] and None)
-        lanes.join()
+                    hip.check(L.sisr_ca_gate_fwd(hip.ptr(d["gap"]), parts, B, 1.0 / (H * W), hip.ptr(d["caw1c"]), hip.ptr(d["cb1"]),
+                                                 hip.ptr(d["caw2c"]), hip.ptr(d["cb2"]), 64, d["R"], hip.ptr(d["mm"]),
+                                                 hip.ptr(d["sv"]), hip.ptr(d["hid"]), hip.ptr(d["ca"]), hip.ptr(d["g"]),
+                                                 hip.stream()), "sisr_ca_gate_fwd")
+            pend = (d["t2"], d["g"], hd)
+        # (st16: bf16 t2 and skips in, the group's output, with its fp32 input as the residual, in fp32)
+        conv(pend[0], pt, bt, out, 1, head=pend[2], in_scale=pend[1], gate_add=blks[n - 1]["u"], gate_out=un, res=x)
         ctx.save_for_backward(*tensors, un, wt)
         ctx.cfg = (n, (B, H, W), meta, parts)
         ctx.packs, ctx.pdt = packs, pdt
@@ -1432,8 +1265,8 @@ class _GatedGroup(Function):
                     fn()
 
             blocks, pos = [], 0
-            for cnt, has_m, s1, s2 in meta:
-                blocks.append((sv_all[pos:pos + cnt], has_m, s1, s2))
+            for cnt, has_m in meta:
+                blocks.append((sv_all[pos:pos + cnt], has_m))
                 pos += cnt
             # st16: the saved activations (un, every block's input, t1, t2) are bf16 maps; g16: so are the gradient maps the
             # launches of this pass hand to each other (the group's own input / output gradients stay fp32)
@@ -1442,24 +1275,21 @@ class _GatedGroup(Function):
             wst = 1 if st16 else 0
             grad_map = _empty_cl16 if g16 else _empty_cl
 
-            def conv(xx, pk, yy, Bl, **kw):
-                """a backward conv of the group under st16: bf16 mask / dot operands; storage bits from the maps' own dtypes"""
+            def conv(xx, pk, yy, head=None, **kw):
+                """a backward conv of the group; under st16 bf16 mask / dot operands and storage bits from the maps' own dtypes"""
                 st = ((1 if xx.dtype == torch.bfloat16 else 0) | (2 if yy.dtype == torch.bfloat16 else 0) |
                       (4 if (kw.get("mask") is not None or kw.get("dot") is not None) else 0) |
-                      (8 if (kw.get("res") is not None and kw["res"].dtype == torch.bfloat16) else 0))
-                if st:
-                    conv_c64s(xx, pk, None, yy, Bl, H, W, st, **kw)
+                      (8 if (kw.get("res") is not None and kw["res"].dtype == torch.bfloat16) else 0)) if st16 else 0
+                if st:  # (no gate heads there)
+                    conv_c64s(xx, pk, None, yy, B, H, W, st, **kw)
                 else:
-                    conv_c64(xx, v, pk, None, (1, 64), yy, v, Bl, H, W, 64, 64, **kw)
+                    conv_c64(xx, v, pk, None, (1, 64), yy, v, B, H, W, 64, 64, ca_head=head, **kw)
 
             side = _side_ok(wt, *(t for blk in blocks for t in blk[0][1:3]))
             # small launches: the group's 2n + 1 weight gradients go out eight to a launch (WgradQueue) instead of one by one
             queue = WgradQueue(B, H, W, dev) if WgradQueue.wanted(B, H, W) else None
-            tails = has_ca and _use_ca_tail(B, H, W)
-            bheads = has_ca and not tails and queue is not None and GATE_HEADS and B * H * W <= GATE_HEADS_MAX_PIXELS
-            lanes = _Lanes(dev, _lane_cuts(B, H, W) if queue is not None else [(0, B)])
-            nl = len(lanes.cuts)
-            gate_jobs, keep = [], []
+            bheads = has_ca and queue is not None and GATE_HEADS and B * H * W <= GATE_HEADS_MAX_PIXELS
+            gate_jobs = []
             # tail conv: weight gradient from (u_n, dout); dU_n = convT(dout), with sum(dU_n * t2_n) on the side
             dwt, dbt = _grad_buf(wt), _grad_buf_or(ctx.bt, 64, dev)
             if queue is not None:
@@ -1468,8 +1298,8 @@ class _GatedGroup(Function):
                 run(lambda: wgrad_c64(un, v, dout, v, dwt, dbt, B, H, W, 64, 64, storage=wst), (un, dout, dwt, dbt))
 
             def gate_bwd_out(k):
-                """Outputs of block k's gate backward (allocated before the conv launch whose tail / head fills them)."""
-                tens, has_m, s_caw1, s_caw2 = blocks[k]
+                """Outputs of block k's gate backward (allocated before the conv launch whose head fills them)."""
+                has_m = blocks[k][1]
                 _, _, caw1, cab1, caw2, cab2 = ctx.small[k]
                 if not has_ca:  # the meta gate's gradient is the sum of the DOT partials; no pooling gradient, no CA parameters
                     return dict(shift=None, dmv=_vec(B, 64, dev), dcaw1=None, dcab1=None, dcaw2=None, dcab2=None, dzw=None,
@@ -1477,94 +1307,7 @@ class _GatedGroup(Function):
                 return dict(shift=_vec(B, 64, dev), dmv=_vec(B, 64, dev) if has_m else None,
                             dcaw1=_grad_buf(caw1), dcab1=_grad_buf(cab1), dcaw2=_grad_buf(caw2), dcab2=_grad_buf(cab2),
                             dgp=torch.empty((B, parts, 64), device=dev, dtype=torch.float32),
-                            dzw=torch.empty((B, 80), device=dev) if queue is not None and not tails else None)
-
-            def tail_for(k, o):
-                if not tails:
-                    return None
-                tens, has_m = blocks[k][0], blocks[k][1]
-                caw1c, caw2c, s, hid, ca = tens[5:10]
-                return _tail_bwd(B, H, W, caw1c.shape[0], caw1c, caw2c, s, hid, ca, tens[11] if has_m else None, o["shift"],
-                                 o["dmv"], o["dcaw1"], o["dcab1"], o["dcaw2"], o["dcab2"], dev)
-
-            def block_bufs(k):
-                """Maps block k's backward writes: dt1 (gradient at ReLU(conv1)) and dprev (gradient at the block's input), plus
-                the gate-backward outputs of block k - 1, which block k's last conv feeds."""
-                return dict(dt1=grad_map(B, 64, H, W, dev), dprev=(grad_map if k > 0 else _empty_cl)(B, 64, H, W, dev),
-                            go=gate_bwd_out(k - 1) if k > 0 else None)
-
-            def first_conv(b0, b1, dy, go):
-                """dU_n = convT_tail(dout), with the partial sums of sum(dU_n * t2_n) for block n - 1's gate backward."""
-                sl = slice(b0, b1)
-                if st16:
-                    conv(dout[sl], ctx.pdt, dy[sl], b1 - b0, gap=go["dgp"][sl], dot=blocks[-1][0][4][sl])
-                else:
-                    conv_c64(dout[sl], v, ctx.pdt, None, (1, 64), dy[sl], v, b1 - b0, H, W, 64, 64, gap=go["dgp"][sl],
-                             dot=blocks[-1][0][4][sl], ca_tail=tail_for(n - 1, go))
-
-            def block_chain(k, b0, b1, dy, go, bufs, mid1=None, mid2=None):
-                """Block k's part of the input-gradient chain on samples [b0, b1): gate backward (as a launch, a head of the next
-                conv, or the previous conv's tail), dgrad through conv2 (ReLU mask, gated gradient rebuilt while staging), dgrad
-                through conv1 (+ the skip's gradient; partial sums for block k - 1's gate backward).  mid1 / mid2: called after
-                the gate backward / after the first conv (where a single chain issues the block's weight gradients)."""
-                sl, Bl = slice(b0, b1), b1 - b0
-                tens, has_m, s_caw1, s_caw2 = blocks[k]
-                pd1, pd2 = ctx.packs[k]
-                bhead = None
-                if not has_ca:
-                    xk, w1, w2, t1, t2, g, gs = tens
-                    hip.check(L.sisr_sum_partials(hip.ptr(go["dgp"][sl]), parts, Bl, 64, 1.0, hip.ptr(go["dmv"][sl]), hip.stream()),
-                              "sisr_sum_partials")
-                    g, shift = gs, None  # dt2 = dU * (alpha * m)
-                else:
-                    xk, w1, w2, t1, t2, caw1c, caw2c, s, hid, ca, g = tens[:11]
-                    mm = tens[11][sl] if has_m else None
-                    R = caw1c.shape[0]
-                    shift, dmv = go["shift"][sl], go["dmv"][sl] if has_m else None
-                if not has_ca:
-                    pass
-                elif bheads:  # the per-sample part of the gate backward is computed by the conv that consumes `shift` (gate head)
-                    bhead = hip.CaTail()
-                    bhead.backward, bhead.hidden, bhead.inv_hw, bhead.head, bhead.head_parts = 1, R, 1.0 / hw, 1, parts
-                    bhead.w1, bhead.w2, bhead.hid, bhead.ca, bhead.mul = (hip.ptr(caw1c), hip.ptr(caw2c), hip.ptr(hid[sl]),
-                                                                          hip.ptr(ca[sl]), hip.ptr(mm))
-                    bhead.shift, bhead.dmul, bhead.workspace, bhead.head_part = (hip.ptr(shift), hip.ptr(dmv), hip.ptr(go["dzw"][sl]),
-                                                                                  hip.ptr(go["dgp"][sl]))
-                    keep.append(bhead)
-                elif not tails and queue is not None:
-                    # small launches: the chain kernel only produces what the next conv waits for; the gates' parameter
-                    # gradients of the whole group are one launch at the end (their dz2 / dz1 wait in per-gate workspaces)
-                    hip.check(L.sisr_ca_gate_bwd(hip.ptr(go["dgp"][sl]), parts, Bl, 1.0 / hw, hip.ptr(caw1c), hip.ptr(caw2c), 64, R,
-                                                 hip.ptr(s[sl]), hip.ptr(hid[sl]), hip.ptr(ca[sl]), hip.ptr(mm), hip.ptr(shift),
-                                                 hip.ptr(dmv), None, None, None, None, hip.ptr(go["dzw"][sl]), None, hip.stream()),
-                              "sisr_ca_gate_bwd")
-                elif not tails:  # (one chain over the whole batch: queue is None implies a single lane)
-                    hip.check(L.sisr_ca_gate_bwd(hip.ptr(go["dgp"]), parts, B, 1.0 / hw, hip.ptr(caw1c), hip.ptr(caw2c), 64, R,
-                                                 hip.ptr(s), hip.ptr(hid), hip.ptr(ca), hip.ptr(mm), hip.ptr(shift),
-                                                 hip.ptr(dmv), hip.ptr(go["dcaw1"]), hip.ptr(go["dcab1"]), hip.ptr(go["dcaw2"]),
-                                                 hip.ptr(go["dcab2"]), hip.ptr(_gate_ws(B, dev)), hip.gate_counter(dev), hip.stream()),
-                              "sisr_ca_gate_bwd")
-                if mid1 is not None:
-                    mid1()
-                dt1, dprev = bufs["dt1"], bufs["dprev"]
-                if st16:
-                    conv(dy[sl], pd2, dt1[sl], Bl, mask=t1[sl], in_scale=g[sl], in_shift=shift)
-                else:
-                    conv_c64(dy[sl], v, pd2, None, (1, 64), dt1[sl], v, Bl, H, W, 64, 64, mask=t1[sl], in_scale=g[sl],
-                             in_shift=shift, ca_tail=bhead)
-                if mid2 is not None:
-                    mid2()
-                if k > 0 and st16:
-                    gn = bufs["go"]
-                    conv(dt1[sl], pd1, dprev[sl], Bl, res=dy[sl], gap=gn["dgp"][sl], dot=blocks[k - 1][0][4][sl])
-                elif k > 0:
-                    gn = bufs["go"]
-                    conv_c64(dt1[sl], v, pd1, None, (1, 64), dprev[sl], v, Bl, H, W, 64, 64, res=dy[sl], gap=gn["dgp"][sl],
-                             dot=blocks[k - 1][0][4][sl], ca_tail=tail_for(k - 1, gn))
-                elif g16:
-                    conv(dt1[sl], pd1, dprev[sl], Bl, res=dy[sl])  # block 0: bf16 in, bf16 residual, the group's fp32 dX out
-                else:
-                    conv_c64(dt1[sl], v, pd1, None, (1, 64), dprev[sl], v, Bl, H, W, 64, 64, res=dy[sl])
+                            dzw=torch.empty((B, 80), device=dev) if queue is not None else None)
 
             grads = [None] * (n * _GatedGroup.PER)
 
@@ -1581,15 +1324,14 @@ class _GatedGroup(Function):
                                           storage=3 if g16 else wst), (t1, dy, g, shift, dw2, db2))
                 grads[k * _GatedGroup.PER + 2:k * _GatedGroup.PER + 4] = [dw2, db2]
 
-            def wgrad1(k, go, bufs):
+            def wgrad1(k, go, dt1):
                 """Weight gradient of block k's first conv, from (the block's input, dt1); the block's small gradients."""
-                tens, has_m = blocks[k][0], blocks[k][1]
+                tens, has_m = blocks[k]
                 xk, w1 = tens[0], tens[1]
                 caw1c, s, hid = (tens[5], tens[7], tens[8]) if has_ca else (None, None, None)
                 dw1, db1 = _grad_buf(w1), _grad_buf_or(ctx.small[k][0], 64, dev)
-                dt1 = bufs["dt1"]
                 if queue is not None:
-                    if not tails and has_ca:
+                    if has_ca:
                         gate_jobs.append((go["dzw"], hid, s, go["dcaw1"], go["dcab1"], go["dcaw2"], go["dcab2"], caw1c.shape[0]))
                     queue.add(xk, dt1, dw1, db1)
                 else:
@@ -1599,54 +1341,61 @@ class _GatedGroup(Function):
                 grads[k * P:k * P + 2] = [dw1, db1]
                 grads[k * P + 4:k * P + 9] = [go["dcaw1"], go["dcab1"], go["dcaw2"], go["dcab2"], go["dmv"] if has_m else None]
 
+            # dU_n = convT_tail(dout), with the partial sums of sum(dU_n * t2_n) for block n - 1's gate backward
             dy = grad_map(B, 64, H, W, dev)
             go = gate_bwd_out(n - 1)
-            if nl == 1:
-                # one chain on the calling stream: buffers come and go block by block, weight gradients follow their operands
-                first_conv(0, B, dy, go)
-                for k in range(n - 1, -1, -1):
-                    bufs = block_bufs(k)
-                    if queue is None:  # side stream: wgrad2 beside the conv2 input gradient, wgrad1 beside conv1's
-                        block_chain(k, 0, B, dy, go, bufs, mid1=lambda: wgrad2(k, dy, go), mid2=lambda: wgrad1(k, go, bufs))
-                    else:  # queued: after the first conv (with a gate head it is that launch which fills `shift`)
-                        block_chain(k, 0, B, dy, go, bufs, mid2=lambda: (wgrad2(k, dy, go), wgrad1(k, go, bufs)))
-                    dy, go = bufs["dprev"], bufs["go"]
-            else:
-                # sample lanes: the chains of a SEGMENT of blocks run side by side; then the lanes meet, the segment's weight
-                # gradients (whole-batch launches, eight to a launch) run, and the lanes part again for the next segment
-                seg = max(1, int(os.environ.get("SISR_LANES_SEGMENT", 4)))
-                state = {"dy": dy, "go": go}
-                k_hi = n - 1
-                first = True
-                while k_hi >= 0:
-                    ks = list(range(k_hi, max(-1, k_hi - seg), -1))
-                    allb = {k: block_bufs(k) for k in ks}  # before the fork, on the calling stream
-
-                    def segment(b0, b1, first=first, ks=ks, allb=allb, dy0=state["dy"], go0=state["go"]):
-                        dyl, gol = dy0, go0
-                        if first:
-                            first_conv(b0, b1, dyl, gol)
-                        for k in ks:
-                            block_chain(k, b0, b1, dyl, gol, allb[k])
-                            dyl, gol = allb[k]["dprev"], allb[k]["go"]
-                            if LANES_INTERLEAVE:
-                                yield
-
-                    lanes.fork()
-                    if LANES_INTERLEAVE:
-                        lanes.run(segment)
+            conv(dout, ctx.pdt, dy, gap=go["dgp"], dot=blocks[-1][0][4])
+            for k in range(n - 1, -1, -1):
+                # block k: gate backward (a launch, or a head of the next conv), dgrad through conv2 (ReLU mask, gated gradient
+                # rebuilt while staging), dgrad through conv1 (+ the skip's gradient; partial sums for block k - 1's gate
+                # backward).  Its maps come and go block by block; its weight gradients follow their operands
+                tens, has_m = blocks[k]
+                pd1, pd2 = ctx.packs[k]
+                dt1 = grad_map(B, 64, H, W, dev)  # gradient at ReLU(conv1)
+                dprev = (grad_map if k > 0 else _empty_cl)(B, 64, H, W, dev)  # gradient at the block's input
+                gn = gate_bwd_out(k - 1) if k > 0 else None  # block k - 1's gate backward, which block k's last conv feeds
+                t1 = tens[3]
+                bhead = None
+                if not has_ca:
+                    hip.check(L.sisr_sum_partials(hip.ptr(go["dgp"]), parts, B, 64, 1.0, hip.ptr(go["dmv"]), hip.stream()),
+                              "sisr_sum_partials")
+                    g, shift = tens[6], None  # dt2 = dU * (alpha * m)
+                else:
+                    caw1c, caw2c, s, hid, ca, g = tens[5:11]
+                    mm = tens[11] if has_m else None
+                    R = caw1c.shape[0]
+                    shift, dmv = go["shift"], go["dmv"]
+                    if bheads:  # the per-sample part of the gate backward is computed by the conv that consumes `shift`
+                        bhead = hip.CaTail()
+                        bhead.backward, bhead.hidden, bhead.inv_hw, bhead.head, bhead.head_parts = 1, R, 1.0 / hw, 1, parts
+                        bhead.w1, bhead.w2, bhead.hid, bhead.ca, bhead.mul = (hip.ptr(caw1c), hip.ptr(caw2c), hip.ptr(hid),
+                                                                              hip.ptr(ca), hip.ptr(mm))
+                        bhead.shift, bhead.dmul, bhead.workspace, bhead.head_part = (hip.ptr(shift), hip.ptr(dmv),
+                                                                                      hip.ptr(go["dzw"]), hip.ptr(go["dgp"]))
+                    elif queue is not None:
+                        # small launches: the chain kernel only produces what the next conv waits for; the gates' parameter
+                        # gradients of the whole group are one launch at the end (their dz2 / dz1 wait in per-gate workspaces)
+                        hip.check(L.sisr_ca_gate_bwd(hip.ptr(go["dgp"]), parts, B, 1.0 / hw, hip.ptr(caw1c), hip.ptr(caw2c), 64,
+                                                     R, hip.ptr(s), hip.ptr(hid), hip.ptr(ca), hip.ptr(mm), hip.ptr(shift),
+                                                     hip.ptr(dmv), None, None, None, None, hip.ptr(go["dzw"]), None,
+                                                     hip.stream()), "sisr_ca_gate_bwd")
                     else:
-                        lanes.run(lambda b0, b1: [None for _ in segment(b0, b1)] and None)
-                    lanes.join()
-                    dyl, gol = state["dy"], state["go"]
-                    for k in ks:
-                        wgrad2(k, dyl, gol)
-                        wgrad1(k, gol, allb[k])
-                        dyl, gol = allb[k]["dprev"], allb[k]["go"]
-                    state["dy"], state["go"] = dyl, gol
-                    first = False
-                    k_hi -= seg
-                dy = state["dy"]
+                        hip.check(L.sisr_ca_gate_bwd(hip.ptr(go["dgp"]), parts, B, 1.0 / hw, hip.ptr(caw1c), hip.ptr(caw2c), 64,
+                                                     R, hip.ptr(s), hip.ptr(hid), hip.ptr(ca), hip.ptr(mm), hip.ptr(shift),
+                                                     hip.ptr(dmv), hip.ptr(go["dcaw1"]), hip.ptr(go["dcab1"]),
+                                                     hip.ptr(go["dcaw2"]), hip.ptr(go["dcab2"]), hip.ptr(_gate_ws(B, dev)),
+                                                     hip.gate_counter(dev), hip.stream()), "sisr_ca_gate_bwd")
+                if queue is None:  # side stream: wgrad2 beside conv2's input gradient, wgrad1 beside conv1's
+                    wgrad2(k, dy, go)
+                conv(dy, pd2, dt1, head=bhead, mask=t1, in_scale=g, in_shift=shift)
+                if queue is not None:  # queued: after the block's first conv (with a gate head it is that launch which fills `shift`)
+                    wgrad2(k, dy, go)
+                wgrad1(k, go, dt1)
+                if k > 0:
+                    conv(dt1, pd1, dprev, res=dy, gap=gn["dgp"], dot=blocks[k - 1][0][4])
+                else:  # (g16: bf16 in, bf16 residual, the group's fp32 dX out)
+                    conv(dt1, pd1, dprev, res=dy)
+                dy, go = dprev, gn
             dx = _affine(dy, None, None, dout, B, H, W, 64) if ctx.needs_input_grad[0] else None
             if queue is not None:
                 queue.flush()  # before the gradients leave the node (reducer hooks may read them right after)
@@ -1952,10 +1701,6 @@ def _padded_packs(weight, cop, cip, need_dgrad):
 # conv -> gather composition of round 3, kept for the stride-2 convs and as the A/B reference; results are bit-identical)
 REFL_GEO = os.environ.get("SISR_REFL_GEO", "1") != "0"
 REFL_BATCH = os.environ.get("SISR_REFL_BATCH", "1") != "0"  # their small weight gradients eight per launch (WgradGeoQueue)
-# ... or on the side stream (captured: a parallel branch).  Measured slower on MI355X, per launch (459 vs 500 images/s) and
-# forked sixteen at a time (467): off
-REFL_SIDE = os.environ.get("SISR_REFL_SIDE", "0") != "0"
-REFL_SIDE_GROUP = int(os.environ.get("SISR_REFL_SIDE_GROUP", 16))  # ... forked this many at a time
 
 
 class _ReflConv(Function):
@@ -2079,20 +1824,10 @@ class _ReflConv(Function):
                         q.add(x, dy, dw, db, (B, Hv, Wv, Cp, cop, wup, co, ci), units, tiles)
                         return dx, dw, db, None, None
                 nbytes = L.sisr_wgrad3x3_c64_workspace_bytes(B, Hv, Wv, Cp, cop)
-
-                def wgrad():  # (the workspace is per stream: taken where the launch is issued)
-                    ws = hip.workspace(dev, nbytes)
-                    hip.check(L.sisr_wgrad3x3_c64_geo(hip.ptr(x), hip.view_plain(H, W, Cp), hip.ptr(dy), hip.view_plain(Hd, Wd, cop),
-                                                      hip.ptr(dw), co, ci, hip.ptr(db), hip.ptr(ws), nbytes, B, Hv, Wv, Cp, cop,
-                                                      wup, units, hip.stream()), "sisr_wgrad3x3_c64_geo")
-
-                # The maps of this network are far smaller than the chip (most launches: 16 - 80 workgroups on 256 CUs): the
-                # weight gradients, which nothing on the input-gradient chain waits for, fill the idle CUs from a second stream
-                # (a parallel branch of the captured step), joined once at the end of the backward pass.
-                if REFL_SIDE and _side_ok(*((weight, ctx.bias) if has_b else (weight,)), fork=True):
-                    _on_side_grouped(dev, wgrad, (x, dy, dw, db), REFL_SIDE_GROUP)
-                else:
-                    wgrad()
+                ws = hip.workspace(dev, nbytes)
+                hip.check(L.sisr_wgrad3x3_c64_geo(hip.ptr(x), hip.view_plain(H, W, Cp), hip.ptr(dy), hip.view_plain(Hd, Wd, cop),
+                                                  hip.ptr(dw), co, ci, hip.ptr(db), hip.ptr(ws), nbytes, B, Hv, Wv, Cp, cop,
+                                                  wup, units, hip.stream()), "sisr_wgrad3x3_c64_geo")
             return dx, dw, db, None, None
         dyf = _empty_cl(B, cop, Hp, Wp, dev)
         hip.check(L.sisr_crop_stride(hip.ptr(dy), hip.ptr(dyf), B, Hp, Wp, cop, stride, 1, hip.stream()), "sisr_crop_stride(embed)")

@@ -191,10 +191,7 @@ class GradReducer:
         mode = self.graph_overlap_mode()
         if mode == "auto":
             mode = "0"
-        from . import ops
-        # SISR_GRAPH_FORK=1 captures the weight gradients as parallel branches: a signal node on the capture stream would not
-        # be ordered behind them, so that combination joins all buckets after the replay
-        return self.flags is not None and self.overlap and mode != "0" and not ops.GRAPH_FORK
+        return self.flags is not None and self.overlap and mode != "0"
 
     def begin_capture(self):
         """Call on the capturing stream, right before the backward pass that is being captured."""

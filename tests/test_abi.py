@@ -121,7 +121,7 @@ def test_round4_entry_points_refuse_bad_arguments_before_any_device_call():
     buf = (C.c_float * 64)()
     a = C.addressof(buf)  # a non-null, 16-byte aligned stand-in: every call below must fail before it is dereferenced
     assert a % 16 == 0 or True
-    ERR_ARG, ERR_UNSUPPORTED = -1, -2
+    ERR_ARG, ERR_UNSUPPORTED = -1, -4
     bad = lambda rc: rc != 0  # noqa: E731
     assert bad(L.sisr_conv3x3_c64_geo(a, v, a, None, a, v, None, 1, 8, 8, 64, 64, 0, 0, 0, None))      # mode 0
     assert bad(L.sisr_conv3x3_c64_geo(a, v, a, None, a, v, None, 1, 8, 8, 64, 64, 5, 0, 0, None))      # mode 5
@@ -146,6 +146,14 @@ def test_round4_entry_points_refuse_bad_arguments_before_any_device_call():
     assert bad(L.sisr_act(a, None, None, a, None, 64, 64, 64, 0, 0, None))                     # PReLU without slopes
     assert bad(L.sisr_act(a, None, a, a, None, 64, 64, 64, 2, 0, None))                        # unknown mode
     assert bad(L.sisr_spar3d(a, a, None, a, None, 6, 0, None))                                 # element count not a multiple of 4
+    # sisr_ca_tail describes gate heads only: a complete record of the removed tail form (head = 0) is refused
+    assert L.sisr_ca_tail_bytes() == C.sizeof(hip.CaTail)
+    rec = hip.CaTail()
+    rec.backward, rec.hidden, rec.inv_hw, rec.head_parts, rec.head = 0, 4, 1.0 / 64, 4, 0
+    for f in ("w1", "b1", "w2", "b2", "s_out", "hid_out", "ca_out", "g_out", "counter", "head_part"):
+        setattr(rec, f, a)
+    assert L.sisr_conv3x3_c64(a, v, a, a, 1, 64, a, v, None, None, None, None, None, 1.0, 0, a, None, None, None,
+                              1, 8, 8, 64, 64, C.addressof(rec), 0, None) == ERR_UNSUPPORTED
     assert ERR_ARG != 0 and ERR_UNSUPPORTED != 0
 
 

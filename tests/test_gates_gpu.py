@@ -165,7 +165,7 @@ def params_batch(jobs_list, B, R):
     return lib().sisr_ca_gate_bwd_params_batch(ctypes.addressof(jobs), len(jobs_list), B, R, S())
 
 
-# (parts, R, B, mul).  block_sum_parts_t: thread group k = 0..15 takes its 16-load unrolled round while k + 240 < parts,
+# (parts, R, B, mul).  block_sum_parts: thread group k = 0..15 takes its 16-load unrolled round while k + 240 < parts,
 # then single rows: parts 1 / 15 / 16 / 17 (groups idle or one row), 240 | 241 (group 0's first unrolled round), 256 | 257
 # (every group's round / one row past), 497 (group 0: a second round, 256 + 240 < 497), 4096 (16 rounds).
 # R <= 4 takes the register ("pre") path, R > 4 the loop path; R <= 16 accepted (17 refused: test below).

@@ -174,39 +174,6 @@ def test_fused_group_node_matches_per_block_nodes(meta):
 
 
 @pytest.mark.parametrize("meta", [False, True])
-def test_channel_attention_tails_are_bit_identical_to_the_gate_launches(meta):
-    """The gate (and its backward) computed by the last-arriving workgroup of the conv launch that writes its partial sums
-    (ops.CA_TAIL) against the stand-alone gate launches: same code path (ca_gate.h), same summation order -> every output
-    and every gradient equal to the bit, on a batch whose samples finish in any order (B = 3, odd sizes)."""
-    torch.manual_seed(8)
-    if meta:
-        net = A.QRCAN(n_resblocks=3, n_resgroups=2, n_feats=64, scale=2, style="standard", num_metadata=10,
-                      include_q_layer=True).to(DEV)
-    else:
-        net = A.RCAN(n_resblocks=3, n_resgroups=2, n_feats=64, scale=2).to(DEV)
-    x = rnd(3, 3, 37, 70, seed=80, scale=0.5).to(DEV)
-    md = rnd(3, 10, 1, 1, seed=81, scale=0.3).to(DEV)
-    cot, res, prev = None, {}, ops.CA_TAIL
-    try:
-        for mode in ("1", "0", "1"):  # twice with tails: the counters must come back to zero
-            ops.CA_TAIL = mode
-            net.zero_grad(set_to_none=True)
-            out = net(x, md) if meta else net(x)
-            if cot is None:
-                cot = rnd(*out.shape, seed=82).to(DEV)
-            out.backward(cot)
-            cur = (out.detach().clone(), {k: p.grad.detach().clone() for k, p in net.named_parameters()})
-            if mode in res:
-                assert torch.equal(res[mode][0], cur[0]) and all(torch.equal(res[mode][1][k], cur[1][k]) for k in cur[1])
-            res[mode] = cur
-    finally:
-        ops.CA_TAIL = prev
-    assert torch.equal(res["1"][0], res["0"][0])
-    for k in res["1"][1]:
-        assert torch.equal(res["1"][1][k], res["0"][1][k]), k
-
-
-@pytest.mark.parametrize("meta", [False, True])
 @pytest.mark.parametrize("shape", [(3, 37, 70), (2, 128, 128)])  # both within ops.GATE_HEADS_MAX_PIXELS
 def test_gate_heads_are_bit_identical_to_the_gate_launches(meta, shape):
     """Small launches: the channel-attention gate and its backward are computed by the conv that CONSUMES them (gate heads,
@@ -238,46 +205,6 @@ def test_gate_heads_are_bit_identical_to_the_gate_launches(meta, shape):
     assert torch.equal(res[True][0], res[False][0])
     for k in res[True][1]:
         assert torch.equal(res[True][1][k], res[False][1][k]), k
-
-
-@pytest.mark.parametrize("meta", [False, True])
-@pytest.mark.parametrize("shape,lanes,heads", [((4, 37, 70), 2, True), ((4, 128, 128), 2, True), ((4, 40, 48), 4, True),
-                                               ((6, 32, 40), 2, False), ((6, 32, 40), 3, True)])
-def test_sample_lanes_are_bit_identical_to_one_chain(meta, shape, lanes, heads):
-    """Small launches of a residual group run as LANES chains of B / LANES samples on parallel streams (ops._lane_cuts; inside
-    a hipGraph capture by default, forced here in eager mode): every launch of a lane is the same kernel on a contiguous
-    slice of the batch and the weight gradients stay whole-batch launches, so outputs and every gradient equal the single
-    chain's to the bit -- with gate heads and with stand-alone gate launches, five blocks (two weight-gradient segments)."""
-    torch.manual_seed(8)
-    if meta:
-        net = A.QRCAN(n_resblocks=5, n_resgroups=2, n_feats=64, scale=2, style="standard", num_metadata=10,
-                      include_q_layer=True).to(DEV)
-    else:
-        net = A.RCAN(n_resblocks=5, n_resgroups=2, n_feats=64, scale=2).to(DEV)
-    B, H, W = shape
-    x = rnd(B, 3, H, W, seed=83, scale=0.5).to(DEV)
-    md = rnd(B, 10, 1, 1, seed=84, scale=0.3).to(DEV)
-    cot, res = None, {}
-    prev = (ops.LANES, ops.LANES_EAGER, ops.GATE_HEADS)
-    if ops.PRECISION != "fp32":
-        pytest.skip("sample lanes are an fp32-path feature")
-    try:
-        ops.GATE_HEADS = heads
-        for mode in (lanes, 1):
-            ops.LANES, ops.LANES_EAGER = mode, True
-            assert len(ops._lane_cuts(B, H, W)) == mode
-            net.zero_grad(set_to_none=True)
-            out = net(x, md) if meta else net(x)
-            if cot is None:
-                cot = rnd(*out.shape, seed=85).to(DEV)
-            out.backward(cot)
-            torch.cuda.synchronize()
-            res[mode] = (out.detach().clone(), {k: p.grad.detach().clone() for k, p in net.named_parameters()})
-    finally:
-        ops.LANES, ops.LANES_EAGER, ops.GATE_HEADS = prev
-    assert torch.equal(res[lanes][0], res[1][0])
-    for k in res[lanes][1]:
-        assert torch.equal(res[lanes][1][k], res[1][1][k]), k
 
 
 def test_conv_residual_alpha_and_multichunk():

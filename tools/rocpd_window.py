@@ -2,7 +2,7 @@
 """A window of consecutive dispatches of the last full step of a rocpd database: start offset, duration, queue, name.
 
     python tools/rocpd_window.py x_results.db [first=300] [count=60] [marker]
-Shows how parallel branches of a replayed hipGraph (the sample lanes) are interleaved on the hardware queues.
+Shows how the dispatches of a replayed hipGraph are interleaved on the hardware queues.
 """
 import sqlite3
 import sys
