@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: LR-patches/s (128x128x3 -> x4) for one training step on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: bench.py starts its N ranks itself,
+    python bench.py --gpus N --steps K --warmup W [--full]  (N > 1 without a launcher: bench.py starts its N ranks itself,
                                                             as a child `python -m torch.distributed.run ...`, and relays the line)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -11,15 +11,20 @@ A step is BaseModel.train_step on the full-depth network: forward + L1 + backwar
 synthetic inputs already resident in HBM.  value = all patches of all ranks / max-over-ranks wall
 time of exactly K steps.
 
+A plain run measures the headline alone: it sets up, runs W warm-up and K timed steps, writes --dump-outputs if asked and
+prints the line (with the roofline derived from the headline value).  --full adds everything below that takes a run of its
+own: the per-family kernel timing step, the side measurements and the CPU baseline (--no-kernel-timing, --no-secondary and
+--no-cpu-baseline leave single parts of it out).
+
 Default workloads (BASELINE.json configs):
-  N = 1   configs[1]: RCAN x4, 32 tiles on the GPU.  The line also carries "meta_rcan": the same measurement for
-          RCAN + meta-attention (QRCAN, north_star's target family), taken right after the timed region.
+  N = 1   configs[1]: RCAN x4, 32 tiles on the GPU.  With --full the line also carries "meta_rcan": the same measurement
+          for RCAN + meta-attention (QRCAN, north_star's target family), taken right after the timed region.
   N > 1   configs[3]: Meta-RCAN (QRCAN) data-parallel, GLOBAL batch 32 -> 32/N tiles per GPU, gradients all-reduced
-          over RCCL ("scaling": "strong"); per-GPU batches <= 8 replay forward+backward from a hipGraph.  The line also
-          carries "weak_scaling": QRCAN at 32 tiles PER GPU (global batch 32 N), measured after the timed region.
+          over RCCL ("scaling": "strong"); per-GPU batches <= 8 replay forward+backward from a hipGraph.  With --full the
+          line also carries "weak_scaling": QRCAN at 32 tiles PER GPU (global batch 32 N), measured after the timed region.
   --batch B (tiles per GPU, weak scaling) or --global-batch G (strong scaling) override either default.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (the "families" of roofline and everything from cpu_baseline on: --full only):
   roofline      bound "mfma" (fp32 path; SURVEY.md 8d: the step is bound by the fp32 matrix rate, not HBM).  Primary
                 achieved / frac = the WHOLE STEP's algorithmic TFLOP/s per GPU against the 157.3 TFLOP/s fp32 MFMA peak.
                 "families": each 64->64 conv kernel family of the step (forward plain, forward GATE, dgrad with ReLU mask,
@@ -379,9 +384,13 @@ def main():
     ap.add_argument("--global-batch", type=int, default=None,
                     help="LR patches per step over ALL GPUs (strong scaling); default 32 when N > 1 (BASELINE config 4)")
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS), help="default: rcan at N = 1, qrcan at N > 1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the meta_rcan / weak_scaling side measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure everything else: per-family kernel timing, the CPU baseline and the "
+                         "side measurements (meta_rcan / weak_scaling, config4_point, han_bf16, ...); without it a run sets up, "
+                         "warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the per-family kernel timing step")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the side measurements")
     ap.add_argument("--graph", nargs="?", const="on", default="auto", choices=["auto", "on", "off"],
                     help=f"replay forward+backward as a hipGraph (auto: per-GPU batch <= {GRAPH_MAX_BATCH})")
     ap.add_argument("--force-dp", action="store_true",
@@ -400,6 +409,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run measures the headline alone: every other measurement is --full's
+        args.no_cpu_baseline = args.no_kernel_timing = args.no_secondary = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started bare (`python bench.py --gpus N`, the way the reference turns multi-GPU on with a flag and no launcher,

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_line_has_the_contract_fields():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                          "--batch", "4", "--workload", "edsr"], capture_output=True, text=True, timeout=900)
+                          "--batch", "4", "--workload", "edsr", "--full"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -33,6 +33,25 @@ def test_bench_line_has_the_contract_fields():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in c, k
     assert c["kind"] in ("port", "reference") and c["value"] > 0 and c["cores"] >= 1
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_alone():
+    """Without --full the default run times its steps and prints the line: the contract's fields and the roofline derived from
+    the headline, no kernel-timing step, no side measurement, no CPU baseline."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0"],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"] == "LR-patches/sec (128x128x3, x4) fwd+bwd" and d["unit"] == "patches/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == 1 and d["warmup"] == 0 and d["config"]["per_gpu_batch"] == 32
+    assert d["value"] > 0 and abs(d["value"] - 32 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    r = d["roofline"]
+    assert r["bound"] == "mfma" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9 and r["families"] == [] and r["kernel"] is None
+    for k in ("cpu_baseline", "meta_rcan", "config4_point", "han_bf16", "meta_edsr", "b1_point", "sparnet", "inference", "bf16x3"):
+        assert k not in d, k
 
 
 @pytest.mark.gpu
@@ -76,11 +95,11 @@ def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher and no WORLD_SIZE: bench.py spawns its two ranks as a child
     torch.distributed.run (never exec) and relays rank 0's single JSON line.  Rehearsed on the one GPU of this box: both ranks
     on cuda:0, gloo transport; the default N > 1 workload = BASELINE config 4 (QRCAN, global batch 32, strong scaling,
-    hipGraph replay), with the weak-scaling object and the watchdogged overlapped-exchange object beside it."""
+    hipGraph replay), with --full's weak-scaling object and watchdogged overlapped-exchange object beside it."""
     env = dict(os.environ, SISR_BENCH_SHARE_GPU="1", SISR_DIST_BACKEND="gloo")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=1500, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
