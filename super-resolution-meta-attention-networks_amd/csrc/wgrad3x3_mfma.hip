@@ -478,6 +478,294 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_full_kernel(WgradParams p
 __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_full_batch_kernel(WgradBatch bt) { wgrad3x3_c64_full_body(bt.job[blockIdx.z]); }
 __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_full_geo_kernel(WgradParams p) { wgrad3x3_c64_full_body<true>(p); }
 
+// ------------------------------------------------------------------ Winograd F(2x2,3x3) form of the dense kernel
+// The forward (conv3x3_c64_w4_kernel) computes each 2 x 2 output block as Y = A^T [(G g G^T) . (B^T d B)] A; its weight
+// gradient is
+//   dg = G^T [ sum_blocks (A dY' A^T) . (B^T d B) ] G
+// i.e. 16 GEMMs, one per transform point xi = (xr, xc): dU[xi][ci][co] = sum_blocks V[xi][block][ci] M[xi][block][co] with
+// V = B^T d B (4 x 4 input patch at stride 2, zero-padded) and M = A dY' A^T (from the 2 x 2 dY' block; dY' outside the map
+// is zero, so ragged and odd sizes need nothing else).  16 x 64 x 64 MACs per block against 36 x 64 x 64 for the direct
+// form; the multiplies stay exact fp32 MFMA products, the transforms add a few fp32 roundings (coefficients 0, +-1, 1/2).
+// M is taken with its last row / column NEGATED (A's row 3 read as (0, +1)), which saves the negation per element; the
+// fold below carries the sign instead.
+//   tile: 4 x 32 output pixels = 2 x 16 blocks (K = 32 per tile and transform point); staged like the dense kernel
+//         (issue the next tile's loads before this tile's K loops, commit them to LDS once the raw image is free):
+//         x halo 6 x 34 x 64 (52.2 KB) and dY' 4 x 32 x 64 (32.8 KB), fp32, [row][col][64 ch]
+//   chunks: per xr, the workgroup transforms the raw image ONCE into V[xc 4][block 32][64 ci] and M[xc 4][block 32][64 co]
+//         (32.8 KB each; 150.5 KB of LDS in all): thread (block tid >> 3, 16-B pieces q, q + 8) builds four xc of both
+//   wave w = (ci half w >> 1, co half w & 1): 16 persistent 32 x 32 accumulators (256 registers, one per xi), K index
+//         (lane >> 5) = block parity, v_mfma_f32_32x32x2_f32 fed by two ds_read_b32 (the dense kernel's K loop: MFMA and
+//         ds_read only; operands requested four steps ahead, one wave per SIMD)
+//   budget per tile and SIMD: 4 x 64 MFMAs = 16.4 K cycles (direct form on the same pixels: 36.9 K); per xr two barriers
+//         around the chunk build (24 ds_read_b128, 16 ds_write_b128, ~110 VALU per thread), not overlapped with MFMAs
+//   epilogue: per lane the 16 dU registers of an element are folded to the nine taps (dg = G^T dU G, coefficients
+//         +-1 and 1/2) and stored as the dense kernel's quadrant slab; bias slabs and the second stage are unchanged.
+#define W4_TH 4
+#define W4_HH (W4_TH + 2)
+#define W4G_X (W4_HH * WH_W * 64)  // floats
+#define W4G_Y (W4_TH * WT_W * 64)
+#define W4G_CHUNK (4 * 32 * 64)
+#define W4G_LDS ((W4G_X + W4G_Y + 2 * W4G_CHUNK) * 4)  // bytes: 150528
+
+__global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* const ldx = lds;
+  float* const ldy = lds + W4G_X;
+  float* const vch = ldy + W4G_Y;
+  float* const mch = vch + W4G_CHUNK;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int pair = blockIdx.y;
+  const int cq = pair % p.cout_chunks, cc = pair / p.cout_chunks;
+  const int cih = __builtin_amdgcn_readfirstlane(wave >> 1), coh = __builtin_amdgcn_readfirstlane(wave & 1);
+  const int i = lane & 31, kk = lane >> 5;
+  const int H = p.H, W = p.W;
+  const bool do_bias = p.bias_slabs && cc == 0;
+  const bool affine = p.dy_scale != nullptr || p.dy_shift != nullptr;  // scalar
+  const int Cout = p.cout_chunks * 64;
+
+  f32x16 acc[16];
+#pragma unroll
+  for (int t = 0; t < 16; ++t) acc[t] = (f32x16){0};
+  f32x4 bsa = {0.f, 0.f, 0.f, 0.f}, bsb = bsa;
+
+  const int tiles_w = p.tiles_w, tiles_h = (H + W4_TH - 1) / W4_TH;
+  const int tiles_per_img = tiles_w * tiles_h;
+  const int total = tiles_per_img * p.B;
+  int t_begin = blockIdx.x, t_end = total, t_step = p.S;
+  if ((p.S & 7) == 0) {
+    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3, per = (total + 7) >> 3;
+    t_begin = xcd * per + idx;
+    t_end = min(total, (xcd + 1) * per);
+    t_step = p.S >> 3;
+  }
+  struct Stage {
+    f32x4 x[W4_HH][2];
+    f32x4 xe[2];
+    f32x4 y[W4_TH][2];
+  };
+  Stage st;
+  const int c8 = tid & 7, pcol = tid >> 3;
+  const int eidx = tid % 96, er = eidx >> 4, eside = (eidx >> 3) & 1, ec8 = eidx & 7;  // edge columns: 6 x 2 x 8 items
+  auto decode = [&](int tile, int& b, int& h0, int& w0) {
+    b = tile / tiles_per_img;
+    const int tr = tile - b * tiles_per_img;
+    const int th = tr / tiles_w;
+    h0 = th * W4_TH;
+    w0 = (tr - th * tiles_w) * WT_W;
+  };
+  auto issue = [&](int tile) {
+    int b, h0, w0;
+    decode(tile, b, h0, w0);
+    const sisr_rsrc_t rx = sisr_rsrc(p.x + (long)b * p.xv.sB + p.xv.chunk(cc));
+    const sisr_rsrc_t ry = sisr_rsrc(p.dy + (long)b * p.yv.sB + p.yv.chunk(cq));
+    const unsigned vx = (unsigned)(min(w0 + pcol, W - 1) * (int)p.xv.sW + c8 * 8) * 4u;
+    const unsigned vy = (unsigned)(min(w0 + pcol, W - 1) * (int)p.yv.sW + c8 * 8) * 4u;
+#pragma unroll
+    for (int r = 0; r < W4_HH; ++r) {
+      const unsigned so = (unsigned)(min(max(h0 - 1 + r, 0), H - 1) * (int)p.xv.sH) * 4u;  // scalar
+      st.x[r][0] = sisr_buf_load4(rx, vx, so);
+      st.x[r][1] = sisr_buf_load4(rx, vx + 16u, so);
+    }
+    {
+      const int gwe = min(max(eside ? w0 + WT_W : w0 - 1, 0), W - 1);
+      const unsigned ve = (unsigned)(min(max(h0 - 1 + er, 0), H - 1) * (int)p.xv.sH + gwe * (int)p.xv.sW + ec8 * 8) * 4u;
+      st.xe[0] = sisr_buf_load4(rx, ve, 0u);
+      st.xe[1] = sisr_buf_load4(rx, ve + 16u, 0u);
+    }
+#pragma unroll
+    for (int r = 0; r < W4_TH; ++r) {
+      const unsigned so = (unsigned)(min(h0 + r, H - 1) * (int)p.yv.sH) * 4u;  // scalar
+      st.y[r][0] = sisr_buf_load4(ry, vy, so);
+      st.y[r][1] = sisr_buf_load4(ry, vy + 16u, so);
+    }
+  };
+  auto commit = [&](int tile) {
+    int b, h0, w0;
+    decode(tile, b, h0, w0);
+    const bool interior = h0 >= 1 && h0 + W4_TH + 1 <= H && w0 >= 1 && w0 + WT_W + 1 <= W;  // scalar
+    const bool okc = w0 + pcol < W;
+    if (!interior) {
+#pragma unroll
+      for (int r = 0; r < W4_HH; ++r) {
+        const int gh = h0 - 1 + r;
+        const bool ok = gh >= 0 && gh < H && okc;
+        st.x[r][0] = sisr_keep_if(st.x[r][0], ok);
+        st.x[r][1] = sisr_keep_if(st.x[r][1], ok);
+      }
+      const int gwe = eside ? w0 + WT_W : w0 - 1, ghe = h0 - 1 + er;
+      const bool oke = ghe >= 0 && ghe < H && gwe >= 0 && gwe < W;
+      st.xe[0] = sisr_keep_if(st.xe[0], oke);
+      st.xe[1] = sisr_keep_if(st.xe[1], oke);
+    }
+    float* lx = ldx + (pcol + 1) * 64 + c8 * 8;
+#pragma unroll
+    for (int r = 0; r < W4_HH; ++r) {
+      *reinterpret_cast<f32x4*>(lx + r * (WH_W * 64)) = st.x[r][0];
+      *reinterpret_cast<f32x4*>(lx + r * (WH_W * 64) + 4) = st.x[r][1];
+    }
+    if (tid < 96) {
+      float* le = ldx + (er * WH_W + (eside ? WH_W - 1 : 0)) * 64 + ec8 * 8;
+      *reinterpret_cast<f32x4*>(le) = st.xe[0];
+      *reinterpret_cast<f32x4*>(le + 4) = st.xe[1];
+    }
+    if (affine) {
+      f32x4 s4a = {1.f, 1.f, 1.f, 1.f}, s4b = s4a, t4a = {0.f, 0.f, 0.f, 0.f}, t4b = t4a;
+      if (p.dy_scale) {
+        const float* sp = p.dy_scale + (long)b * Cout + cq * 64 + c8 * 8;
+        s4a = *reinterpret_cast<const f32x4*>(sp);
+        s4b = *reinterpret_cast<const f32x4*>(sp + 4);
+      }
+      if (p.dy_shift) {
+        const float* tp = p.dy_shift + (long)b * Cout + cq * 64 + c8 * 8;
+        t4a = *reinterpret_cast<const f32x4*>(tp);
+        t4b = *reinterpret_cast<const f32x4*>(tp + 4);
+      }
+#pragma unroll
+      for (int r = 0; r < W4_TH; ++r) {
+        st.y[r][0] = st.y[r][0] * s4a + t4a;
+        st.y[r][1] = st.y[r][1] * s4b + t4b;
+      }
+    }
+    if (!interior) {
+#pragma unroll
+      for (int r = 0; r < W4_TH; ++r) {
+        const bool ok = okc && h0 + r < H;
+        st.y[r][0] = sisr_keep_if(st.y[r][0], ok);
+        st.y[r][1] = sisr_keep_if(st.y[r][1], ok);
+      }
+    }
+    float* ly = ldy + pcol * 64 + c8 * 8;
+#pragma unroll
+    for (int r = 0; r < W4_TH; ++r) {
+      *reinterpret_cast<f32x4*>(ly + r * (WT_W * 64)) = st.y[r][0];
+      *reinterpret_cast<f32x4*>(ly + r * (WT_W * 64) + 4) = st.y[r][1];
+    }
+    if (do_bias) {
+#pragma unroll
+      for (int r = 0; r < W4_TH; ++r) {
+        bsa += st.y[r][0];
+        bsb += st.y[r][1];
+      }
+    }
+  };
+
+  // chunk builder: thread (block vb = tid >> 3 = (row vbr, column vbc), 16-B pieces q and q + 8 of the 64 channels)
+  const int vb = tid >> 3, q = tid & 7;
+  const int vbr = vb >> 4, vbc = vb & 15;
+  auto build = [&](int xr) {
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+      const int ch = (q + 8 * hf) * 4;
+      {  // V = B^T d B: rows xr 0: d0 - d2, 1: d1 + d2, 2: d2 - d1, 3: d1 - d3, then the same over columns
+        const int ra = xr == 0 ? 0 : (xr == 3 ? 3 : 2), rb = xr == 0 ? 2 : 1;
+        f32x4 rr[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float* base = ldx + (2 * vbc + j) * 64 + ch;
+          const f32x4 da = *reinterpret_cast<const f32x4*>(base + (2 * vbr + ra) * (WH_W * 64));
+          const f32x4 db = *reinterpret_cast<const f32x4*>(base + (2 * vbr + rb) * (WH_W * 64));
+          rr[j] = xr == 0 ? da - db : (xr == 1 ? db + da : (xr == 2 ? da - db : db - da));
+        }
+        float* vw = vch + vb * 64 + ch;
+        *reinterpret_cast<f32x4*>(vw + 0 * 2048) = rr[0] - rr[2];
+        *reinterpret_cast<f32x4*>(vw + 1 * 2048) = rr[1] + rr[2];
+        *reinterpret_cast<f32x4*>(vw + 2 * 2048) = rr[2] - rr[1];
+        *reinterpret_cast<f32x4*>(vw + 3 * 2048) = rr[1] - rr[3];
+      }
+      {  // M = A dY' A^T with A's last row negated: rows xr 0: y0, 1: y0 + y1, 2: y0 - y1, 3: y1, then over columns
+        f32x4 rr[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const float* base = ldy + (2 * vbc + j) * 64 + ch;
+          const f32x4 y0 = *reinterpret_cast<const f32x4*>(base + (2 * vbr) * (WT_W * 64));
+          const f32x4 y1 = *reinterpret_cast<const f32x4*>(base + (2 * vbr + 1) * (WT_W * 64));
+          rr[j] = xr == 0 ? y0 : (xr == 1 ? y0 + y1 : (xr == 2 ? y0 - y1 : y1));
+        }
+        float* mw = mch + vb * 64 + ch;
+        *reinterpret_cast<f32x4*>(mw + 0 * 2048) = rr[0];
+        *reinterpret_cast<f32x4*>(mw + 1 * 2048) = rr[0] + rr[1];
+        *reinterpret_cast<f32x4*>(mw + 2 * 2048) = rr[0] - rr[1];
+        *reinterpret_cast<f32x4*>(mw + 3 * 2048) = rr[1];
+      }
+    }
+  };
+
+  if (t_begin < t_end) {
+    issue(t_begin);
+    commit(t_begin);
+  }
+  for (int tile = t_begin; tile < t_end; tile += t_step) {
+    const bool has_next = tile + t_step < t_end;  // uniform
+    if (has_next) issue(tile + t_step);
+#pragma unroll
+    for (int xr = 0; xr < 4; ++xr) {
+      __syncthreads();  // the previous chunks are consumed (and the raw image committed)
+      build(xr);
+      __syncthreads();
+      if (xr == 3 && has_next) commit(tile + t_step);  // no wave reads the raw image again
+      // ---- 4 xc x 16 K-steps of two blocks: step s = xc * 16 + ks reads block 2 s + kk of the chunk pair
+      const float* va = vch + kk * 64 + cih * 32 + i;
+      const float* vm = mch + kk * 64 + coh * 32 + i;
+      float pa[4], pb[4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        pa[s] = va[s * 128];
+        pb[s] = vm[s * 128];
+      }
+#pragma unroll
+      for (int s = 0; s < 64; ++s) {
+        const float a = pa[s & 3], bb = pb[s & 3];
+        if (s + 4 < 64) {
+          pa[s & 3] = va[(s + 4) * 128];
+          pb[s & 3] = vm[(s + 4) * 128];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        acc[xr * 4 + (s >> 4)] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bb, acc[xr * 4 + (s >> 4)], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  }
+
+  // ---- fold dg = G^T dU G per element (rows of G: (1,0,0), (1/2,1/2,1/2), (1/2,-1/2,1/2), (0,0,1); the last with the sign
+  // of M's negated row), store the quadrant slab in the dense kernel's layout
+  {
+    float* out = p.slabs + ((long)blockIdx.x * ((long)gridDim.y * 4) + pair * 4 + cih * 2 + coh) * SLAB;
+    auto fold = [](float u0, float u1, float u2, float u3, float& f0, float& f1, float& f2) {
+      const float h = 0.5f * (u1 + u2);
+      f0 = u0 + h;
+      f1 = 0.5f * (u1 - u2);
+      f2 = h - u3;
+    };
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float rw[3][4];
+#pragma unroll
+      for (int xc = 0; xc < 4; ++xc) fold(acc[xc][r], acc[4 + xc][r], acc[8 + xc][r], acc[12 + xc][r], rw[0][xc], rw[1][xc], rw[2][xc]);
+#pragma unroll
+      for (int kh = 0; kh < 3; ++kh) {
+        float g0, g1, g2;
+        fold(rw[kh][0], rw[kh][1], rw[kh][2], rw[kh][3], g0, g1, g2);
+        out[((kh * 3 + 0) * 16 + r) * 64 + lane] = g0;
+        out[((kh * 3 + 1) * 16 + r) * 64 + lane] = g1;
+        out[((kh * 3 + 2) * 16 + r) * 64 + lane] = g2;
+      }
+    }
+  }
+  if (do_bias) {
+    __syncthreads();
+    float* red = lds;
+    *reinterpret_cast<f32x4*>(red + tid * 8) = bsa;
+    *reinterpret_cast<f32x4*>(red + tid * 8 + 4) = bsb;
+    __syncthreads();
+    if (tid < 64) {  // channel tid = c8 * 8 + e lives in the threads with (tid & 7) == c8
+      const int cc8 = tid >> 3, e = tid & 7;
+      float s = 0.f;
+      for (int k = 0; k < 32; ++k) s += red[(k * 8 + cc8) * 8 + e];
+      p.bias_slabs[((long)blockIdx.x * p.cout_chunks + cq) * 64 + tid] = s;
+    }
+  }
+}
+
 // ------------------------------------------------------------------ bf16 matrix-core weight gradient
 // Operands rounded to bf16 (RNE) as they are staged into LDS, products exact, fp32 accumulation; the bias
 // gradient is summed from the unrounded fp32 dY'.  A workgroup owns all 64 ci x 64 co of one (cin chunk, cout
@@ -1219,7 +1507,16 @@ static int wgrad_fp32_launch(const float* x, const int64_t* xview, const float* 
   p.S = dense ? wgrad_full_split(B, H, W, units / 4) : wgrad_split(B, H, W, units);
   p.slabs = workspace;
   p.bias_slabs = dbias ? workspace + (size_t)p.S * units * SLAB : nullptr;
-  if (dense) {  // one persistent workgroup per CU owning all four quadrants of its chunk pair
+  // The Winograd form replaces the dense one from the forward's threshold up (more than 8 x 128^2 pixels per launch; below
+  // it the batched weight gradients must keep computing what a single launch does).  SISR_WGRAD_WINOGRAD=0, or the forward's
+  // SISR_CONV_WINOGRAD=0, switches it off per call.  Its K-split and slabs are the dense form's.
+  const char* ew = getenv("SISR_WGRAD_WINOGRAD");
+  const char* ec = getenv("SISR_CONV_WINOGRAD");
+  const bool wino = dense && !geo && (long)B * H * W > 8L * 128 * 128 && !(ew && ew[0] == '0') && !(ec && ec[0] == '0');
+  if (wino) {
+    SISR_ALLOW_LDS(wgrad3x3_c64_w4_kernel, (size_t)W4G_LDS);
+    hipLaunchKernelGGL(wgrad3x3_c64_w4_kernel, dim3(p.S, units / 4), dim3(256), (size_t)W4G_LDS, (hipStream_t)stream, p);
+  } else if (dense) {  // one persistent workgroup per CU owning all four quadrants of its chunk pair
     const size_t lds_full = (size_t)(FW_X + FW_Y) * sizeof(float);
     if (geo) {
       SISR_ALLOW_LDS(wgrad3x3_c64_full_geo_kernel, lds_full);
