@@ -556,6 +556,18 @@ int sisr_nl_output_bwd_parts(const int* domains);
 int sisr_nl_output_bwd(const float* dz, const float* y, const float* w, float* dy, float* part, const int* domains,
                        void* stream);
 
+/* ---- image-quality metrics (csrc/metrics.hip) ----------------------------------------------------------------------
+ * ref: sr_tools/metrics.py:64-91 -> skimage.metrics.structural_similarity(a, b, data_range, gaussian_weights=True, sigma=1.5,
+ * use_sample_covariance=False), float64 form: Gaussian window (11 taps, sigma 1.5), population covariance, the mean of the SSIM
+ * map over the (h - 10) x (w - 10) windows that lie inside the image.  a, b: n contiguous fp32 images [n][channels][h][w];
+ * channels == 3: RGB, clipped to [0, 1] and compared on Y = (0.299 R + 0.587 G) + 0.114 B in fp32 (NaN stays NaN);
+ * channels == 1: the planes as given.  out: n doubles on the device, one SSIM per image.  Two launches, no atomics: a repeat
+ * call is bit-identical.  Refused before any launch (-1): null pointers, n <= 0, h or w < 11, channels other than 1 or 3,
+ * data_range not finite or <= 0, workspace_bytes < sisr_ssim_workspace_bytes(n, h, w). */
+size_t sisr_ssim_workspace_bytes(int n, int h, int w);
+int sisr_ssim(const float* a, const float* b, int n, int channels, int h, int w, double data_range, double* out,
+              void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """train_sisr / eval_sisr entry points (same TOML schema and outputs as the reference's console scripts).
 
 ref: Code/SISR/net_train.py:16-74 (experiment_setup), Code/SISR/training/training_handler.py:25-323
-     (TrainingHandler: epoch loop, Y-PSNR validation, summary.csv, per-epoch checkpoints, early stopping),
+     (TrainingHandler: epoch loop, Y-PSNR / Y-SSIM validation, summary.csv, per-epoch checkpoints, early stopping),
      Code/SISR/net_eval.py:20-74 + Code/SISR/evaluation/standard_eval.py:217-319 (full_image_protocol).
 Run:  python -m sisr_cli train --parameters cfg.toml      |      python -m sisr_cli eval --config cfg.toml
 With WORLD_SIZE > 1 (torch.distributed.run) training is data parallel: every rank walks the same seeded
@@ -105,14 +105,23 @@ class TrainingHandler:
 
     def eval(self, epoch_idx):
         losses = defaultdict(list)
+        wanted = list(dict.fromkeys(self.metrics or ()))  # columns follow the order the metrics are listed in
         for batch in self.val_data:
             y = batch['hr']
-            rgb_out, ycbcr_out, loss, _ = self.model.net_run_and_process(**batch, request_loss=True)
+            if 'SSIM' in wanted:  # SSIM on the device output, before it is copied back
+                rgb_out, ycbcr_out, loss, _, measured = self.model.net_run_process_and_measure(
+                    **batch, metrics=wanted, max_value=self.max_im_val, request_loss=True)
+            else:
+                rgb_out, ycbcr_out, loss, _ = self.model.net_run_and_process(**batch, request_loss=True)
+                measured = {}
             y_proc = self.model.colorspace_convert(y, colorspace='rgb')
             losses['val-loss'].append(loss)
-            if self.metrics and 'PSNR' in self.metrics:
-                for i in range(ycbcr_out.shape[0]):
-                    losses['val-PSNR'].append(M.psnr(ycbcr_out[i, 0], y_proc[i, 0], max_value=self.max_im_val))
+            for metric in wanted:
+                if metric == 'PSNR':
+                    for i in range(ycbcr_out.shape[0]):
+                        losses['val-PSNR'].append(M.psnr(ycbcr_out[i, 0], y_proc[i, 0], max_value=self.max_im_val))
+                elif metric == 'SSIM':
+                    losses['val-SSIM'].extend(measured['SSIM'])
         return losses
 
     def run_experiment(self):
@@ -181,7 +190,8 @@ def train_sisr(parameters, experiment_name=None, **overrides):
 
 
 def eval_sisr(config=None, **kw):
-    """ref: net_eval.py:64-74 / standard_eval.py full_image_protocol: per-image and average Y-PSNR CSVs."""
+    """ref: net_eval.py:64-74 / standard_eval.py full_image_protocol: per-image and average Y-PSNR CSVs, plus Y-SSIM
+    columns when the config's `metrics` lists 'SSIM' (ref: standard_eval.py:268-271)."""
     import pandas as pd
     cfg = dict(_load_toml(config)) if config is not None else {}
     cfg.update({k: v for k, v in kw.items() if v is not None})
@@ -199,14 +209,22 @@ def eval_sisr(config=None, **kw):
                           dataset=cfg.get('dataset_name'), scale=scale, degradation_metadata_file=meta,
                           recursive_search=bool(cfg.get('recursive')))
     loader = torch.utils.data.DataLoader(dataset=data, batch_size=cfg.get('batch_size', 1))
+    with_ssim = 'SSIM' in (cfg.get('metrics') or ())
     rows = []
     for batch in loader:
         y_proc = ModelInterface.colorspace_convert(batch['hr'], colorspace='rgb')
         for m in models:
-            rgb, ycbcr, _, secs = m.net_run_and_process(**batch, timing=cfg.get('time_models', True))
+            if with_ssim:  # SSIM on the device output (data_range 1), outside the timed window
+                rgb, ycbcr, _, secs, measured = m.net_run_process_and_measure(**batch, metrics=['SSIM'], max_value=1,
+                                                                              timing=cfg.get('time_models', True))
+            else:
+                rgb, ycbcr, _, secs = m.net_run_and_process(**batch, timing=cfg.get('time_models', True))
             for i, tag in enumerate(batch['tag']):
-                rows.append({'Image_Name': tag, 'Model': m.experiment, 'PSNR': M.psnr(ycbcr[i, 0], y_proc[i, 0], 1),
-                             'runtime': secs})
+                row = {'Image_Name': tag, 'Model': m.experiment, 'PSNR': M.psnr(ycbcr[i, 0], y_proc[i, 0], 1)}
+                if with_ssim:
+                    row['SSIM'] = measured['SSIM'][i]
+                row['runtime'] = secs
+                rows.append(row)
             if cfg.get('save_im'):
                 from PIL import Image
                 d = os.path.join(out_dir, m.experiment)
@@ -218,7 +236,7 @@ def eval_sisr(config=None, **kw):
     mdir = os.path.join(out_dir, 'standard_metrics')
     create_dir_if_empty(mdir)
     df.to_csv(os.path.join(mdir, 'individual_metrics.csv'), index=False)
-    avg = df.groupby('Model')[['PSNR', 'runtime']].mean().reset_index()
+    avg = df.groupby('Model')[['PSNR', 'SSIM', 'runtime'] if with_ssim else ['PSNR', 'runtime']].mean().reset_index()
     avg.to_csv(os.path.join(mdir, 'average_metrics.csv'), index=False)
     return df, avg
 

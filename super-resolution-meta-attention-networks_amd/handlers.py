@@ -23,6 +23,7 @@ from torch import nn, optim
 
 from . import architectures as A
 from . import metrics, ops
+from .metrics import batch_ssim
 
 
 class L1Loss(nn.Module):
@@ -612,6 +613,24 @@ class ModelInterface:
         out_ycbcr = self.colorspace_convert(out_rgb, colorspace='rgb')
         out_rgb = self._standard_image_formatting(out_rgb.numpy())
         return out_rgb, out_ycbcr, loss, timing
+
+    def net_run_process_and_measure(self, lr=None, hr=None, metrics=(), max_value=1, **kwargs):
+        """net_run_and_process plus per-image image-quality metrics of the output against `hr`, measured where the output
+        is (on the device, sisr_ssim, when the model runs on one) and outside the `timing` window.
+        -> (rgb, ycbcr, loss, timing, {metric: [one value per image]}).  Measured here: 'SSIM' (Y channels, data_range
+        `max_value`); PSNR stays with the callers, on the host."""
+        if 'rgb' not in self.configuration['colorspace']:
+            raise NotImplementedError('Y-channel-only models (SRCNN/VDSR) are out of scope of the HIP path')
+        out, loss, timing = self.model.run_eval(x=lr, y=hr, keep_on_device=True, **kwargs)
+        measured = {}
+        if 'SSIM' in metrics:
+            if hr is None:
+                raise RuntimeError('Need a reference to calculate SSIM.')
+            measured['SSIM'] = batch_ssim(out, hr.to(device=out.device), max_value=max_value)
+        out_rgb = out.cpu()
+        out_ycbcr = self.colorspace_convert(out_rgb, colorspace='rgb')
+        out_rgb = self._standard_image_formatting(out_rgb.numpy())
+        return out_rgb, out_ycbcr, loss, timing, measured
 
     @staticmethod
     def colorspace_convert(image, colorspace='rgb'):

@@ -7,7 +7,7 @@ for device memory and streams only (``tensor.data_ptr()``, ``torch.cuda.current_
 import collections
 import ctypes
 import os
-from ctypes import c_float, c_int, c_int64, c_long, c_size_t, c_void_p
+from ctypes import c_double, c_float, c_int, c_int64, c_long, c_size_t, c_void_p
 
 import torch  # noqa: F401  (must be imported first: libsisr_hip.so binds to torch's libamdhip64.so.7 by SONAME)
 
@@ -177,6 +177,11 @@ _SIGS.update({  # SAN attention (csrc/san.hip)
     "sisr_soca_bwd_apply": (c_int, [P, P, P, P, P, P, c_int, c_long, c_int, P]),
     "sisr_nl_attn_fwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "sisr_nl_attn_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
+})
+
+_SIGS.update({  # image-quality metrics (csrc/metrics.hip)
+    "sisr_ssim_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "sisr_ssim": (c_int, [P, P, c_int, c_int, c_int, c_int, c_double, P, P, c_size_t, P]),
 })
 
 

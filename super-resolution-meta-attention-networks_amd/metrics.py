@@ -1,7 +1,11 @@
-"""PSNR on the BT.601 'jpg' luma, the reference's parity metric (host-side numpy).
+"""PSNR and SSIM on the BT.601 'jpg' luma, the reference's validation / evaluation metrics.
 
-ref: Code/sr_tools/metrics.py:6-17 (psnr), Code/sr_tools/image_manipulation.py:65-89 (rgb_to_ycbcr 'jpg'),
-     Code/SISR/models/__init__.py:158-169 (clip to [0,1] before conversion).
+PSNR is host-side numpy.  SSIM has a host float64 form (`ssim`, numpy only) and a device form (csrc/metrics.hip,
+`sisr_ssim`) that `batch_ssim` uses for tensors on a HIP device.
+
+ref: Code/sr_tools/metrics.py:6-17 (psnr), :64-91 (ssim: skimage.metrics.structural_similarity with gaussian_weights=True,
+     sigma=1.5, use_sample_covariance=False, on Y planes one image at a time), Code/sr_tools/image_manipulation.py:65-89
+     (rgb_to_ycbcr 'jpg'), Code/SISR/models/__init__.py:158-169 (clip to [0,1] before conversion).
 """
 import numpy as np
 
@@ -11,6 +15,53 @@ def psnr(img1, img2, max_value=255.0):
     if mse == 0:
         return 100
     return 20 * np.log10(max_value / (np.sqrt(mse)))
+
+
+SSIM_SIGMA, SSIM_TRUNCATE = 1.5, 3.5
+SSIM_RADIUS = int(SSIM_TRUNCATE * SSIM_SIGMA + 0.5)  # 5: an 11 x 11 window
+
+
+def ssim_taps():
+    """The 11 Gaussian taps, computed as scipy.ndimage's _gaussian_kernel1d(1.5, 0, 5) computes them."""
+    x = np.arange(-SSIM_RADIUS, SSIM_RADIUS + 1)
+    phi = np.exp(-0.5 / (SSIM_SIGMA * SSIM_SIGMA) * x ** 2)
+    return phi / phi.sum()
+
+
+def _valid_gauss(m, taps):
+    """Separable correlation with `taps` over the windows that lie inside the 2-D map `m` (rows, then columns)."""
+    k = len(taps)
+    h, w = m.shape[0] - k + 1, m.shape[1] - k + 1
+    t = taps[0] * m[0:h]
+    for i in range(1, k):
+        t = t + taps[i] * m[i:i + h]
+    u = taps[0] * t[:, 0:w]
+    for i in range(1, k):
+        u = u + taps[i] * t[:, i:i + w]
+    return u
+
+
+def ssim(img1, img2, max_value=1):
+    """Mean SSIM of two 2-D images in float64: skimage.metrics.structural_similarity(img1, img2, data_range=max_value,
+    gaussian_weights=True, sigma=1.5, use_sample_covariance=False) as scikit-image 0.16-0.18 computes it.  Its map is cropped
+    by the filter radius, so only windows inside the image count and the filter's padding mode never shows."""
+    x = np.asarray(img1, dtype=np.float64)
+    y = np.asarray(img2, dtype=np.float64)
+    if x.ndim != 2 or x.shape != y.shape:
+        raise ValueError(f"ssim takes two 2-D images of one shape; got {x.shape} and {y.shape}")
+    win = 2 * SSIM_RADIUS + 1
+    if min(x.shape) < win:
+        raise ValueError("win_size exceeds image extent.  Either ensure that your images are at least 11x11; or pass "
+                         "win_size explicitly in the function call, with an odd value less than or equal to the smaller "
+                         "side of your images.")
+    taps = ssim_taps()
+    ux, uy = _valid_gauss(x, taps), _valid_gauss(y, taps)
+    uxx, uyy, uxy = _valid_gauss(x * x, taps), _valid_gauss(y * y, taps), _valid_gauss(x * y, taps)
+    vx, vy, vxy = uxx - ux * ux, uyy - uy * uy, uxy - ux * uy
+    c1, c2 = (0.01 * max_value) ** 2, (0.03 * max_value) ** 2
+    a1, a2 = 2 * ux * uy + c1, 2 * vxy + c2
+    b1, b2 = ux ** 2 + uy ** 2 + c1, vx + vy + c2
+    return float(((a1 * a2) / (b1 * b2)).mean(dtype=np.float64))
 
 
 def rgb_to_ycbcr_jpg(img, max_val=1):
@@ -39,3 +90,41 @@ def y_psnr(sr, hr, max_value=1):
     a = rgb_to_ycbcr_jpg(standard_image_formatting(np.asarray(sr)))[0]
     b = rgb_to_ycbcr_jpg(standard_image_formatting(np.asarray(hr)))[0]
     return psnr(a, b, max_value=max_value)
+
+
+def y_ssim(sr, hr, max_value=1):
+    """SSIM between the Y channels of a clipped SR image and its HR reference (both C,H,W RGB in [0,1])."""
+    a = rgb_to_ycbcr_jpg(standard_image_formatting(np.asarray(sr)))[0]
+    b = rgb_to_ycbcr_jpg(standard_image_formatting(np.asarray(hr)))[0]
+    return ssim(a, b, max_value=max_value)
+
+
+def batch_ssim(sr, hr, max_value=1):
+    """Per-image SSIM of two (N, C, H, W) batches -> list of N floats.  C == 3: clipped RGB compared on Y (as y_ssim);
+    C == 1: Y planes used as given.  If either batch is a tensor on a HIP device, both go to the device kernel (sisr_ssim,
+    fp32 contiguous copies made here); anything else takes the host float64 form."""
+    import torch
+    dev = next((t.device for t in (sr, hr) if isinstance(t, torch.Tensor) and t.is_cuda), None)
+    if dev is None:
+        a, b = (t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in (sr, hr))
+        if a.ndim != 4 or a.shape != b.shape or a.shape[1] not in (1, 3):
+            raise ValueError(f"batch_ssim takes two (N, 1|3, H, W) batches of one shape; got {a.shape} and {b.shape}")
+        if a.shape[1] == 3:
+            a, b = batch_rgb_to_ycbcr(a), batch_rgb_to_ycbcr(b)
+        return [ssim(a[i, 0], b[i, 0], max_value=max_value) for i in range(a.shape[0])]
+    from . import hip
+    a, b = (torch.as_tensor(t).to(device=dev, dtype=torch.float32).contiguous() for t in (sr, hr))
+    if a.dim() != 4 or a.shape != b.shape or a.shape[1] not in (1, 3):
+        raise ValueError(f"batch_ssim takes two (N, 1|3, H, W) batches of one shape; got {tuple(a.shape)} and "
+                         f"{tuple(b.shape)}")
+    n, c, h, w = a.shape
+    L = hip.lib()
+    nbytes = L.sisr_ssim_workspace_bytes(n, h, w)
+    if nbytes == 0:
+        raise ValueError("win_size exceeds image extent.  Images must be at least 11x11.")
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(n, dtype=torch.float64, device=dev)
+        hip.check(L.sisr_ssim(hip.ptr(a), hip.ptr(b), n, c, h, w, float(max_value), out.data_ptr(), ws.data_ptr(), nbytes,
+                              hip.stream()), "sisr_ssim")
+    return out.cpu().tolist()
