@@ -86,8 +86,9 @@ typedef struct {
   int head_parts, head;
 } sisr_ca_tail;
 size_t sisr_ca_tail_bytes(void);
-/* select: 0 (= 4) issue-lean kernel, tile height chosen by grid size, general kernel as fallback; 5 / 6 the same with
- * the 4-row / 2-row tile forced (bit-identical results; A/B measurements and tests); 2 general kernel only.
+/* select: 0 (= 4) issue-lean kernel -- per-tile (2-row tiles) below 1024 4 x 32 tiles per launch, persistent from there up
+ * (SISR_CONV_PERSISTENT=0: never) -- with the general kernel as fallback; 6 / 7 the same with the per-tile / persistent
+ * form forced (bit-identical results; A/B measurements and tests); 2 general kernel only.  1, 3 and 5 are refused.
  * 8 / 9 / 10: the caller asserts structural zeros in the packed weight (SFTMD's merged convs) and the kernel skips them:
  *   8  64 -> 128 block-diagonal (output chunk q contracts input channels 32q .. 32q+31 only), plain epilogue;
  *   9  128 -> 64 whose input channels >= 80 are zero (second chunk: first 16 channels only), LeakyReLU epilogue;

@@ -25,19 +25,6 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#ifdef SISR_WT_STORES
-#define SISR_Y_STORE1 sisr_buf_store1_wt
-#define SISR_Y_STORE4 sisr_buf_store4_wt
-#else
-#define SISR_Y_STORE1 sisr_buf_store1
-#define SISR_Y_STORE4 sisr_buf_store4
-#endif
-#ifndef SISR_GATE_WGS
-#define SISR_GATE_WGS 4   // resident workgroups per CU of the 2-row GATE build (3: single-batch staging, see the kernel)
-#endif
-#ifndef SISR_GATE_PRIO
-#define SISR_GATE_PRIO 0  // 1: the GATE prologue (two maps, arithmetic, a store) runs at wave priority 3
-#endif
 #define TH 4
 #define TW 32
 #define HALO_H (TH + 2)
@@ -285,21 +272,23 @@ __global__ __launch_bounds__(256, 3) void conv3x3_c64_kernel(ConvParams p) {
 // In-kernel stamps and the pure-MFMA ceiling (tools/conv_phases.py, tools/mfma_peak.py) showed that the fp32
 // MFMA holds its SIMD's issue port for the whole 64 cycles: every other instruction a co-resident wave
 // issues is paid on top, so throughput = 64 / (64 + 4 * non-MFMA instructions per MFMA).  conv3x3_c64_kernel
-// spent ~4.6 such instructions per MFMA (82 % ceiling).  This variant keeps the same tile / wave / LDS
-// geometry and cuts them to ~1.3:
+// spent ~4.6 such instructions per MFMA (82 % ceiling).  This variant keeps the same wave / LDS geometry on a tile
+// of V4_TH = 2 rows x 32 columns (wave (ph, ch) -> row ph x channels [32ch, 32ch+32): one 32x32 accumulator; four rows
+// of halo, 34.8 KB, four resident workgroups per CU) and cuts them to ~1.3:
 //   * halo staging walks (row, 16-column block) pairs: row base is scalar, the lane's column offset is one
 //     of three precomputed VGPRs -> one global_load (saddr+voffset) + one mask op + one ds_write per item;
 //   * the LDS swizzle uses the halo COLUMN (slot = chunk ^ (col & 15)), so the 24 (kw, octet) A addresses
-//     are lane constants computed once; tap row and M-tile enter as ds_read immediates (fully unrolled K loop);
+//     are lane constants computed once; the tap row enters as a ds_read immediate (fully unrolled K loop);
 //   * B fragments: scalar base + one lane offset VGPR + immediate;
 //   * bias is the accumulator's initial value; stores use scalar row/column bases + one lane offset; interior
 //     tiles take a predicate-free path.
 // Covers the block-hot combinations (plain/ReLU/scale, +GAP, +residual, +mask, +mask+affine prologue); anything
 // else is routed to conv3x3_c64_kernel.  Results are bit-identical to it (same MFMA order).
-// MT = output rows (32-pixel M-tiles) per wave: 2 -> the 4-row tile described above; 1 -> 2-row tiles (four rows
-// of halo, 34.8 KB, one accumulator) for launches whose 4-row grid has fewer workgroups than the chip has CUs (one 128x128 sample: 22.7 -> 14.3 us).
-// Both produce bit-identical outputs and GAP partials (same MFMA order per output element; partials are per
-// 2-row strip, summed row by row).
+// Why 2 rows: a 4 x 32 tile (two accumulators per wave, three workgroups per CU) leaves half the chip idle on one 128x128
+// sample (22.7 vs 14.3 us), and with buffer-addressed weight loads, which are free beside the MFMAs, the 2-row tile won at
+// every size measured (four resident workgroups and a finer last round), so this kernel has the one height.  Outputs
+// and GAP partials are bit-identical to the 4 x 32-tile kernels' (same MFMA order per output element; partials are per 2-row
+// strip, summed row by row, in the layout of sisr_conv3x3_c64_gap_parts).
 // GATE (forward of a gated residual chain): the conv's input is the previous block's output
 //   y = t * gate[b,c] + skip,  built while the halo is staged instead of by a separate pass; the tile that owns a
 // pixel also writes y out (the next skip / weight-gradient operand), so the map is read and written exactly once
@@ -311,7 +300,7 @@ __global__ __launch_bounds__(256, 3) void conv3x3_c64_kernel(ConvParams p) {
 // KSEL (SFTMD's merged convs, whose weights are structurally sparse; every other caller: 0 = the dense code path, untouched):
 //   1  block-diagonal 64 -> 128: output chunk q contracts input channels 32q .. 32q+31 only (4 of 8 octets per tap)
 //   2  128 -> 64 whose second input chunk carries at most 16 channels (2 of 8 octets per tap)
-//   3  the transpose of 1, 128 -> 64: input chunk c feeds output channels 32c .. 32c+31 only.  2-row tiles (MT = 1) with
+//   3  the transpose of 1, 128 -> 64: input chunk c feeds output channels 32c .. 32c+31 only.
 //      BOTH chunks' halos resident (2 x 34.8 KB): wave (row, half) runs one K loop over its own half's chunk -- no
 //      branch ("the other two waves skip the chunk" was a wave-uniform branch around the unrolled K loop: 118 spilled VGPRs)
 // The skipped products are exact zeros, so results are those of the dense kernel on the zero-padded weights.
@@ -326,14 +315,16 @@ __global__ __launch_bounds__(256, 3) void conv3x3_c64_kernel(ConvParams p) {
 // throw-away outputs is computed; with geo_off the same kernel produces the (H + 2) x (W + 2) transposed-conv result from an
 // H x W gradient.  KSEL 4 / 5 (one input chunk whose channels >= 32 / >= 8 are zero padding: 32-feature layers, RGB and
 // attention-logit ends): 4 / 1 of the 8 octets per tap.
-template <bool AFFINE, bool MASK, bool RES, int MT, bool GATE = false, bool DOT = false, bool LEAKY = false, int KSEL = 0, int HEAD = 0,
+#define V4_TH 2                                                    // output rows per tile
+#define V4_HALO_BYTES ((V4_TH + 2) * HALO_W * 64 * sizeof(float))  // LDS of one input chunk's halo (stride-1 forms)
+template <bool AFFINE, bool MASK, bool RES, bool GATE = false, bool DOT = false, bool LEAKY = false, int KSEL = 0, int HEAD = 0,
           bool GEO = false, bool S2 = false>
-__global__ __launch_bounds__(256, KSEL == 3 ? 2 : (MT == 1 ? (GATE ? SISR_GATE_WGS : 4) : 3)) void conv3x3_c64_v4_kernel(ConvParams p) {
-  // S2 (GEO, 2-row tiles): the stride-2 ConvLayer conv computed at its OUTPUT pixels -- lane n of an M-tile reads halo column
+__global__ __launch_bounds__(256, KSEL == 3 ? 2 : 4) void conv3x3_c64_v4_kernel(ConvParams p) {
+  // S2 (GEO): the stride-2 ConvLayer conv computed at its OUTPUT pixels -- lane n of an M-tile reads halo column
   // 2 n + kw of a 5-row x 66-column halo (84.5 KB) -- instead of the stride-1 conv subsampled (a quarter of the arithmetic)
-  static_assert(!S2 || (GEO && MT == 1 && !GATE && !AFFINE && HEAD == 0 && (KSEL == 0 || KSEL == 4)), "S2: plain GEO form only");
+  static_assert(!S2 || (GEO && !GATE && !AFFINE && HEAD == 0 && (KSEL == 0 || KSEL == 4)), "S2: plain GEO form only");
   constexpr int SS = S2 ? 2 : 1, HWv = S2 ? 66 : HALO_W, NK = S2 ? 5 : 3;
-  constexpr int THv = 2 * MT, HHv = S2 ? 2 * THv + 1 : THv + 2;
+  constexpr int THv = V4_TH, HHv = S2 ? 5 : 4;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   // (Static priorities per workgroup -- the four workgroups of a CU, ids 256 apart, at s_setprio 3 / 2 / 1 / 0 so that their K loops
   // run one after the other and only the last epilogue is exposed -- were measured at 4 tiles in round 4: within +-1 % on three
@@ -368,17 +359,17 @@ __global__ __launch_bounds__(256, KSEL == 3 ? 2 : (MT == 1 ? (GATE ? SISR_GATE_W
   }
 #endif
   const float bv = p.bias ? p.bias[co * p.bias_n + q * p.bias_q] : 0.f;
-  f32x16 acc0, acc1;  // acc1 is dead code for MT == 1
+  f32x16 acc;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = bv;
+  for (int r = 0; r < 16; ++r) acc[r] = bv;
 
-  // lane constants for the A reads: float offset of (halo row 2ph, col n+kw, slot (2j+hh)^((n+kw)&15))
+  // lane constants for the A reads: float offset of (halo row ph, col n+kw, slot (2j+hh)^((n+kw)&15))
   unsigned aoff[3][8];
 #pragma unroll
   for (int kw = 0; kw < 3; ++kw)
 #pragma unroll
     for (int j = 0; j < 8; ++j)
-      aoff[kw][j] = ((SS * MT * ph) * HWv + SS * n + kw) * 64 +
+      aoff[kw][j] = ((SS * ph) * HWv + SS * n + kw) * 64 +
                     (((2 * (KSEL == 1 ? (j & 3) + 4 * q : j) + hh) ^ ((SS * n + kw) & 15)) << 2) +
                     (KSEL == 3 ? ch * (HHv * HWv * 64) : 0);
   const unsigned boff = hh * 256 + co * 4;
@@ -512,10 +503,9 @@ __global__ __launch_bounds__(256, KSEL == 3 ? 2 : (MT == 1 ? (GATE ? SISR_GATE_W
                                    : *reinterpret_cast<const f32x4*>(p.in_scale + (long)b * 64 + c4 * 4);
         const sisr_rsrc_t ru = sisr_rsrc(p.gate_add + (long)b * p.xv.sB);
         const sisr_rsrc_t ro_ = sisr_rsrc(p.gate_out + (long)b * p.xv.sB);
-        // 2-row tiles with three resident workgroups (168 registers): both operand maps of all four halo rows are requested
-        // at once, one memory round trip per tile instead of two
-        constexpr int RB = (MT == 1 && SISR_GATE_WGS == 3) ? HHv : HHv / 2;
-        if (SISR_GATE_PRIO) __builtin_amdgcn_s_setprio(3);
+        // (Three resident workgroups (168 registers) with both operand maps of all four halo rows requested at once, and the
+        // prologue at wave priority 3, were measured and left out.)
+        constexpr int RB = HHv / 2;
 #pragma unroll
         for (int r0 = 0; r0 < HHv; r0 += RB) {
           f32x4 v[RB][3], u[RB][3];
@@ -542,11 +532,10 @@ __global__ __launch_bounds__(256, KSEL == 3 ? 2 : (MT == 1 ? (GATE ? SISR_GATE_W
                 if (interior) *reinterpret_cast<f32x4*>(lds + hr * (HWv * 64) + loff[k]) = t;
                 else *reinterpret_cast<f32x4*>(lds + hr * (HWv * 64) + loff[k]) = sisr_keep_if(t, rok && cok[k]);
                 const int col = pcol + 16 * k;
-                if (rown && cok[k] && col >= 1 && col <= TW) SISR_Y_STORE4(t, ro_, goff[k], ro);
+                if (rown && cok[k] && col >= 1 && col <= TW) sisr_buf_store4(t, ro_, goff[k], ro);
               }
           }
         }
-        if (SISR_GATE_PRIO) __builtin_amdgcn_s_setprio(0);
       }
     }
     __syncthreads();
@@ -562,34 +551,24 @@ __global__ __launch_bounds__(256, KSEL == 3 ? 2 : (MT == 1 ? (GATE ? SISR_GATE_W
         constexpr int NJ = decltype(nj_tag)::value, NS = 9 * NJ;
         const sisr_rsrc_t rwb = sisr_rsrc(wb);
         auto ldb = [&](int s) { return sisr_buf_load4(rwb, boff * 4u, (unsigned)(((s / NJ) * 8 + (s % NJ)) * 2048)); };
-        auto lda = [&](int m, int s) {
-          return *reinterpret_cast<const f32x4*>(lds + (((s / NJ) / 3 + m) * (HWv * 64)) + aoff[(s / NJ) % 3][s % NJ]);
+        auto lda = [&](int s) {
+          return *reinterpret_cast<const f32x4*>(lds + (((s / NJ) / 3) * (HWv * 64)) + aoff[(s / NJ) % 3][s % NJ]);
         };
         f32x4 bq[8];
-        f32x4 aq[4][2];
+        f32x4 aq[4];
 #pragma unroll
         for (int s = 0; s < 6; ++s) bq[s] = ldb(s);
 #pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          aq[s][0] = lda(0, s);
-          if (MT == 2) aq[s][1] = lda(1, s);
-        }
+        for (int s = 0; s < 2; ++s) aq[s] = lda(s);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
           if (s + 6 < NS) bq[(s + 6) & 7] = ldb(s + 6);
-          if (s + 2 < NS) {
-            aq[(s + 2) & 3][0] = lda(0, s + 2);
-            if (MT == 2) aq[(s + 2) & 3][1] = lda(1, s + 2);
-          }
+          if (s + 2 < NS) aq[(s + 2) & 3] = lda(s + 2);
           const f32x4 bb = bq[s & 7];
-          const f32x4 a0 = aq[s & 3][0];
-          const f32x4 a1 = aq[s & 3][1];
+          const f32x4 a0 = aq[s & 3];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[e], bb[e], acc0, 0, 0, 0);
-            if (MT == 2) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[e], bb[e], acc1, 0, 0, 0);
-          }
+          for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[e], bb[e], acc, 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
         }
       };
@@ -607,34 +586,23 @@ __global__ __launch_bounds__(256, KSEL == 3 ? 2 : (MT == 1 ? (GATE ? SISR_GATE_W
       }
     } else {
 #define V4_LOAD_B(s) sisr_buf_load4(rw, boff * 4u, (unsigned)((s) * 2048))
-#define V4_LOAD_A(m, s) \
-  (*reinterpret_cast<const f32x4*>(lds + ((((s) >> 3) / 3 + (m)) * (HWv * 64)) + aoff[((s) >> 3) % 3][(s) & 7]))
-    f32x4 aq[4][2];
+#define V4_LOAD_A(s) (*reinterpret_cast<const f32x4*>(lds + ((((s) >> 3) / 3) * (HWv * 64)) + aoff[((s) >> 3) % 3][(s) & 7]))
+    f32x4 aq[4];
     if constexpr (!EARLY_B) {
 #pragma unroll
       for (int s = 0; s < 6; ++s) bq[s] = V4_LOAD_B(s);
     }
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      aq[s][0] = V4_LOAD_A(0, s);
-      if (MT == 2) aq[s][1] = V4_LOAD_A(1, s);
-    }
+    for (int s = 0; s < 2; ++s) aq[s] = V4_LOAD_A(s);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int s = 0; s < 72; ++s) {
       if (s + 6 < 72) bq[(s + 6) & 7] = V4_LOAD_B(s + 6);
-      if (s + 2 < 72) {
-        aq[(s + 2) & 3][0] = V4_LOAD_A(0, s + 2);
-        if (MT == 2) aq[(s + 2) & 3][1] = V4_LOAD_A(1, s + 2);
-      }
+      if (s + 2 < 72) aq[(s + 2) & 3] = V4_LOAD_A(s + 2);
       const f32x4 bb = bq[s & 7];
-      const f32x4 a0 = aq[s & 3][0];
-      const f32x4 a1 = aq[s & 3][1];
+      const f32x4 a0 = aq[s & 3];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[e], bb[e], acc0, 0, 0, 0);
-        if (MT == 2) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[e], bb[e], acc1, 0, 0, 0);
-      }
+      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[e], bb[e], acc, 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
 #undef V4_LOAD_A
@@ -661,36 +629,37 @@ __global__ __launch_bounds__(256, KSEL == 3 ? 2 : (MT == 1 ? (GATE ? SISR_GATE_W
   const sisr_rsrc_t rmk = sisr_rsrc(MASK ? p.mask + tile_base : p.y);
   const sisr_rsrc_t rrs = sisr_rsrc(RES ? p.res + tile_base : p.y);
   const sisr_rsrc_t rdt = sisr_rsrc(DOT ? p.dot + tile_base : p.y);
-  float grow[2] = {0.f, 0.f};  // per output row: the GAP partial is (row 0) + (row 1) of a 2-row strip
-  // Epilogue operands (ReLU mask / residual / DOT map) of BOTH output rows are requested before the first store: y, mask,
+  // Epilogue operands (ReLU mask / residual / DOT map) of the output row are requested before the first store: y, mask,
   // res and dot are distinct buffers, but the compiler cannot know that, and with loads and stores interleaved it emitted
   // load -> s_waitcnt vmcnt(0) -> store per element (a full memory round trip each).  One round trip per tile remains.
-  // (With two operand sets -- DOT + residual -- the second set is fetched per row: 64 values in flight measured slower.)
+  // (With two operand sets -- DOT + residual -- the second set is fetched after the first: 64 values in flight measured slower.)
   constexpr bool TWO_SETS = DOT && RES;
-  float mk[MT][16], rs[MT][16], dt[MT][16];
-  auto fetch = [&](int m, bool first_set, bool second_set) {
-    const int row = h0 + MT * ph + m;
-    const unsigned row_off = (unsigned)(min(row, H - 1) * (int)p.yv.sH) * 4u;  // scalar, bytes
+  float mk[16], rs[16], dt[16];
+  auto fetch = [&](bool first_set, bool second_set) {
+    const unsigned row_off = (unsigned)(min(h0 + ph, H - 1) * (int)p.yv.sH) * 4u;  // scalar, bytes: the wave's row, clamped
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int cr = (r & 3) + 8 * (r >> 2);
       // partial tiles: unconditional loads from a clamped (in-image) column instead of a branch + wait per element
       const unsigned vo = full ? loff_y : (unsigned)(co + (min(w0 + cr + 4 * hh, W - 1) - w0) * (int)p.yv.sW) * 4u;
       const unsigned so = full ? row_off + (unsigned)cr * swb : row_off;
-      if (MASK && first_set) mk[m][r] = sisr_buf_load1(rmk, vo, so);
-      if (RES && first_set) rs[m][r] = sisr_buf_load1(rrs, vo, so);
-      if (DOT && (TWO_SETS ? second_set : first_set)) dt[m][r] = sisr_buf_load1(rdt, vo, so);
+      if (MASK && first_set) mk[r] = sisr_buf_load1(rmk, vo, so);
+      if (RES && first_set) rs[r] = sisr_buf_load1(rrs, vo, so);
+      if (DOT && (TWO_SETS ? second_set : first_set)) dt[r] = sisr_buf_load1(rdt, vo, so);
     }
   };
+  // (The two one-trip loops are what is left of the loops over a wave's output rows, and fetch() and the second loop each
+  // compute the row for themselves.  Both stay because the compiler orders the epilogue differently without them -- invariant
+  // arithmetic is no longer hoisted ahead of the loads -- and every form then changes, the DOT form growing by 184 B.)
 #pragma unroll
-  for (int m = 0; m < MT; ++m) fetch(m, true, false);
+  for (int m = 0; m < 1; ++m) fetch(true, false);
+  float grow = 0.f;  // this wave's output row; the GAP partial is (row 0) + (row 1) of a 2-row strip
 #pragma unroll
-  for (int m = 0; m < MT; ++m) {
+  for (int m = 0; m < 1; ++m) {
     float gsum = 0.f;
-    const int row = h0 + MT * ph + m;
-    f32x16 acc = m ? acc1 : acc0;
+    const int row = h0 + ph;
     const unsigned row_off = (unsigned)(row * (int)p.yv.sH) * 4u;  // scalar, bytes (used for in-image rows only)
-    if (TWO_SETS) fetch(m, false, true);
+    if (TWO_SETS) fetch(false, true);
     if (LEAKY && !MASK) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = acc[r] > 0.f ? acc[r] : 0.2f * acc[r];
@@ -704,45 +673,43 @@ __global__ __launch_bounds__(256, KSEL == 3 ? 2 : (MT == 1 ? (GATE ? SISR_GATE_W
     }
     if (MASK) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = mk[m][r] > 0.f ? acc[r] : (LEAKY ? 0.2f * acc[r] : 0.f);
+      for (int r = 0; r < 16; ++r) acc[r] = mk[r] > 0.f ? acc[r] : (LEAKY ? 0.2f * acc[r] : 0.f);
     }
     if (RES) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] += rs[m][r];
+      for (int r = 0; r < 16; ++r) acc[r] += rs[r];
     }
     if (full) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        SISR_Y_STORE1(acc[r], ry, loff_y, row_off + (unsigned)((r & 3) + 8 * (r >> 2)) * swb);
+        sisr_buf_store1(acc[r], ry, loff_y, row_off + (unsigned)((r & 3) + 8 * (r >> 2)) * swb);
       if (want_sum) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) gsum = DOT ? __builtin_fmaf(acc[r], dt[m][r], gsum) : gsum + acc[r];  // explicit fma: same bits in every build
+        for (int r = 0; r < 16; ++r) gsum = DOT ? __builtin_fmaf(acc[r], dt[r], gsum) : gsum + acc[r];  // explicit fma: same bits in every build
       }
     } else if (row < H) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int cr = (r & 3) + 8 * (r >> 2);
         if (w0 + cr + 4 * hh < W) {
-          SISR_Y_STORE1(acc[r], ry, loff_y, row_off + (unsigned)cr * swb);
-          gsum = DOT ? __builtin_fmaf(acc[r], dt[m][r], gsum) : gsum + acc[r];  // explicit fma: same bits in every build
+          sisr_buf_store1(acc[r], ry, loff_y, row_off + (unsigned)cr * swb);
+          gsum = DOT ? __builtin_fmaf(acc[r], dt[r], gsum) : gsum + acc[r];  // explicit fma: same bits in every build
         }
       }
     }
-    grow[m] = gsum + __shfl_xor(gsum, 32);
+    grow = gsum + __shfl_xor(gsum, 32);
   }
   if (p.gap) {
-    const long parts = (long)p.tiles_w * ((H + 3) / 4) * 2;  // one partial per (2-row strip, 32 columns)
-    if (MT == 2) {
-      if (hh == 0) p.gap[(((long)b * parts) + (th * p.tiles_w + tw) * 2 + ph) * Cout + q * 64 + co] = grow[0] + grow[1];
-    } else {  // the strip's two rows live in waves ph = 0 and ph = 1: add them through LDS in row order
-      __syncthreads();
-      if (ph == 1 && hh == 0) lds[co] = grow[0];
-      __syncthreads();
-      if (ph == 0 && hh == 0) {
-        float* g = p.gap + (((long)b * parts) + ((th >> 1) * p.tiles_w + tw) * 2 + (th & 1)) * Cout + q * 64 + co;
-        g[0] = grow[0] + lds[co];
-        if ((th & 1) == 0 && th + 1 >= p.tiles_h) g[Cout] = 0.f;  // H % 4 in {1, 2}: the tile's second strip is empty
-      }
+    // one partial per (2-row strip, 32 columns), two strips per 4 x 32 tile.  The strip's two rows live in waves ph = 0 and
+    // ph = 1: add them through LDS in row order
+    const long parts = (long)p.tiles_w * ((H + 3) / 4) * 2;
+    __syncthreads();
+    if (ph == 1 && hh == 0) lds[co] = grow;
+    __syncthreads();
+    if (ph == 0 && hh == 0) {
+      float* g = p.gap + (((long)b * parts) + ((th >> 1) * p.tiles_w + tw) * 2 + (th & 1)) * Cout + q * 64 + co;
+      g[0] = grow + lds[co];
+      if ((th & 1) == 0 && th + 1 >= p.tiles_h) g[Cout] = 0.f;  // H % 4 in {1, 2}: the tile's second strip is empty
     }
   }
 #ifdef SISR_DIAG
@@ -868,7 +835,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_p4_kernel(ConvParams p, in
           if (GATE) {
             t = sisr_mul_add4(t, s4, u[r][k]);
             if (rown && cok && col >= 1 && col <= TW)
-              SISR_Y_STORE4(t, ro_, (unsigned)(min(max(gw, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u, ro);
+              sisr_buf_store4(t, ro_, (unsigned)(min(max(gw, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u, ro);
           }
           if (!interior) t = sisr_keep_if(t, rok && cok);
           *reinterpret_cast<f32x4*>(lds + r * (HALO_W * 64) + col * 64 + ((c4 ^ (col & 15)) << 2)) = t;
@@ -983,7 +950,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_p4_kernel(ConvParams p, in
         if (full) {
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            SISR_Y_STORE1(acc[r], ry, loff_y, row_off + (unsigned)((r & 3) + 8 * (r >> 2)) * swb);
+            sisr_buf_store1(acc[r], ry, loff_y, row_off + (unsigned)((r & 3) + 8 * (r >> 2)) * swb);
           if (want_sum) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) gsum = DOT ? __builtin_fmaf(acc[r], dt[m][r], gsum) : gsum + acc[r];
@@ -993,7 +960,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_p4_kernel(ConvParams p, in
           for (int r = 0; r < 16; ++r) {
             const int cr = (r & 3) + 8 * (r >> 2);
             if (w0 + cr + 4 * hh < W) {
-              SISR_Y_STORE1(acc[r], ry, loff_y, row_off + (unsigned)cr * swb);
+              sisr_buf_store1(acc[r], ry, loff_y, row_off + (unsigned)cr * swb);
               gsum = DOT ? __builtin_fmaf(acc[r], dt[m][r], gsum) : gsum + acc[r];
             }
           }
@@ -1112,7 +1079,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
           if (GATE) {
             t = sisr_mul_add4(t, s4, u[r][k]);
             if (rown && cok && col >= 1 && col <= TW)
-              SISR_Y_STORE4(t, ro_, (unsigned)(min(max(gw, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u, ro);
+              sisr_buf_store4(t, ro_, (unsigned)(min(max(gw, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u, ro);
           }
           if (!interior) t = sisr_keep_if(t, rok && cok);
           *reinterpret_cast<f32x4*>(lds + r * (HALO_W * 64) + col * 64 + ((c4 ^ (col & 15)) << 2)) = t;
@@ -1257,7 +1224,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
               if (RES) a += rs[i][j][r];
               const int row = h0 + 2 * mb + i, col = w0 + 8 * q + 2 * r + j;
               if (row < H && col < W) {
-                SISR_Y_STORE1(a, ry, (unsigned)(col * (int)p.yv.sW + co) * 4u, (unsigned)(row * (int)p.yv.sH) * 4u);
+                sisr_buf_store1(a, ry, (unsigned)(col * (int)p.yv.sW + co) * 4u, (unsigned)(row * (int)p.yv.sH) * 4u);
                 gs = DOT ? __builtin_fmaf(a, dt[i][j][r], gs) : gs + a;
               }
             }
@@ -1592,9 +1559,9 @@ __device__ __forceinline__ void sisr_store_split3(unsigned char* dst, f32x4 a, f
   *reinterpret_cast<u32x4*>(dst + 2 * X3_PLANE) = lo & mk;
 }
 
-// BD = B-fragment prefetch distance in K-steps (ring of BD + 1 slots); the A fragments of step s + 1 are requested before
+// The B fragments are requested four K-steps ahead (ring of five slots); the A fragments of step s + 1 are requested before
 // the MFMAs of step s (double buffer).
-template <bool AFFINE, bool MASK, bool RES, bool GATE = false, bool DOT = false, int BD = 4, bool STAMP = false>
+template <bool AFFINE, bool MASK, bool RES, bool GATE = false, bool DOT = false, bool STAMP = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_c64_x3_kernel(ConvParams p, long wplane) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
   // Wave priority: the two resident workgroups take turns in the K loop (the older wave's MFMA stream wins the SIMD's
@@ -1744,7 +1711,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_x3_kernel(ConvParams p, lo
 #define BF_LOAD_B(s, pl) sisr_buf_load_bf16x8(rwq, boff, (unsigned)((pl) * (unsigned)wplane + (s) * 2048))
 #define BF_LOAD_A(m, s, pl) \
   (*reinterpret_cast<const bf16x8*>(ldsb + (pl) * X3_PLANE + ((((s) >> 2) / 3 + (m)) * (HALO_W * BH_PIX)) + aoff[((s) >> 2) % 3][(s) & 3]))
-    constexpr int RING = BD + 1;
+    constexpr int BD = 4, RING = BD + 1;  // B prefetch distance in K-steps, ring slots
     bf16x8 bq[RING][3];
     bf16x8 aq[2][2][3];  // [step parity][M-tile][plane]
 #pragma unroll
@@ -2621,17 +2588,10 @@ extern "C" int sisr_pack_conv3x3_many(const void* jobs_device, int n_jobs, int t
   return sisr_check_launch();
 }
 
-// Kernel selection (process-wide, read-only during launches): 4 = issue-lean kernel (2-row tiles on small grids,
-// 4-row tiles otherwise) with the general kernel as fallback (default); 5 / 6 = the same with the 4-row / 2-row
-// tile forced; 2 = general kernel only; 13 / 16 = diagnostic builds of the general kernel (see above).
-// 4-row-tile workgroups below which the 2-row kernel is used.  Round 2 (weights fetched with 64-bit lane addresses: the
-// 2-row tile's twice-as-many weight loads per MFMA cost matrix-pipe time): 1.6x faster at 128 workgroups, a tie or worse from
-// 256 up, so 200.  With buffer-addressed weight loads (free beside the MFMAs) the 2-row tile wins at every size measured
-// (64 -> 64, 128 x 128 maps: 8 samples 85 vs 101 us, 16: 158 vs 170, 32: 296 vs 307): four resident workgroups per CU
-// instead of three and a finer last round.  SISR_CONV_TILE_ROWS=4 (read per call, no state kept) restores the old rule.
-#define SMALL_GRID_BLOCKS (sisr_small_grid_blocks())
-// the persistent form (conv3x3_c64_p4_kernel) is used from two tiles per workgroup on (select 7 forces it, 5 / 6 the
-// per-tile kernels; SISR_CONV_PERSISTENT=0 switches it off per call, for A/B measurements)
+// Kernel selection (per call; the library keeps no state).  Launches are sized in 4 x 32 tiles (nblk): the persistent and
+// Winograd kernels walk those, and the per-tile kernel (conv3x3_c64_v4_kernel) splits each into two V4_TH-row tiles.
+// The persistent form (conv3x3_c64_p4_kernel) is used from two tiles per workgroup on (select 7 forces it, 6 the
+// per-tile kernel; SISR_CONV_PERSISTENT=0 switches it off per call, for A/B measurements)
 static inline bool sisr_use_persistent(int variant, long nblk) {
   if (variant == 7) return true;
   if (variant != 4) return false;
@@ -2651,12 +2611,10 @@ static inline bool sisr_use_winograd(bool avail, bool force, long pixels) {
   if (e && e[0] == '0') return false;
   return pixels > SISR_WINO_MIN_PIXELS;
 }
-static inline long sisr_small_grid_blocks() {
-  const char* e = getenv("SISR_CONV_TILE_ROWS");
-  if (e && e[0] == '4') return 200;
-  if (e && e[0] == '2') return 0x7fffffffL;
-  if (const char* n = getenv("SISR_CONV_SMALL_BLOCKS")) return atol(n);
-  return 0x7fffffffL;
+// Grid of the per-tile kernel: p.tiles_h is recounted in V4_TH-row tiles.
+static inline dim3 sisr_v4_grid(ConvParams& p) {
+  p.tiles_h = (p.H + V4_TH - 1) / V4_TH;
+  return dim3((unsigned)((long)p.tiles_w * p.tiles_h * p.B), p.cout_chunks);
 }
 // Host-side description of a gate head (include/sisr_hip.h: sisr_ca_tail; head must be nonzero, `s`, dw1..db2 and
 // `counter` are unused).
@@ -2705,19 +2663,17 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
                           !head->s_out || !head->hid_out || !head->ca_out || !head->g_out))
       return SISR_ERR_ARG;
   }
-  // select (per call; the library keeps no state): 0 / 4 = issue-lean kernel, tile height by grid size, general kernel
-  // as fallback; 5 / 6 = the same with the 4-row / 2-row tile forced (A/B measurements, bit-identical results);
-  // 2 = general kernel only.  Diagnostic builds (-DSISR_DIAG) add 13 / 16.
+  // select (per call; the library keeps no state): 0 / 4 = issue-lean kernel (per-tile below the persistent threshold,
+  // persistent from it up), general kernel as fallback; 6 / 7 = the same with the per-tile / persistent form forced (A/B
+  // measurements, bit-identical results); 2 = general kernel only.  Diagnostic builds (-DSISR_DIAG) add 13 / 16.
   // 8 / 9 / 10 = structurally sparse weights (SFTMD's merged convs; KSEL 1 / 2 / 3 of conv3x3_c64_v4_kernel): the caller
   // asserts that the skipped blocks of the packed weight are zero
   const int ksel = (select >= 8 && select <= 10) ? select - 7 : 0;
   const int variant = (select == 0 || ksel) ? 4 : select;
 #ifdef SISR_DIAG
-  if (variant != 4 && variant != 5 && variant != 6 && variant != 7 && variant != 2 && variant != 13 &&
-      variant != 16)
-    return SISR_ERR_ARG;
+  if (variant != 4 && variant != 6 && variant != 7 && variant != 2 && variant != 13 && variant != 16) return SISR_ERR_ARG;
 #else
-  if (variant != 4 && variant != 5 && variant != 6 && variant != 7 && variant != 2) return SISR_ERR_ARG;
+  if (variant != 4 && variant != 6 && variant != 7 && variant != 2) return SISR_ERR_ARG;
 #endif
   if (ksel) {
     const bool shape_ok = ksel == 1 ? (cin == 64 && cout == 128) : (cin == 128 && cout == 64);
@@ -2814,58 +2770,39 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
 #undef P4X
       return sisr_check_launch();
     }
-    const bool small = variant == 6 || (variant != 5 && nblk < SMALL_GRID_BLOCKS);
-    dim3 g = grid;
-    size_t lb = HALO_H * HALO_W * 64 * sizeof(float);
-    if (small) {
-      p.tiles_h = (H + 1) / 2;
-      g = dim3((unsigned)((long)p.tiles_w * p.tiles_h * B), 1);
-      lb = 4 * HALO_W * 64 * sizeof(float);
-    }
-#define V4X(RS, MTV, GT, DT) hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, RS, MTV, GT, DT>), g, dim3(256), lb, st, p)
     if (head && (!gate || head->backward)) return SISR_ERR_ARG;
-#define V4H(RS, MTV) hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, RS, MTV, true, false, false, 0, 1>), g, dim3(256), lb + SISR_HEAD_LDS, st, p)
+    const dim3 g = sisr_v4_grid(p);
+    const size_t lb = V4_HALO_BYTES;
+#define V4X(RS, GT, DT) hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, RS, GT, DT>), g, dim3(256), lb, st, p)
+#define V4H(RS) hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, RS, true, false, false, 0, 1>), g, dim3(256), lb + SISR_HEAD_LDS, st, p)
     if (gate && head) {
-      if (small) { if (rs) V4H(true, 1); else V4H(false, 1); }
-      else       { if (rs) V4H(true, 2); else V4H(false, 2); }
+      if (rs) V4H(true); else V4H(false);
     } else if (gate) {
-      if (small) { if (rs) V4X(true, 1, true, false); else V4X(false, 1, true, false); }
-      else       { if (rs) V4X(true, 2, true, false); else V4X(false, 2, true, false); }
+      if (rs) V4X(true, true, false); else V4X(false, true, false);
     } else {
-      if (small) { if (rs) V4X(true, 1, false, true); else V4X(false, 1, false, true); }
-      else       { if (rs) V4X(true, 2, false, true); else V4X(false, 2, false, true); }
+      if (rs) V4X(true, false, true); else V4X(false, false, true);
     }
 #undef V4X
 #undef V4H
     return sisr_check_launch();
   }
-  if (variant == 4 || variant == 5 || variant == 6 || variant == 7) {
+  if (variant == 4 || variant == 6 || variant == 7) {
     const bool aff = in_scale != nullptr, msk = mask != nullptr, rs = res != nullptr;
     hipStream_t st = (hipStream_t)stream;
     if (ksel) {
       // 1: plain (bias only); 2: LeakyReLU epilogue; 3: LeakyReLU' mask -- the forms SFTMD needs
       const bool form_ok = ksel == 1 ? (!msk && p.relu == 0) : (ksel == 2 ? (!msk && p.relu == 2) : (msk && p.mask_leaky && p.relu == 0 && !p.bias));
       if (!form_ok) return SISR_ERR_UNSUPPORTED;
-      if (ksel == 3) {  // always the 2-row tile, both input chunks resident in LDS
-        p.tiles_h = (H + 1) / 2;
-        const dim3 g3((unsigned)((long)p.tiles_w * p.tiles_h * B), 1);
-        const size_t lb3 = 2 * 4 * HALO_W * 64 * sizeof(float);
-        SISR_ALLOW_LDS((conv3x3_c64_v4_kernel<false, true, false, 1, false, false, true, 3>), lb3);
-        hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, true, false, 1, false, false, true, 3>), g3, dim3(256), lb3, st, p);
+      const dim3 g = sisr_v4_grid(p);
+      if (ksel == 3) {  // both input chunks resident in LDS
+        const size_t lb3 = 2 * V4_HALO_BYTES;
+        SISR_ALLOW_LDS((conv3x3_c64_v4_kernel<false, true, false, false, false, true, 3>), lb3);
+        hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, true, false, false, false, true, 3>), g, dim3(256), lb3, st, p);
         return sisr_check_launch();
       }
-      const bool small = nblk * p.cout_chunks < SMALL_GRID_BLOCKS;
-      dim3 g = grid;
-      size_t lb = HALO_H * HALO_W * 64 * sizeof(float);
-      if (small) {
-        p.tiles_h = (H + 1) / 2;
-        g = dim3((unsigned)((long)p.tiles_w * p.tiles_h * B), p.cout_chunks);
-        lb = 4 * HALO_W * 64 * sizeof(float);
-      }
-#define V4K(MK, MTV, LK, KS) hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, MK, false, MTV, false, false, LK, KS>), g, dim3(256), lb, st, p)
-      if (ksel == 1) { if (small) V4K(false, 1, false, 1); else V4K(false, 2, false, 1); }
-      else { if (small) V4K(false, 1, true, 2); else V4K(false, 2, true, 2); }
-#undef V4K
+      const size_t lb = V4_HALO_BYTES;
+      if (ksel == 1) hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, false, false, false, false, 1>), g, dim3(256), lb, st, p);
+      else hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, false, false, false, true, 2>), g, dim3(256), lb, st, p);
       return sisr_check_launch();
     }
     if (!(in_shift && !in_scale) && !(aff && !msk) && !(msk && rs) && !leaky && !head && cin == 64 && cout == 64 &&
@@ -2897,44 +2834,18 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
       return sisr_check_launch();
     }
     if (!(in_shift && !in_scale) && !(aff && !msk) && !(msk && rs)) {
-      // Grids with fewer 4-row workgroups than CUs (a single 128x128 sample) leave half the chip idle: halve the tile.  Variant 5 / 6 force
-      // the 4-row / 2-row kernel (A/B measurements); results are bit-identical either way.
-      const bool small = variant == 6 || (variant == 4 && nblk * p.cout_chunks < SMALL_GRID_BLOCKS);
-      if (small) {
-        p.tiles_h = (H + 1) / 2;
-        const dim3 grid2((unsigned)((long)p.tiles_w * p.tiles_h * B), p.cout_chunks);
-        const size_t lb2 = 4 * HALO_W * 64 * sizeof(float);
-        if (leaky && msk)
-          hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, true, false, 1, false, false, true>), grid2, dim3(256), lb2, st, p);
-        else if (leaky)
-          hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, false, 1, false, false, true>), grid2, dim3(256), lb2, st, p);
-        else if (aff && head)
-          hipLaunchKernelGGL((conv3x3_c64_v4_kernel<true, true, false, 1, false, false, false, 0, 2>), grid2, dim3(256), lb2 + SISR_HEAD_LDS, st, p);
-        else if (aff)
-          hipLaunchKernelGGL((conv3x3_c64_v4_kernel<true, true, false, 1>), grid2, dim3(256), lb2, st, p);
-        else if (msk)
-          hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, true, false, 1>), grid2, dim3(256), lb2, st, p);
-        else if (rs)
-          hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, true, 1>), grid2, dim3(256), lb2, st, p);
-        else
-          hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, false, 1>), grid2, dim3(256), lb2, st, p);
-        return sisr_check_launch();
-      }
-      const size_t lb = HALO_H * HALO_W * 64 * sizeof(float);
-      if (leaky && msk)
-        hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, true, false, 2, false, false, true>), grid, dim3(256), lb, st, p);
-      else if (leaky)
-        hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, false, 2, false, false, true>), grid, dim3(256), lb, st, p);
+      const dim3 g = sisr_v4_grid(p);
+      const size_t lb = V4_HALO_BYTES;
+#define V4P(...) hipLaunchKernelGGL((conv3x3_c64_v4_kernel<__VA_ARGS__>), g, dim3(256), lb, st, p)
+      if (leaky && msk) V4P(false, true, false, false, false, true);
+      else if (leaky) V4P(false, false, false, false, false, true);
       else if (aff && head)
-        hipLaunchKernelGGL((conv3x3_c64_v4_kernel<true, true, false, 2, false, false, false, 0, 2>), grid, dim3(256), lb + SISR_HEAD_LDS, st, p);
-      else if (aff)
-        hipLaunchKernelGGL((conv3x3_c64_v4_kernel<true, true, false, 2>), grid, dim3(256), lb, st, p);
-      else if (msk)
-        hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, true, false, 2>), grid, dim3(256), lb, st, p);
-      else if (rs)
-        hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, true, 2>), grid, dim3(256), lb, st, p);
-      else
-        hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, false, 2>), grid, dim3(256), lb, st, p);
+        hipLaunchKernelGGL((conv3x3_c64_v4_kernel<true, true, false, false, false, false, 0, 2>), g, dim3(256), lb + SISR_HEAD_LDS, st, p);
+      else if (aff) V4P(true, true, false);
+      else if (msk) V4P(false, true, false);
+      else if (rs) V4P(false, false, true);
+      else V4P(false, false, false);
+#undef V4P
       return sisr_check_launch();
     }
     if (head) return SISR_ERR_UNSUPPORTED;  // the general kernel has no heads
@@ -3010,32 +2921,24 @@ extern "C" int sisr_conv3x3_c64_geo(const float* x, const int64_t* xview, const 
   const long nblk = (long)p.tiles_w * p.tiles_h * B;
   if (nblk > 0x7fffffffL) return SISR_ERR_ARG;
   const int ksel = (cin == 64 && kreal > 0 && kreal <= 8) ? 5 : ((cin == 64 && kreal > 0 && kreal <= 32) ? 4 : 0);
-  const bool small = nblk * p.cout_chunks < SMALL_GRID_BLOCKS;
-  dim3 g((unsigned)nblk, p.cout_chunks);
-  size_t lb = HALO_H * HALO_W * 64 * sizeof(float);
-  if (small) {
-    p.tiles_h = (H + 1) / 2;
-    g = dim3((unsigned)((long)p.tiles_w * p.tiles_h * B), p.cout_chunks);
-    lb = 4 * HALO_W * 64 * sizeof(float);
-  }
+  const dim3 g = sisr_v4_grid(p);
   hipStream_t st = (hipStream_t)stream;
-  if (mode == 3) {  // 2-row tiles, 5 x 66-pixel halo
-    p.tiles_h = (H + 1) / 2;
-    g = dim3((unsigned)((long)p.tiles_w * p.tiles_h * B), p.cout_chunks);
-    lb = 5 * 66 * 64 * sizeof(float);
+  if (mode == 3) {  // 5 x 66-pixel halo
+    const size_t lb = 5 * 66 * 64 * sizeof(float);
     if (ksel == 4) {
-      SISR_ALLOW_LDS((conv3x3_c64_v4_kernel<false, false, false, 1, false, false, false, 4, 0, true, true>), lb);
-      hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, false, 1, false, false, false, 4, 0, true, true>), g, dim3(256), lb, st, p);
+      SISR_ALLOW_LDS((conv3x3_c64_v4_kernel<false, false, false, false, false, false, 4, 0, true, true>), lb);
+      hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, false, false, false, false, 4, 0, true, true>), g, dim3(256), lb, st, p);
     } else {
-      SISR_ALLOW_LDS((conv3x3_c64_v4_kernel<false, false, false, 1, false, false, false, 0, 0, true, true>), lb);
-      hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, false, 1, false, false, false, 0, 0, true, true>), g, dim3(256), lb, st, p);
+      SISR_ALLOW_LDS((conv3x3_c64_v4_kernel<false, false, false, false, false, false, 0, 0, true, true>), lb);
+      hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, false, false, false, false, 0, 0, true, true>), g, dim3(256), lb, st, p);
     }
     return sisr_check_launch();
   }
-#define V4G(MTV, KS) hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, false, MTV, false, false, false, KS, 0, true>), g, dim3(256), lb, st, p)
-  if (ksel == 5) { if (small) V4G(1, 5); else V4G(2, 5); }
-  else if (ksel == 4) { if (small) V4G(1, 4); else V4G(2, 4); }
-  else { if (small) V4G(1, 0); else V4G(2, 0); }
+  const size_t lb = V4_HALO_BYTES;
+#define V4G(KS) hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, false, false, false, false, KS, 0, true>), g, dim3(256), lb, st, p)
+  if (ksel == 5) V4G(5);
+  else if (ksel == 4) V4G(4);
+  else V4G(0);
 #undef V4G
   return sisr_check_launch();
 }
@@ -3328,14 +3231,8 @@ extern "C" int sisr_conv3x3_c64_x3(const float* x, const int64_t* xview, const v
   } while (0)
 #ifdef SISR_DIAG
   if (getenv("SISR_X3_STAMP") && dot && !gate && !in_scale && !mask && !res) {  // tools/x3_phases.py
-    SISR_ALLOW_LDS((conv3x3_c64_x3_kernel<false, false, false, false, false, 4, true>), lb);
-    hipLaunchKernelGGL((conv3x3_c64_x3_kernel<false, false, false, false, false, 4, true>), grid, dim3(256), lb, st, p, wplane);
-    return sisr_check_launch();
-  }
-  static const int x3_bd = getenv("SISR_X3_BD") ? atoi(getenv("SISR_X3_BD")) : 4;  // diagnostic A/B of the plain form
-  if (x3_bd == 6 && !gate && !dot && !in_scale && !mask && !res) {
-    SISR_ALLOW_LDS((conv3x3_c64_x3_kernel<false, false, false, false, false, 6>), lb);
-    hipLaunchKernelGGL((conv3x3_c64_x3_kernel<false, false, false, false, false, 6>), grid, dim3(256), lb, st, p, wplane);
+    SISR_ALLOW_LDS((conv3x3_c64_x3_kernel<false, false, false, false, false, true>), lb);
+    hipLaunchKernelGGL((conv3x3_c64_x3_kernel<false, false, false, false, false, true>), grid, dim3(256), lb, st, p, wplane);
     return sisr_check_launch();
   }
 #endif
@@ -3379,8 +3276,7 @@ extern "C" int sisr_diag_conv_occupancy(int which) {
     SISR_ALLOW_LDS((conv3x3_c64_x3_kernel<false, false, false, false, false>), lb);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv3x3_c64_x3_kernel<false, false, false, false, false>, 256, lb) != hipSuccess) return -2;
   } else {
-    const size_t lb = HALO_H * HALO_W * 64 * sizeof(float);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv3x3_c64_v4_kernel<false, false, false, 2>, 256, lb) != hipSuccess) return -2;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv3x3_c64_v4_kernel<false, false, false>, 256, V4_HALO_BYTES) != hipSuccess) return -2;
   }
   return n;
 }

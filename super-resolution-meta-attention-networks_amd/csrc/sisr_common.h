@@ -64,14 +64,8 @@ __device__ __forceinline__ void sisr_buf_store4(f32x4 v, sisr_rsrc_t r, unsigned
 __device__ __forceinline__ void sisr_buf_store1(float v, sisr_rsrc_t r, unsigned voff_bytes, unsigned soff_bytes) {
   __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)voff_bytes, (int)soff_bytes, 0);
 }
-// write-through forms (cache policy sc1): the bytes leave the XCD's L2 as they are written instead of in the write-back burst
-// at the end of the kernel (MI355X guide, "boundary": + B / 6 TB/s behind B dirty bytes)
-__device__ __forceinline__ void sisr_buf_store1_wt(float v, sisr_rsrc_t r, unsigned voff_bytes, unsigned soff_bytes) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)voff_bytes, (int)soff_bytes, 16);
-}
-__device__ __forceinline__ void sisr_buf_store4_wt(f32x4 v, sisr_rsrc_t r, unsigned voff_bytes, unsigned soff_bytes) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)voff_bytes, (int)soff_bytes, 16);
-}
+// (Write-through stores -- cache policy sc1, so that the bytes leave the XCD's L2 as they are written instead of in the
+// write-back burst at the end of the kernel -- were measured for the conv output tiles and not kept: DESIGN.md.)
 
 #define SISR_OK 0
 #define SISR_ERR_ARG (-1)

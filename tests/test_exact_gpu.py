@@ -205,8 +205,8 @@ def check_conv_case(name, D, packs, select, winograd=False, out_cast=None):
 
 
 SMALL = [(1, 13, 9), (2, 6, 33), (2, 5, 1), (1, 3, 2), (1, 57, 86), (3, 9, 64)]  # ragged off 4 x 32 and 2 x 32, 1 / 2 wide
-# select: 0 default (plain packing), 2 general kernel, 5 / 6 4-row / 2-row tile, 7 persistent, 11 / 12 Winograd auto / forced
-SELECTS = [0, 2, 5, 6, 7, 11, 12]
+# select: 0 default (plain packing), 2 general kernel, 6 per-tile kernel, 7 persistent, 11 / 12 Winograd auto / forced
+SELECTS = [0, 2, 6, 7, 11, 12]
 
 
 @pytest.mark.parametrize("B,H,W", SMALL)
@@ -254,6 +254,7 @@ def test_fp32_conv_refused_combinations():
         "relu code 3": dict(relu=3),
         "select 1": dict(select=1),
         "select 3": dict(select=3),
+        "select 5": dict(select=5),
         "select 13 (diagnostic builds only)": dict(select=13),
         "sparse select with residual": dict(select=ops.SPARSE_BLOCK_DIAGONAL, res=dv["res"]),
     }
@@ -273,7 +274,7 @@ def test_fp32_conv_refused_combinations():
                          32, 128, 64, select=sel)
 
 
-@pytest.mark.parametrize("select", [0, 2, 5, 6])
+@pytest.mark.parametrize("select", [0, 2, 6])
 def test_fp32_conv_multichunk_channels(select):
     """128 -> 192 (two input chunks, three output chunks), forward with bias / ReLU / partial sums and residual / alpha, and
     the 192 -> 128 input-gradient packing with a ReLU' mask."""
@@ -306,7 +307,7 @@ def test_fp32_conv_reads_and_writes_stay_inside_the_views():
     ybuf = torch.full((B, 128, H, W), 1234.5, device=DEV).contiguous(memory_format=CL)
     v128 = hip.view_plain(H, W, 128)
     conv_budget(D.x, D.w, extras=(D.b, D.res))
-    for select in (0, 2, 5, 6):
+    for select in (0, 2, 6):
         ybuf[:, 64:] = NAN
         ops.conv_c64(stack[:, 1], hip.view_maps(H, W, 2), pf, D.dev["b"], (1, 64), ybuf[:, 64:], v128, B, H, W, 64, 64,
                      res=rbuf[:, 64:], select=select)

@@ -68,13 +68,13 @@ def test_conv64_fwd_bwd(B, H, W):
 
 
 @pytest.mark.parametrize("B,H,W", [(2, 16, 16), (1, 13, 9), (1, 57, 86), (2, 4, 32), (1, 5, 33), (1, 128, 128), (9, 128, 128)])
-def test_conv_tile_heights_are_bit_identical(B, H, W):
-    """The fp32 conv's kernel forms -- 4-row tiles (variant 5), 2-row tiles (6), and the persistent two-workgroups-per-CU form
-    that prefetches its next tile (7; the automatic choice from two tiles per workgroup on) -- must give the same bits for
-    outputs and GAP partials, for every epilogue they serve (the 9 x 128 x 128 case walks 2 - 3 tiles per persistent
-    workgroup, ragged last round included)."""
+def test_conv_kernel_forms_are_bit_identical(B, H, W):
+    """The fp32 conv's kernel forms -- the per-tile kernel on 2-row tiles (select 6), the persistent two-workgroups-per-CU form
+    that walks 4-row tiles and prefetches its next one (7), and the automatic choice between them (0: persistent from two
+    tiles per workgroup on) -- must give the same bits for outputs and GAP partials, for every epilogue they serve (the
+    9 x 128 x 128 case walks 2 - 3 tiles per persistent workgroup, ragged last round included)."""
     if ops.PRECISION != "fp32":
-        pytest.skip("tile-height selection is an argument of the fp32 kernel family only")
+        pytest.skip("kernel-form selection is an argument of the fp32 kernel family only")
     hip = sisr_amd.hip
     cl = torch.channels_last
     x = rnd(B, 64, H, W, seed=50).to(DEV).contiguous(memory_format=cl)
@@ -88,7 +88,7 @@ def test_conv_tile_heights_are_bit_identical(B, H, W):
     cases = [dict(bias=b, relu=True, gap=True), dict(res=res, alpha=0.3), dict(mask=mask),
              dict(mask=mask, in_scale=sc, in_shift=sh)]
     outs = {}
-    for variant in (5, 6, 7):  # per-call kernel selection (the library keeps no state)
+    for variant in (6, 7, 0):  # per-call kernel selection (the library keeps no state)
         for i, kw in enumerate(cases):
             kw = dict(kw)
             y = torch.zeros(B, 64, H, W, device=DEV).contiguous(memory_format=cl)
@@ -96,20 +96,20 @@ def test_conv_tile_heights_are_bit_identical(B, H, W):
             ops.conv_c64(x, v, pk, kw.pop("bias", None), (1, 64), y, v, B, H, W, 64, 64, gap=gap, select=variant, **kw)
             outs[(variant, i)] = (y, gap)
     for i in range(len(cases)):
-        y5, g5 = outs[(5, i)]
-        for other in (6, 7):
-            y6, g6 = outs[(other, i)]
-            assert torch.equal(y5, y6), f"case {i}: outputs differ between kernel forms 5 and {other}"
-            if g5 is not None:
-                assert torch.equal(g5, g6), f"case {i}: GAP partials differ between kernel forms 5 and {other}"
+        y6, g6 = outs[(6, i)]
+        for other in (7, 0):
+            yo, go = outs[(other, i)]
+            assert torch.equal(y6, yo), f"case {i}: outputs differ between kernel forms 6 and {other}"
+            if g6 is not None:
+                assert torch.equal(g6, go), f"case {i}: GAP partials differ between kernel forms 6 and {other}"
     want = F.relu(F.conv2d(x.cpu(), w.cpu(), b.cpu(), padding=1))
-    close(outs[(5, 0)][0], want, 2e-5, 2e-6, "4-row tile vs ATen")
+    close(outs[(6, 0)][0], want, 2e-5, 2e-6, "per-tile kernel vs ATen")
 
 
 @pytest.mark.parametrize("B,H,W", [(1, 13, 9), (2, 16, 40), (1, 57, 86), (1, 128, 128), (10, 128, 128)])
 def test_conv_gate_prologue_and_dot_epilogue(B, H, W):
     """The neighbour-fusion hooks of the 64->64 conv: GATE (input = t*g + skip, also written out) and DOT (GAP
-    slots hold sum(v * dot)), on both tile heights (B = 10 at 128x128 uses the 4-row tile)."""
+    slots hold sum(v * dot)), on the per-tile and the persistent kernel (B = 10 at 128x128 has enough tiles for the latter)."""
     hip = sisr_amd.hip
     cl = torch.channels_last
     dev4 = lambda t: t.to(DEV).contiguous(memory_format=cl)  # noqa: E731
@@ -178,8 +178,7 @@ def test_fused_group_node_matches_per_block_nodes(meta):
 def test_gate_heads_are_bit_identical_to_the_gate_launches(meta, shape):
     """Small launches: the channel-attention gate and its backward are computed by the conv that CONSUMES them (gate heads,
     ops.GATE_HEADS; every workgroup for its own sample) and the gates' parameter gradients by one launch per group -- against
-    the stand-alone gate launches: same device functions (ca_gate.h), same summation order -> equal to the bit.  Both tile
-    heights (the second shape has enough tiles for the 4-row kernel)."""
+    the stand-alone gate launches: same device functions (ca_gate.h), same summation order -> equal to the bit."""
     torch.manual_seed(8)
     if meta:
         net = A.QRCAN(n_resblocks=3, n_resgroups=2, n_feats=64, scale=2, style="standard", num_metadata=10,

@@ -92,7 +92,7 @@ def test_sft_layer_matches_the_four_conv_formulation(relu, M):
 def test_sparse_select_codes_equal_the_dense_kernel(shape):
     """`select` 8 / 9 skip structural zeros of the merged SFT weights: the remaining products are accumulated in the dense
     kernel's order, so the outputs are bit-identical; the masked weight gradient (other K-slice split) agrees to rounding.
-    Both tile heights (small and large grids)."""
+    Small and large grids."""
     B, H, W = shape
     g = torch.Generator().manual_seed(11)
     cl = torch.channels_last

@@ -36,7 +36,7 @@ b = torch.randn(64, device=dev)
 sc, sh = torch.rand(B, 64, device=dev), torch.rand(B, 64, device=dev)
 pk = ops.pack_weight(w, "fwd")
 v = hip.view_plain(H, W, 64)
-rows = 4 if (os.environ.get("SISR_CONV_TILE_ROWS", "") == "4" or form == "x3") else 2  # the library's tile-height rule for this grid
+rows = 4 if form == "x3" else 2  # tile height of the kernel that is stamped
 nwg = B * (H // rows) * (W // 32)
 stamp = torch.zeros(nwg * 4 * 8, dtype=torch.int32, device=dev)
 gap = torch.empty(B, ops.gap_parts(H, W), 64, device=dev)

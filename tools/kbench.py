@@ -41,7 +41,7 @@ def main():
     ap.add_argument("--hw", type=int, default=128)
     ap.add_argument("--warm", type=int, default=3, help="untimed launches before each timed loop (clocks settle over tens of ms)")
     ap.add_argument("--only", default="")
-    ap.add_argument("--variants", default="4,2", help="conv kernel selections to time: 4 auto, 5 / 6 forced 4-row / 2-row tile, 2 general")
+    ap.add_argument("--variants", default="4,2", help="conv kernel selections to time: 4 auto, 6 / 7 per-tile / persistent form forced, 2 general")
     ap.add_argument("--rounds", type=int, default=0, help="interleaved A/B rounds over --variants (conv only)")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "bf16x3"])
     a = ap.parse_args()
