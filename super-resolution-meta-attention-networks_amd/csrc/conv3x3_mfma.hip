@@ -987,36 +987,37 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_p4_kernel(ConvParams p, in
 // direct weights by pack_conv3x3_many_kernel, layout [xi 16][G 4][q 4][co 64][e 4] for ci = 16 G + 4 q + e), and the
 // output 2 x 2 block is A^T M A.  4/9 of the direct form's MFMAs; multiplies stay exact fp32, the transforms add a few
 // fp32 roundings (only 0, +-1 and 1/2 coefficients).
-//   wave w: output channels [16w, 16w + 16) of all 32 Winograd tiles, v_mfma_f32_16x16x4_f32 with two M-blocks (tile
-//           rows) sharing each B fragment: lane (n = l & 15, q = l >> 4) accumulates tiles (mb, 4q + reg) x channel 16w + n,
+//   wave (mb = w >> 1, coh = w & 1): Winograd tile row mb x output channels [32 coh, 32 coh + 32) as two 16-wide N blocks nb,
+//           v_mfma_f32_16x16x4_f32: lane (n = l & 15, q = l >> 4) accumulates tiles (mb, 4q + reg) x channel 32 coh + 16 nb + n,
 //           the same (tile, co) for every xi, so the output transform stays in registers (folded once per xr row)
-//   V chunk: per (xr, ci half) the workgroup transforms the halo ONCE into LDS, [xc 4][tile 32][32 ci] (16 KB, 16-B piece
-//           k of tile t at slot k ^ ((t >> 1) & 7): conflict-free ds_read_b128 of the A fragments), 64 MFMAs per wave
-//           between barriers
+//   A fragments: built by the wave itself, straight from the halo.  Lane (n, q) IS the A-operand slot (tile (mb, n), ci piece
+//           4G + q): per step (xr, G) it reads its 4 x 2 halo pieces (rows 2mb + {ra, rb}, columns 2n .. 2n + 3; the halo's
+//           col & 15 key keeps every ds_read_b128 lane group on 16 distinct 16-B bank groups), forms B^T d B in registers (32
+//           adds) and feeds 32 MFMAs (4 xc x 2 nb x 4 e).  Step s + 1 is read and transformed under the MFMAs of step s.
+//           No LDS beside the halo and no barrier inside the K loop: two per tile (halo free / next halo visible)
 //   epilogue: p4's arithmetic per output pixel (bias added after the transform), stores and partial sums masked to the
 //           image; GAP / DOT partials in p4's slot layout (one per (2-row strip, 32 columns)).
-#define W4_VCHUNK (4 * 32 * 32)  // floats
 template <bool AFFINE, bool MASK, bool RES, bool GATE, bool DOT>
 __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, int total_tiles, const float* __restrict__ wu) {
   constexpr int THv = 4, HHv = 6;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* const vbuf = lds + HALO_H * HALO_W * 64;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int mb = wave >> 1, coh = wave & 1;
   const int n = lane & 15, q = lane >> 4;
   const int H = p.H, W = p.W;
-  const int co = wave * 16 + n;
-  const float bv = p.bias ? p.bias[co * p.bias_n] : 0.f;
+  const int co = coh * 32 + n;  // N block nb adds 16
+  const float bv[2] = {p.bias ? p.bias[co * p.bias_n] : 0.f, p.bias ? p.bias[(co + 16) * p.bias_n] : 0.f};
   const sisr_rsrc_t rw = sisr_rsrc(wu);
-  const unsigned boff = (unsigned)(q * 64 + co) * 16u;
+  const unsigned boff = (unsigned)(q * 64 + co) * 16u;  // N block nb: + 256 B
 
-  const int G = gridDim.x;
-  int t_begin = blockIdx.x, t_end = total_tiles, t_step = G;
-  if ((G & 7) == 0) {
+  const int nwg = gridDim.x;
+  int t_begin = blockIdx.x, t_end = total_tiles, t_step = nwg;
+  if ((nwg & 7) == 0) {
     const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3, per = (total_tiles + 7) >> 3;
     t_begin = xcd * per + idx;
     t_end = min(total_tiles, (xcd + 1) * per);
-    t_step = G >> 3;
+    t_step = nwg >> 3;
   }
   auto decode = [&](int tile, int& b, int& h0, int& w0) {
     const int tw = tile % p.tiles_w;
@@ -1025,15 +1026,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
     h0 = (t2 - b * p.tiles_h) * THv;
     w0 = tw * TW;
   };
-  // halo staging: conv3x3_c64_p4_kernel's issue / commit
+  // halo staging: conv3x3_c64_p4_kernel's issue / commit; the staged rows live in the caller's scope (one tile's worth:
+  // a kernel-wide array would be one live range around the tile loop)
   const int c4 = tid & 15, pcol = tid >> 4;
-  f32x4 v[HHv][3];
-  auto issue = [&](int tile) {
+  typedef f32x4 halo_regs_t[HHv][3];
+  auto issue = [&](halo_regs_t& v, int tile, int r0, int r1) {  // halo rows [r0, r1)
     int b, h0, w0;
     decode(tile, b, h0, w0);
     const sisr_rsrc_t rx = sisr_rsrc(p.x + (long)b * p.xv.sB);
 #pragma unroll
-    for (int r = 0; r < HHv; ++r) {
+    for (int r = r0; r < r1; ++r) {
       const unsigned ro = (unsigned)(min(max(h0 - 1 + r, 0), H - 1) * (int)p.xv.sH) * 4u;
 #pragma unroll
       for (int k = 0; k < 3; ++k)
@@ -1043,7 +1045,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
         }
     }
   };
-  auto commit = [&](int tile) {
+  auto commit = [&](const halo_regs_t& v, int tile) {
     int b, h0, w0;
     decode(tile, b, h0, w0);
     const bool interior = h0 >= 1 && h0 + THv + 1 <= H && w0 >= 1 && w0 + TW + 1 <= W;
@@ -1087,108 +1089,129 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
     }
   };
 
-  // input transform map: thread (Winograd tile vt = tr * 16 + tc, 16-B channel piece vc of the current ci half)
-  const int vt = tid >> 3, vc = tid & 7;
-  const int vtr = vt >> 4, vtc = vt & 15;
-  const unsigned vw_off = (unsigned)(vt * 32 + ((vc ^ ((vt >> 1) & 7)) << 2));
-  // A fragments: tile mb * 16 + n, pieces 4g + q of the ci half
-  unsigned aoff[2][2];
+  // A fragments: halo float offset of (row 2mb, column 2n + j, piece q ^ (col & 15)); step G flips bits 4..5 (piece 4G + q)
+  unsigned aoff[4];
 #pragma unroll
-  for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-      const int t = mb * 16 + n;
-      aoff[mb][g] = (unsigned)(t * 32 + (((4 * g + q) ^ ((t >> 1) & 7)) << 2));
-    }
+  for (int j = 0; j < 4; ++j) {
+    const int col = 2 * n + j;
+    aoff[j] = (unsigned)(2 * mb * (HALO_W * 64) + col * 64 + ((q ^ (col & 15)) << 2));
+  }
 
   if (t_begin < t_end) {
-    issue(t_begin);
-    commit(t_begin);
+    halo_regs_t v;
+    issue(v, t_begin, 0, HHv);
+    commit(v, t_begin);
   }
   __syncthreads();
   for (int tile = t_begin; tile < t_end; tile += t_step) {
     const bool has_next = tile + t_step < t_end;
     int b, h0, w0;
     decode(tile, b, h0, w0);
-    // step s = ((xr * 2 + hf) * 4 + xc) * 2 + g: B fragment U[xi = 4 xr + xc][G = 2 hf + g], 4 KB apart per (xi, G)
-#define W4_BOFF(s) ((unsigned)((((((s) >> 4) * 4 + (((s) >> 1) & 3)) * 4) + (((s) >> 3) & 1) * 2 + ((s) & 1)) * 4096))
+    // step s = xr * 4 + G; weight load t = (s * 4 + xc) * 2 + nb: B fragment U[xi = 4 xr + xc][G], 4 KB apart per (xi, G)
+#define W4_LOAD_B(t) \
+  sisr_buf_load4(rw, boff, (unsigned)((((((t) >> 5) * 4 + (((t) >> 1) & 3)) * 4 + (((t) >> 3) & 3)) * 4096) + ((t) & 1) * 256))
     f32x4 bq[8];
 #pragma unroll
-    for (int s = 0; s < 6; ++s) bq[s] = sisr_buf_load4(rw, boff, W4_BOFF(s));
-    if (GATE && has_next) issue(tile + t_step);
-    f32x4 y[2][2][2];  // [mb][out row i][out col j], registers = the lane's four tiles 4q + reg
-    f32x4 acc[4][2];   // [xc][mb] of the current xr
+    for (int t = 0; t < 6; ++t) bq[t] = W4_LOAD_B(t);
+    f32x4 y[2][2][2];  // [nb][out row i][out col j], registers = the lane's four tiles 4q + reg
+    f32x4 acc[4][2];   // [xc][nb] of the current xr
+    f32x4 raw[4], rr[4], av[2][4];
+    halo_regs_t v;  // the next tile's staged halo: written (steps 12, 14) and read (commit) under has_next only, else undefined
+    // halo pieces of step s, columns 2n + 2hc + {0, 1}: rows 2mb + ra, 2mb + rb, combined into the rows of B^T d B
+    // xr 0: d0 - d2, 1: d1 + d2, 2: d2 - d1, 3: d1 - d3  (ra, rb) = (0,2) (2,1) (2,1) (3,1)
+    auto read_half = [&](int s, int hc) {
+      const int xr = s >> 2, G = s & 3;
+      const int ra = xr == 0 ? 0 : (xr == 3 ? 3 : 2), rb = xr == 0 ? 2 : 1;
 #pragma unroll
-    for (int xc = 0; xc < 4; ++xc) acc[xc][0] = acc[xc][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      for (int jj = 0; jj < 2; ++jj) {
+        const float* base = lds + (aoff[2 * hc + jj] ^ (unsigned)(G << 4));
+        raw[2 * jj] = *reinterpret_cast<const f32x4*>(base + ra * (HALO_W * 64));
+        raw[2 * jj + 1] = *reinterpret_cast<const f32x4*>(base + rb * (HALO_W * 64));
+      }
+    };
+    auto rows_half = [&](int s, int hc) {
+      const int xr = s >> 2;
 #pragma unroll
-    for (int xr = 0; xr < 4; ++xr) {
+      for (int jj = 0; jj < 2; ++jj) {
+        const f32x4 da = raw[2 * jj], db = raw[2 * jj + 1];
+        rr[2 * hc + jj] = xr == 0 ? da - db : (xr == 1 ? db + da : (xr == 2 ? da - db : db - da));
+      }
+    };
+    auto cols_step = [&](int s) {
+      f32x4* a = av[s & 1];
+      a[0] = rr[0] - rr[2];
+      a[1] = rr[1] + rr[2];
+      a[2] = rr[2] - rr[1];
+      a[3] = rr[1] - rr[3];
+    };
+    read_half(0, 0);
+    rows_half(0, 0);
+    read_half(0, 1);
+    rows_half(0, 1);
+    cols_step(0);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-        // ---- V chunk (xr, ci half hf) from the halo: rows, then columns, of B^T d B
-        if (xr | hf) __syncthreads();  // every wave is done reading the previous chunk
-        // the next tile's halo is requested two chunks before this one's is last read (fewer registers held across the
-        // K loop than p4's whole-tile lead) and written to LDS right after that.  GATE keeps p4's schedule: its commit
-        // also fetches the skip map, which does not fit beside the K loop's registers
-        if (!GATE && xr == 3 && hf == 0 && has_next) issue(tile + t_step);
-        {
-          const int ra = xr == 0 ? 0 : (xr == 3 ? 3 : 2), rb = xr == 0 ? 2 : 1;  // row combine d[ra] -+ d[rb]
-          const int c = hf * 8 + vc;
-          f32x4 rr[4];
+    for (int s = 0; s < 16; ++s) {
+      const int xr = s >> 2, G = s & 3;
+      // the next tile's halo is requested in two halves, at steps 12 and 14 of 16 (few registers held across the K loop),
+      // and written to LDS right after the loop
+      if (s == 12 && has_next) issue(v, tile + t_step, 0, 3);
+      if (s == 14 && has_next) issue(v, tile + t_step, 3, HHv);
+      // step s + 1 is read and transformed under the MFMAs of step s, half the columns at a time
+      if (s + 1 < 16) read_half(s + 1, 0);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int col = 2 * vtc + j;
-            const float* base = lds + col * 64 + ((c ^ (col & 15)) << 2);
-            const f32x4 da = *reinterpret_cast<const f32x4*>(base + (2 * vtr + ra) * (HALO_W * 64));
-            const f32x4 db = *reinterpret_cast<const f32x4*>(base + (2 * vtr + rb) * (HALO_W * 64));
-            // xr 0: d0 - d2, 1: d1 + d2, 2: d2 - d1, 3: d1 - d3  (ra, rb) = (0,2) (2,1) (2,1) (3,1)
-            rr[j] = xr == 0 ? da - db : (xr == 1 ? db + da : (xr == 2 ? da - db : db - da));
-          }
-          float* vw = vbuf + vw_off;
-          *reinterpret_cast<f32x4*>(vw + 0 * 1024) = rr[0] - rr[2];
-          *reinterpret_cast<f32x4*>(vw + 1 * 1024) = rr[1] + rr[2];
-          *reinterpret_cast<f32x4*>(vw + 2 * 1024) = rr[2] - rr[1];
-          *reinterpret_cast<f32x4*>(vw + 3 * 1024) = rr[1] - rr[3];
+      for (int xc = 0; xc < 4; ++xc) {
+        const f32x4 a = av[s & 1][xc];
+        f32x4 bb[2];
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+          const int t = (s * 4 + xc) * 2 + nb;
+          bb[nb] = bq[t & 7];
         }
-        __syncthreads();
-        if (!GATE && xr == 3 && hf == 1 && has_next) commit(tile + t_step);  // the halo is free: no wave reads it again
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- 4 transform points x 32 input channels: 64 MFMAs per wave
 #pragma unroll
-        for (int xc = 0; xc < 4; ++xc)
+        for (int e = 0; e < 4; ++e)
 #pragma unroll
-          for (int g = 0; g < 2; ++g) {
-            const int s = ((xr * 2 + hf) * 4 + xc) * 2 + g;
-            if (s + 6 < 64) bq[(s + 6) & 7] = sisr_buf_load4(rw, boff, W4_BOFF(s + 6));
-            const f32x4 a0 = *reinterpret_cast<const f32x4*>(vbuf + xc * 1024 + aoff[0][g]);
-            const f32x4 a1 = *reinterpret_cast<const f32x4*>(vbuf + xc * 1024 + aoff[1][g]);
-            const f32x4 bb = bq[s & 7];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              acc[xc][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[e], bb[e], acc[xc][0], 0, 0, 0);
-              acc[xc][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[e], bb[e], acc[xc][1], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
+          for (int nb = 0; nb < 2; ++nb) {
+            // a new xr row starts from a zero C operand: the accumulators are never cleared
+            const f32x4 c = (G | e) ? acc[xc][nb] : (f32x4){0.f, 0.f, 0.f, 0.f};
+            acc[xc][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], bb[nb][e], c, 0, 0, 0);
           }
-      }
-      // ---- fold row xr of A^T M A: T = (m0 + m1 + m2, m1 - m2 - m3); y0 += T (xr 0..2), y1 += T (1), -= T (2, 3)
 #pragma unroll
-      for (int mb = 0; mb < 2; ++mb) {
-        const f32x4 t0 = acc[0][mb] + acc[1][mb] + acc[2][mb];
-        const f32x4 t1 = acc[1][mb] - acc[2][mb] - acc[3][mb];
-        if (xr == 0) { y[mb][0][0] = t0; y[mb][0][1] = t1; }
-        if (xr == 1) { y[mb][0][0] += t0; y[mb][0][1] += t1; y[mb][1][0] = t0; y[mb][1][1] = t1; }
-        if (xr == 2) { y[mb][0][0] += t0; y[mb][0][1] += t1; y[mb][1][0] -= t0; y[mb][1][1] -= t1; }
-        if (xr == 3) { y[mb][1][0] -= t0; y[mb][1][1] -= t1; }
+        for (int nb = 0; nb < 2; ++nb) {
+          const int t = (s * 4 + xc) * 2 + nb;
+          if (t + 6 < 128) bq[(t + 6) & 7] = W4_LOAD_B(t + 6);
+        }
+        if (s + 1 < 16) {
+          if (xc == 1) {
+            rows_half(s + 1, 0);
+            read_half(s + 1, 1);
+          }
+          if (xc == 2) rows_half(s + 1, 1);
+          if (xc == 3) cols_step(s + 1);
+        }
+        __builtin_amdgcn_sched_barrier(0);
       }
+      if (G == 3) {
+        // ---- fold row xr of A^T M A: T = (m0 + m1 + m2, m1 - m2 - m3); y0 += T (xr 0..2), y1 += T (1), -= T (2, 3)
 #pragma unroll
-      for (int xc = 0; xc < 4; ++xc) acc[xc][0] = acc[xc][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int nb = 0; nb < 2; ++nb) {
+          const f32x4 t0 = acc[0][nb] + acc[1][nb] + acc[2][nb];
+          const f32x4 t1 = acc[1][nb] - acc[2][nb] - acc[3][nb];
+          if (xr == 0) { y[nb][0][0] = t0; y[nb][0][1] = t1; }
+          if (xr == 1) { y[nb][0][0] += t0; y[nb][0][1] += t1; y[nb][1][0] = t0; y[nb][1][1] = t1; }
+          if (xr == 2) { y[nb][0][0] += t0; y[nb][0][1] += t1; y[nb][1][0] -= t0; y[nb][1][1] -= t1; }
+          if (xr == 3) { y[nb][1][0] -= t0; y[nb][1][1] -= t1; }
+          // the fold happens here: sunk towards the epilogue it would keep every row's 32 accumulators live instead
+#pragma unroll
+          for (int i = 0; i < (xr == 0 ? 1 : 2); ++i) asm volatile("" : "+v"(y[nb][i][0]), "+v"(y[nb][i][1]));
+        }
+      }
     }
-#undef W4_BOFF
-    __syncthreads();  // every wave is done with this tile's V chunk (and the halo); but for GATE the next halo is in LDS
-    // ---- epilogue: pixel (h0 + 2 mb + i, w0 + 8 q + 2 reg + j), channel co
+#undef W4_LOAD_B
+    __syncthreads();  // every wave is done with this tile's halo
+    if (has_next) commit(v, tile + t_step);
+    // ---- epilogue: pixel (h0 + 2 mb + i, w0 + 8 q + 2 reg + j), channel co + 16 nb
     {
-      float os = p.alpha;
-      if (p.out_scale) os *= p.out_scale[(long)b * 64 + co];
       const bool scaled = p.out_scale != nullptr || p.alpha != 1.0f;
       const sisr_rsrc_t ry = sisr_rsrc(p.y + (long)b * p.yv.sB);
       const sisr_rsrc_t rmk = sisr_rsrc(MASK ? p.mask + (long)b * p.yv.sB : p.y);
@@ -1196,7 +1219,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
       const sisr_rsrc_t rdt = sisr_rsrc(DOT ? p.dot + (long)b * p.yv.sB : p.y);
       float gsum[2];
 #pragma unroll
-      for (int mb = 0; mb < 2; ++mb) {
+      for (int nb = 0; nb < 2; ++nb) {
+        const int con = co + 16 * nb;
+        float os = p.alpha;
+        if (p.out_scale) os *= p.out_scale[(long)b * 64 + con];
         float mk[2][2][4], rs[2][2][4], dt[2][2][4];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -1205,7 +1231,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int row = min(h0 + 2 * mb + i, H - 1), col = min(w0 + 8 * q + 2 * r + j, W - 1);
-              const unsigned vo = (unsigned)(col * (int)p.yv.sW + co) * 4u, so = (unsigned)(row * (int)p.yv.sH) * 4u;
+              const unsigned vo = (unsigned)(col * (int)p.yv.sW + con) * 4u, so = (unsigned)(row * (int)p.yv.sH) * 4u;
               if (MASK) mk[i][j][r] = sisr_buf_load1(rmk, vo, so);
               if (RES) rs[i][j][r] = sisr_buf_load1(rrs, vo, so);
               if (DOT) dt[i][j][r] = sisr_buf_load1(rdt, vo, so);
@@ -1217,31 +1243,28 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
           for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              float a = y[mb][i][j][r] + bv;
+              float a = y[nb][i][j][r] + bv[nb];
               if (p.relu) a = fmaxf(a, 0.f);
               if (scaled) a *= os;
               if (MASK) a = mk[i][j][r] > 0.f ? a : 0.f;
               if (RES) a += rs[i][j][r];
               const int row = h0 + 2 * mb + i, col = w0 + 8 * q + 2 * r + j;
               if (row < H && col < W) {
-                sisr_buf_store1(a, ry, (unsigned)(col * (int)p.yv.sW + co) * 4u, (unsigned)(row * (int)p.yv.sH) * 4u);
+                sisr_buf_store1(a, ry, (unsigned)(col * (int)p.yv.sW + con) * 4u, (unsigned)(row * (int)p.yv.sH) * 4u);
                 gs = DOT ? __builtin_fmaf(a, dt[i][j][r], gs) : gs + a;
               }
             }
         gs += __shfl_xor(gs, 16);
-        gsum[mb] = gs + __shfl_xor(gs, 32);
+        gsum[nb] = gs + __shfl_xor(gs, 32);
       }
       if (p.gap && q == 0) {
         const long parts = (long)p.tiles_w * ((H + 3) / 4) * 2;
         const int th = h0 / THv, tw = w0 / TW;
 #pragma unroll
-        for (int mb = 0; mb < 2; ++mb) p.gap[(((long)b * parts) + (th * p.tiles_w + tw) * 2 + mb) * 64 + co] = gsum[mb];
+        for (int nb = 0; nb < 2; ++nb) p.gap[(((long)b * parts) + (th * p.tiles_w + tw) * 2 + mb) * 64 + co + 16 * nb] = gsum[nb];
       }
     }
-    if (GATE && has_next) {
-      commit(tile + t_step);
-      __syncthreads();
-    }
+    __syncthreads();  // the next tile's halo is in LDS
   }
 }
 
@@ -2752,12 +2775,10 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
       const dim3 gp((unsigned)(nblk < 512 ? nblk : 512));
       const size_t lbp = HALO_H * HALO_W * 64 * sizeof(float);
       if (sisr_use_winograd(wino_avail, wino_force, (long)B * H * W)) {
-        const size_t lbw = lbp + W4_VCHUNK * sizeof(float);
         const float* wu = wpacked + 64 * 64 * 9;
 #define W4X(RS, GT, DT)                                                                                       \
   do {                                                                                                        \
-    SISR_ALLOW_LDS((conv3x3_c64_w4_kernel<false, false, RS, GT, DT>), lbw);                                   \
-    hipLaunchKernelGGL((conv3x3_c64_w4_kernel<false, false, RS, GT, DT>), gp, dim3(256), lbw, st, p, (int)nblk, wu); \
+    hipLaunchKernelGGL((conv3x3_c64_w4_kernel<false, false, RS, GT, DT>), gp, dim3(256), lbp, st, p, (int)nblk, wu); \
   } while (0)
         if (gate) { if (rs) W4X(true, true, false); else W4X(false, true, false); }
         else      { if (rs) W4X(true, false, true); else W4X(false, false, true); }
@@ -2811,12 +2832,10 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
       const dim3 gp((unsigned)(nblk < 512 ? nblk : 512));
       const size_t lbp = HALO_H * HALO_W * 64 * sizeof(float);
       if (sisr_use_winograd(wino_avail, wino_force, (long)B * H * W)) {
-        const size_t lbw = lbp + W4_VCHUNK * sizeof(float);
         const float* wu = wpacked + 64 * 64 * 9;
 #define W4K(AF, MK, RS)                                                                                       \
   do {                                                                                                        \
-    SISR_ALLOW_LDS((conv3x3_c64_w4_kernel<AF, MK, RS, false, false>), lbw);                                   \
-    hipLaunchKernelGGL((conv3x3_c64_w4_kernel<AF, MK, RS, false, false>), gp, dim3(256), lbw, st, p, (int)nblk, wu); \
+    hipLaunchKernelGGL((conv3x3_c64_w4_kernel<AF, MK, RS, false, false>), gp, dim3(256), lbp, st, p, (int)nblk, wu); \
   } while (0)
         if (aff) W4K(true, true, false);
         else if (msk) W4K(false, true, false);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the hot kernels through the C ABI (HIP-event timing, one process).
 
-    python tools/kbench.py [--batch 8] [--iters 20] [--only conv,wgrad,...]
+    python tools/kbench.py [--batch 8] [--iters 20] [--only conv,wgrad,...] [--winograd]
 Prints one JSON line per kernel: mean launch time and achieved TFLOP/s (or GB/s) on 128x128x64 maps.
 Used for interleaved A/B of kernel variants and as the target of rocprofv3 --pmc passes.
 """
@@ -44,6 +44,8 @@ def main():
     ap.add_argument("--variants", default="4,2", help="conv kernel selections to time: 4 auto, 6 / 7 per-tile / persistent form forced, 2 general")
     ap.add_argument("--rounds", type=int, default=0, help="interleaved A/B rounds over --variants (conv only)")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "bf16x3"])
+    ap.add_argument("--winograd", action="store_true", help="pack the weight as the step-level plan does, Winograd transform "
+                    "included: the default-selection convs then run conv3x3_c64_w4_kernel above 8 x 128^2 pixels")
     a = ap.parse_args()
     ops.set_precision(a.precision)
     WARM[0] = a.warm
@@ -63,7 +65,13 @@ def main():
     sc = torch.rand(B, 64, generator=g).to(dev)
     sh = torch.rand(B, 64, generator=g).to(dev)
     v = hip.view_plain(H, W, 64)
-    pk = ops.pack_weight(w, "fwd")
+    if a.winograd:
+        plan = ops._PackPlan([(w, 1)], w.device)
+        plan.run()
+        ops.invalidate_packs()
+        pk = plan.slices[0][0]
+    else:
+        pk = ops.pack_weight(w, "fwd")
     gap = torch.empty(B, ops.gap_parts(H, W), 64, device=dev)
     dw, db = torch.empty_like(w), torch.empty(64, device=dev)
     flop = 2.0 * B * H * W * 64 * 64 * 9
