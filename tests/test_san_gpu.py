@@ -3,6 +3,11 @@
 Tolerances, fp32: the covariance / Newton-Schulz chain amplifies summation-order noise a little more than a conv
 (five coupled 64x64 iterations), so the second-order gate is compared at 1e-4 relative; the whole-net and Set5 checks
 use the same bars as the other models (1e-3 dB Y-PSNR).
+
+These bars are those of whole blocks and nets.  The kernels of csrc/san.hip and csrc/nonlocal.hip themselves are pinned to
+float64 by tests/test_san_kernels_gpu.py: every native entry point called directly, exact on dyadic data, bounded by
+c * 2^-24 of the magnitude for the one-pass kernels, and within 8x the reference's own fp32 error for the square-root and
+attention chains (references: tests/_san.py, checked on the CPU by tests/test_san_cpu.py).
 """
 import numpy as np
 import pytest
