@@ -491,28 +491,28 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_full_geo_kernel(WgradPara
 //   tile: 4 x 32 output pixels = 2 x 16 blocks (K = 32 per tile and transform point); staged like the dense kernel
 //         (issue the next tile's loads before this tile's K loops, commit them to LDS once the raw image is free):
 //         x halo 6 x 34 x 64 (52.2 KB) and dY' 4 x 32 x 64 (32.8 KB), fp32, [row][col][64 ch]
-//   chunks: per xr, the workgroup transforms the raw image ONCE into V[xc 4][block 32][64 ci] and M[xc 4][block 32][64 co]
-//         (32.8 KB each; 150.5 KB of LDS in all): thread (block tid >> 3, 16-B pieces q, q + 8) builds four xc of both
+//         (85.0 KB of LDS in all; V and M never go to LDS)
 //   wave w = (ci half w >> 1, co half w & 1): 16 persistent 32 x 32 accumulators (256 registers, one per xi), K index
-//         (lane >> 5) = block parity, v_mfma_f32_32x32x2_f32 fed by two ds_read_b32 (the dense kernel's K loop: MFMA and
-//         ds_read only; operands requested four steps ahead, one wave per SIMD)
-//   budget per tile and SIMD: 4 x 64 MFMAs = 16.4 K cycles (direct form on the same pixels: 36.9 K); per xr two barriers
-//         around the chunk build (24 ds_read_b128, 16 ds_write_b128, ~110 VALU per thread), not overlapped with MFMAs
+//         (lane >> 5) = block parity, one wave per SIMD.  K-step ks (16 per tile) covers blocks 2 ks and 2 ks + 1: lane
+//         (i, kk) reads the raw 4 x 4 patch of block 2 ks + kk, channel ci half * 32 + i, and the raw 2 x 2 dY' block of
+//         channel co half * 32 + i (20 ds_read_b32, 32 consecutive floats per 32-lane half: no bank conflict), forms its 16
+//         V and 16 M values itself (32 + 12 adds, rows first, then columns) and issues 16 v_mfma_f32_32x32x2_f32, one per
+//         xi.  Per accumulator the K order is ks ascending with block 2 ks + kk in lane slot kk, as when V and M were
+//         staged through LDS chunks, so the sums are the same bit for bit.
+//   budget per tile and SIMD: 16 x 16 MFMAs = 16.4 K cycles (direct form on the same pixels: 36.9 K); the reads and adds of
+//         step ks + 1 sit between step ks's MFMAs (sched_group_barrier), two barriers per tile around the commit
 //   epilogue: per lane the 16 dU registers of an element are folded to the nine taps (dg = G^T dU G, coefficients
 //         +-1 and 1/2) and stored as the dense kernel's quadrant slab; bias slabs and the second stage are unchanged.
 #define W4_TH 4
 #define W4_HH (W4_TH + 2)
 #define W4G_X (W4_HH * WH_W * 64)  // floats
 #define W4G_Y (W4_TH * WT_W * 64)
-#define W4G_CHUNK (4 * 32 * 64)
-#define W4G_LDS ((W4G_X + W4G_Y + 2 * W4G_CHUNK) * 4)  // bytes: 150528
+#define W4G_LDS ((W4G_X + W4G_Y) * 4)  // bytes: 84992
 
 __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* const ldx = lds;
   float* const ldy = lds + W4G_X;
-  float* const vch = ldy + W4G_Y;
-  float* const mch = vch + W4G_CHUNK;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int pair = blockIdx.y;
   const int cq = pair % p.cout_chunks, cc = pair / p.cout_chunks;
@@ -649,79 +649,119 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
     }
   };
 
-  // chunk builder: thread (block vb = tid >> 3 = (row vbr, column vbc), 16-B pieces q and q + 8 of the 64 channels)
-  const int vb = tid >> 3, q = tid & 7;
-  const int vbr = vb >> 4, vbc = vb & 15;
-  auto build = [&](int xr) {
+  // K-step ks: this lane's block 2 ks + kk = (row ks >> 3, column 2 (ks & 7) + kk); raw 4 x 4 patch of its ci channel and
+  // raw 2 x 2 dY' block of its co channel (the lane base carries kk and the channel, the rest is a constant per step)
+  const float* const xl = ldx + kk * (2 * 64) + cih * 32 + i;
+  const float* const yl = ldy + kk * (2 * 64) + coh * 32 + i;
+  struct Raw {
+    float d[4][4], y[2][2];
+  };
+  auto fetch = [&](int ks, Raw& rw) {
+    const int br = ks >> 3, bc = ks & 7;
 #pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-      const int ch = (q + 8 * hf) * 4;
-      {  // V = B^T d B: rows xr 0: d0 - d2, 1: d1 + d2, 2: d2 - d1, 3: d1 - d3, then the same over columns
-        const int ra = xr == 0 ? 0 : (xr == 3 ? 3 : 2), rb = xr == 0 ? 2 : 1;
-        f32x4 rr[4];
+    for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float* base = ldx + (2 * vbc + j) * 64 + ch;
-          const f32x4 da = *reinterpret_cast<const f32x4*>(base + (2 * vbr + ra) * (WH_W * 64));
-          const f32x4 db = *reinterpret_cast<const f32x4*>(base + (2 * vbr + rb) * (WH_W * 64));
-          rr[j] = xr == 0 ? da - db : (xr == 1 ? db + da : (xr == 2 ? da - db : db - da));
-        }
-        float* vw = vch + vb * 64 + ch;
-        *reinterpret_cast<f32x4*>(vw + 0 * 2048) = rr[0] - rr[2];
-        *reinterpret_cast<f32x4*>(vw + 1 * 2048) = rr[1] + rr[2];
-        *reinterpret_cast<f32x4*>(vw + 2 * 2048) = rr[2] - rr[1];
-        *reinterpret_cast<f32x4*>(vw + 3 * 2048) = rr[1] - rr[3];
-      }
-      {  // M = A dY' A^T with A's last row negated: rows xr 0: y0, 1: y0 + y1, 2: y0 - y1, 3: y1, then over columns
-        f32x4 rr[2];
+      for (int j = 0; j < 4; ++j) rw.d[r][j] = xl[((2 * br + r) * WH_W + 4 * bc + j) * 64];
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const float* base = ldy + (2 * vbc + j) * 64 + ch;
-          const f32x4 y0 = *reinterpret_cast<const f32x4*>(base + (2 * vbr) * (WT_W * 64));
-          const f32x4 y1 = *reinterpret_cast<const f32x4*>(base + (2 * vbr + 1) * (WT_W * 64));
-          rr[j] = xr == 0 ? y0 : (xr == 1 ? y0 + y1 : (xr == 2 ? y0 - y1 : y1));
-        }
-        float* mw = mch + vb * 64 + ch;
-        *reinterpret_cast<f32x4*>(mw + 0 * 2048) = rr[0];
-        *reinterpret_cast<f32x4*>(mw + 1 * 2048) = rr[0] + rr[1];
-        *reinterpret_cast<f32x4*>(mw + 2 * 2048) = rr[0] - rr[1];
-        *reinterpret_cast<f32x4*>(mw + 3 * 2048) = rr[1];
-      }
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) rw.y[r][j] = yl[((2 * br + r) * WT_W + 4 * bc + j) * 64];
+  };
+  // V = B^T d B (rows 0: d0 - d2, 1: d1 + d2, 2: d2 - d1, 3: d1 - d3, then the same over columns) and M = A dY' A^T with
+  // A's last row negated (rows 0: y0, 1: y0 + y1, 2: y0 - y1, 3: y1, then over columns); index xi = xr * 4 + xc
+  auto transform = [&](const Raw& rw, float (&V)[16], float (&M)[16]) {
+    float rr[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      rr[0][j] = rw.d[0][j] - rw.d[2][j];
+      rr[1][j] = rw.d[1][j] + rw.d[2][j];
+      rr[2][j] = rw.d[2][j] - rw.d[1][j];
+      rr[3][j] = rw.d[1][j] - rw.d[3][j];
+    }
+#pragma unroll
+    for (int xr = 0; xr < 4; ++xr) {
+      V[xr * 4 + 0] = rr[xr][0] - rr[xr][2];
+      V[xr * 4 + 1] = rr[xr][1] + rr[xr][2];
+      V[xr * 4 + 2] = rr[xr][2] - rr[xr][1];
+      V[xr * 4 + 3] = rr[xr][1] - rr[xr][3];
+    }
+    float ry[4][2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      ry[0][j] = rw.y[0][j];
+      ry[1][j] = rw.y[0][j] + rw.y[1][j];
+      ry[2][j] = rw.y[0][j] - rw.y[1][j];
+      ry[3][j] = rw.y[1][j];
+    }
+#pragma unroll
+    for (int xr = 0; xr < 4; ++xr) {
+      M[xr * 4 + 0] = ry[xr][0];
+      M[xr * 4 + 1] = ry[xr][0] + ry[xr][1];
+      M[xr * 4 + 2] = ry[xr][0] - ry[xr][1];
+      M[xr * 4 + 3] = ry[xr][1];
     }
   };
 
+  // ---- per tile 16 K-steps of two blocks, 16 MFMAs each (one per transform point).  Step ks + 1's raw values are
+  // requested behind step ks's first MFMAs and transformed between the others, so V / M alternate between two register
+  // sets.  Once step 15's values are read no wave needs the raw image: the next tile is committed in front of step 15's
+  // MFMAs and its step 0 is fetched and transformed between them (read, unused, from the stale image after the last tile).
+  float V[2][16], M[2][16];
+  auto step_order = [&]() {  // reads behind the first two MFMAs, two MFMAs for them to land, then the 44 adds four to a gap
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 5, 0);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+#pragma unroll
+    for (int t = 4; t < 15; ++t) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+  };
   if (t_begin < t_end) {
     issue(t_begin);
     commit(t_begin);
+    __syncthreads();
+    Raw rw;
+    fetch(0, rw);
+    transform(rw, V[0], M[0]);
   }
   for (int tile = t_begin; tile < t_end; tile += t_step) {
     const bool has_next = tile + t_step < t_end;  // uniform
     if (has_next) issue(tile + t_step);
 #pragma unroll
-    for (int xr = 0; xr < 4; ++xr) {
-      __syncthreads();  // the previous chunks are consumed (and the raw image committed)
-      build(xr);
-      __syncthreads();
-      if (xr == 3 && has_next) commit(tile + t_step);  // no wave reads the raw image again
-      // ---- 4 xc x 16 K-steps of two blocks: step s = xc * 16 + ks reads block 2 s + kk of the chunk pair
-      const float* va = vch + kk * 64 + cih * 32 + i;
-      const float* vm = mch + kk * 64 + coh * 32 + i;
-      float pa[4], pb[4];
+    for (int ks = 0; ks < 15; ++ks) {
+      const int cur = ks & 1, nxt = cur ^ 1;
+      Raw rw;
+      fetch(ks + 1, rw);
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        pa[s] = va[s * 128];
-        pb[s] = vm[s * 128];
-      }
+      for (int t = 0; t < 16; ++t)
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(V[cur][t], M[cur][t], acc[t], 0, 0, 0);
+      transform(rw, V[nxt], M[nxt]);
+      step_order();
+    }
+    __syncthreads();  // no wave reads the raw image again
+    if (has_next) commit(tile + t_step);
 #pragma unroll
-      for (int s = 0; s < 64; ++s) {
-        const float a = pa[s & 3], bb = pb[s & 3];
-        if (s + 4 < 64) {
-          pa[s & 3] = va[(s + 4) * 128];
-          pb[s & 3] = vm[(s + 4) * 128];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        acc[xr * 4 + (s >> 4)] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bb, acc[xr * 4 + (s >> 4)], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
+    for (int t = 0; t < 8; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(V[1][t], M[1][t], acc[t], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);  // the commit's LDS writes drain under those eight MFMAs
+    __syncthreads();  // the next raw image is committed
+    {
+      Raw rw;
+      fetch(0, rw);
+#pragma unroll
+      for (int t = 8; t < 16; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(V[1][t], M[1][t], acc[t], 0, 0, 0);
+      transform(rw, V[0], M[0]);
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 10, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+#pragma unroll
+      for (int t = 0; t < 5; ++t) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 9, 0);
       }
     }
   }
