@@ -569,6 +569,41 @@ size_t sisr_ssim_workspace_bytes(int n, int h, int w);
 int sisr_ssim(const float* a, const float* b, int n, int channels, int h, int w, double data_range, double* out,
               void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- SRCNN / VDSR building blocks (csrc/basic.hip) ------------------------------------------------------------------
+ * ref: SISR/models/basic/architectures.py (SRCNN, VDSR: K x K convs, padding K/2), basic/handlers.py (nn.MSELoss).
+ * K odd, 1..9.  Maps between layers: channels-last, cp = 32 or 64 channels (real channels first, the rest zero); the image
+ * ends are planar (B,1,H,W).  Weights keep their OIHW layout with the REAL channel counts.  Refused before any launch:
+ * null / empty operands (-1), a K, width or padded width outside these limits (-4), misaligned maps (-2).
+ * sisr_convk_y2f: y[b,h,w,c] = act(bias[c] + sum_k x[b,h+kh-K/2,w+kw-K/2] w[c][kh][kw]), channels >= cout written as zero;
+ *   flip_taps reads w[c][K-1-kh][K-1-kw] (the input gradient of sisr_convk_f2y); mask (a cp-channel map, optional) zeroes the
+ *   result where the map is <= 0.
+ * sisr_convk_f2y: y[b,h,w] = bias[0] + sum_{c<cin,k} x[b,h+kh-K/2,w+kw-K/2,c] w[0][c][kh][kw] (+ residual[b,h,w]).
+ * sisr_corrk_y: dw[c][kh][kw] = sum_pix P[pix + s (k - K/2)] Q[pix][c], s = -1 with flip_taps (P planar, Q channels-last;
+ *   P = x, Q = dy for the 1 -> C end, P = dy, Q = x with flip_taps for the C -> 1 end); qmask (optional) zeroes Q where the
+ *   map is <= 0; db_mode 0 none, 1 db[c] = sum Q[.,c], 2 db[0] = sum P.  Ordered two-stage sums: a repeat is bit-identical.
+ * sisr_pack_convk: OIHW (cout,cin,K,K) -> the MFMA kernel's order for the forward conv (fwd, K*K*cop*cip floats) and, when
+ *   dgrad is given, for its input gradient (taps flipped, channel roles swapped).
+ * sisr_convk_mfma: y = act(conv(x [masked by in_mask > 0], packed) + bias[< nbias]) between channels-last maps of cin_p and
+ *   cout_p channels on v_mfma_f32_32x32x2_f32; relu, then mask (optional: zero where the map is <= 0).
+ * sisr_wgradk_mfma: dw (cout,cin,K,K) and db (cout, optional) from x (cip channels) and dy (cop channels, optionally
+ *   masked by dymask > 0), ordered sums.
+ * sisr_mse_loss: loss = mean (a - b)^2, grad (optional) = 2 (a - b) / n, ordered two-stage sum. */
+int sisr_convk_y2f(const float* x, const float* w, const float* bias, const float* mask, float* y, int B, int H, int W, int K,
+                   int cout, int cp, int relu, int flip_taps, void* stream);
+int sisr_convk_f2y(const float* x, const float* w, const float* bias, const float* residual, float* y, int B, int H, int W,
+                   int K, int cin, int cp, void* stream);
+size_t sisr_corrk_y_workspace_bytes(int B, int H, int W, int K, int cp);
+int sisr_corrk_y(const float* P, const float* Q, const float* qmask, float* dw, float* db, int B, int H, int W, int K,
+                 int channels, int cp, int flip_taps, int db_mode, float* workspace, size_t workspace_bytes, void* stream);
+int sisr_pack_convk(const float* w, float* fwd, float* dgrad, int K, int cout, int cin, int cop, int cip, void* stream);
+int sisr_convk_mfma(const float* x, const float* in_mask, const float* packed, const float* bias, int nbias, const float* mask,
+                    float* y, int B, int H, int W, int K, int cin_p, int cout_p, int relu, void* stream);
+size_t sisr_wgradk_mfma_workspace_bytes(int B, int H, int W, int K, int cin_p, int cout_p);
+int sisr_wgradk_mfma(const float* x, const float* dy, const float* dymask, float* dw, float* db, int B, int H, int W, int K,
+                     int cout, int cin, int cop, int cip, float* workspace, size_t workspace_bytes, void* stream);
+size_t sisr_mse_loss_workspace_bytes(void);
+int sisr_mse_loss(const float* a, const float* b, long n, float* loss, float* grad, float* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,7 +114,10 @@ class TrainingHandler:
             else:
                 rgb_out, ycbcr_out, loss, _ = self.model.net_run_and_process(**batch, request_loss=True)
                 measured = {}
-            y_proc = self.model.colorspace_convert(y, colorspace='rgb')
+            if 'rgb' in self.model.configuration['colorspace']:
+                y_proc = self.model.colorspace_convert(y, colorspace='rgb')
+            else:  # ref training_handler.py:194-197: a Y-channel model's reference images already are YCbCr
+                y_proc = self.model._standard_image_formatting(y.numpy())
             losses['val-loss'].append(loss)
             for metric in wanted:
                 if metric == 'PSNR':

@@ -1,0 +1,629 @@
+// SRCNN / VDSR building blocks: K x K convolutions (odd K <= 9, padding K/2), the one-channel (luminance) image ends and
+// the MSE loss, fp32.  ref: Code/SISR/models/basic/architectures.py (SRCNN, VDSR), basic/handlers.py (nn.MSELoss).
+//
+// Maps between layers are channels-last with CP = 32 or 64 channels (zero-padded); the image ends are planar (B,1,H,W).
+//
+//   sisr_convk_y2f     planar Y -> CP-channel map on the VALU: one thread per pixel, all CP outputs in registers, the haloed
+//                      input tile and the K^2 x CP weights in LDS, 16-byte stores.  With flip_taps (and an optional mask)
+//                      it is the input gradient of sisr_convk_f2y.
+//   sisr_convk_f2y     CP-channel map -> planar Y (+ bias, + residual): the haloed tile is staged 16 channels at a time.
+//   sisr_corrk_y       weight / bias gradient of both ends: dw[c][kh][kw] = sum_pix P[pix + s (k - K/2)] * Q[pix][c] with a
+//                      planar P and a channels-last Q; ordered two-stage sum (per-block partials, then one ordered pass).
+//   sisr_convk_mfma    K x K conv between channels-last maps on v_mfma_f32_32x32x2_f32 (implicit GEMM: M = 32 pixels of a row,
+//                      N = 32 output channels, contraction over K^2 x Cin).  The haloed input tile is staged 32 channels at
+//                      a time; the weights are streamed per tap from the packed buffer (sisr_pack_convk), which stays in L2.
+//                      The same kernel is the input gradient when given the 'dgrad' packing (taps flipped, roles swapped).
+//   sisr_wgradk_mfma   its weight gradient: per (tap, 32 input channels, pixel slice) workgroup, M = Cout, N = 32 input
+//                      channels, contraction over pixels; slices are summed in order by a second pass.
+//   sisr_mse_loss      mean squared difference and its gradient 2 (a - b) / n in the same launch (ordered two-stage sum).
+//
+// Within a lane the contraction index of the 32x32x2 MFMA is permuted (lane half h takes channels 16 h + kk at step kk), so
+// both operands are read 16 bytes at a time; A and B use the same permutation, so the sum is over the same products.
+#include "sisr_common.h"
+
+#define BK_TH 8    // pixel tile: 8 rows x 32 columns, 256 threads
+#define BK_TW 32
+#define BK_MAXK 9
+#define BK_PARTS 1024  // at most this many partial sums per reduced value (four workgroups per CU)
+#define BK_XS 36       // LDS pixel stride (floats) of the 32-channel MFMA tile: 32 + 4, keeps 16-byte reads aligned
+#define BK_FS 20       // LDS pixel stride of the 16-channel f2y tile
+
+static inline bool bk_k_ok(int K) { return K >= 1 && K <= BK_MAXK && (K & 1); }
+static inline bool bk_cp_ok(int cp) { return cp == 32 || cp == 64; }
+static inline bool bk_dims_ok(int B, int H, int W) {
+  return B > 0 && H > 0 && W > 0 && B <= 65535 && (long)B * H * W <= (1L << 28);
+}
+
+// ------------------------------------------------------------------------------------------------ Y -> features
+template <int CP>
+__global__ __launch_bounds__(256) void bk_y2f_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                     const float* __restrict__ bias, const float* __restrict__ mask,
+                                                     float* __restrict__ y, int H, int W, int K, int cout, int relu, int flip) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int p = K / 2, LW = BK_TW + K - 1, LH = BK_TH + K - 1, KK = K * K;
+  float* ws = lds;                 // [KK][CP]
+  float* bs = ws + KK * CP;        // [CP]
+  float* xs = bs + CP;             // [LH][LW]
+  const int tid = threadIdx.x, b = blockIdx.z, h0 = blockIdx.y * BK_TH, w0 = blockIdx.x * BK_TW;
+  for (int i = tid; i < LH * LW; i += 256) {
+    const int hh = h0 + i / LW - p, ww = w0 + i % LW - p;
+    xs[i] = (hh >= 0 && hh < H && ww >= 0 && ww < W) ? x[((long)b * H + hh) * W + ww] : 0.f;
+  }
+  for (int i = tid; i < KK * CP; i += 256) {
+    const int tap = i / CP, c = i % CP;
+    ws[i] = c < cout ? w[c * KK + (flip ? KK - 1 - tap : tap)] : 0.f;
+  }
+  if (tid < CP) bs[tid] = (bias && tid < cout) ? bias[tid] : 0.f;
+  __syncthreads();
+  const int ty = tid / BK_TW, tx = tid % BK_TW;
+  f32x4 acc[CP / 4];
+#pragma unroll
+  for (int q = 0; q < CP / 4; ++q) acc[q] = reinterpret_cast<const f32x4*>(bs)[q];
+  for (int kh = 0; kh < K; ++kh)
+    for (int kw = 0; kw < K; ++kw) {
+      const float v = xs[(ty + kh) * LW + tx + kw];
+      const f32x4* wr = reinterpret_cast<const f32x4*>(ws + (kh * K + kw) * CP);
+#pragma unroll
+      for (int q = 0; q < CP / 4; ++q) acc[q] += v * wr[q];
+    }
+  const int hh = h0 + ty, ww = w0 + tx;
+  if (hh >= H || ww >= W) return;
+  const long o = (((long)b * H + hh) * W + ww) * CP;
+#pragma unroll
+  for (int q = 0; q < CP / 4; ++q) {
+    f32x4 v = acc[q];
+    if (relu) {
+      v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+    }
+    if (mask) {
+      const f32x4 m = reinterpret_cast<const f32x4*>(mask + o)[q];
+      v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
+    }
+    reinterpret_cast<f32x4*>(y + o)[q] = v;
+  }
+}
+
+static size_t bk_y2f_lds(int K, int cp) {
+  return sizeof(float) * ((size_t)K * K * cp + cp + (size_t)(BK_TH + K - 1) * (BK_TW + K - 1));
+}
+
+extern "C" int sisr_convk_y2f(const float* x, const float* w, const float* bias, const float* mask, float* y, int B, int H,
+                              int W, int K, int cout, int cp, int relu, int flip_taps, void* stream) {
+  if (!x || !w || !y || !bk_dims_ok(B, H, W) || cout < 1) return SISR_ERR_ARG;
+  if (!bk_k_ok(K) || !bk_cp_ok(cp) || cout > cp) return SISR_ERR_UNSUPPORTED;
+  if (!sisr_aligned16(y) || !sisr_aligned16(mask)) return SISR_ERR_ALIGN;
+  const dim3 grid((W + BK_TW - 1) / BK_TW, (H + BK_TH - 1) / BK_TH, B);
+  const size_t lds = bk_y2f_lds(K, cp);
+  if (cp == 64)
+    hipLaunchKernelGGL(bk_y2f_kernel<64>, grid, dim3(256), lds, (hipStream_t)stream, x, w, bias, mask, y, H, W, K, cout, relu,
+                       flip_taps);
+  else
+    hipLaunchKernelGGL(bk_y2f_kernel<32>, grid, dim3(256), lds, (hipStream_t)stream, x, w, bias, mask, y, H, W, K, cout, relu,
+                       flip_taps);
+  return sisr_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------ features -> Y
+__global__ __launch_bounds__(256) void bk_f2y_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                     const float* __restrict__ bias, const float* __restrict__ res,
+                                                     float* __restrict__ y, int H, int W, int K, int cin, int cp) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int p = K / 2, LW = BK_TW + K - 1, LH = BK_TH + K - 1, KK = K * K;
+  float* ws = lds;             // [KK][cp]
+  float* xs = ws + KK * cp;    // [LH * LW][BK_FS]
+  const int tid = threadIdx.x, b = blockIdx.z, h0 = blockIdx.y * BK_TH, w0 = blockIdx.x * BK_TW;
+  for (int i = tid; i < KK * cp; i += 256) {
+    const int tap = i / cp, c = i % cp;
+    ws[i] = c < cin ? w[c * KK + tap] : 0.f;
+  }
+  const int ty = tid / BK_TW, tx = tid % BK_TW;
+  float acc = 0.f;
+  for (int c0 = 0; c0 < cin; c0 += 16) {
+    __syncthreads();  // the previous chunk's readers (and, first time round, nothing) are done with xs
+    for (int i = tid; i < LH * LW * 4; i += 256) {
+      const int pix = i >> 2, q = i & 3;
+      const int hh = h0 + pix / LW - p, ww = w0 + pix % LW - p;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (hh >= 0 && hh < H && ww >= 0 && ww < W)
+        v = *reinterpret_cast<const f32x4*>(x + (((long)b * H + hh) * W + ww) * cp + c0 + q * 4);
+      *reinterpret_cast<f32x4*>(xs + pix * BK_FS + q * 4) = v;
+    }
+    __syncthreads();
+    for (int kh = 0; kh < K; ++kh)
+      for (int kw = 0; kw < K; ++kw) {
+        const f32x4* xp = reinterpret_cast<const f32x4*>(xs + ((ty + kh) * LW + tx + kw) * BK_FS);
+        const f32x4* wp = reinterpret_cast<const f32x4*>(ws + (kh * K + kw) * cp + c0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const f32x4 a = xp[q], ww4 = wp[q];
+          acc += a.x * ww4.x + a.y * ww4.y + a.z * ww4.z + a.w * ww4.w;
+        }
+      }
+  }
+  const int hh = h0 + ty, ww = w0 + tx;
+  if (hh >= H || ww >= W) return;
+  const long o = ((long)b * H + hh) * W + ww;
+  float v = acc + (bias ? bias[0] : 0.f);
+  if (res) v += res[o];
+  y[o] = v;
+}
+
+static size_t bk_f2y_lds(int K, int cp) {
+  return sizeof(float) * ((size_t)K * K * cp + (size_t)(BK_TH + K - 1) * (BK_TW + K - 1) * BK_FS);
+}
+
+extern "C" int sisr_convk_f2y(const float* x, const float* w, const float* bias, const float* residual, float* y, int B,
+                              int H, int W, int K, int cin, int cp, void* stream) {
+  if (!x || !w || !y || !bk_dims_ok(B, H, W) || cin < 1) return SISR_ERR_ARG;
+  if (!bk_k_ok(K) || !bk_cp_ok(cp) || cin > cp) return SISR_ERR_UNSUPPORTED;
+  if (!sisr_aligned16(x)) return SISR_ERR_ALIGN;
+  const dim3 grid((W + BK_TW - 1) / BK_TW, (H + BK_TH - 1) / BK_TH, B);
+  const size_t lds = bk_f2y_lds(K, cp);  // 9 x 9 from 64 channels: 72 KB
+  SISR_ALLOW_LDS(bk_f2y_kernel, bk_f2y_lds(BK_MAXK, 64));
+  hipLaunchKernelGGL(bk_f2y_kernel, grid, dim3(256), lds, (hipStream_t)stream, x, w, bias, residual, y, H, W, K, cin, cp);
+  return sisr_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------ gradients of the ends
+// Thread (g, c): channel c, tap group g (256 / CP groups, NT = ceil(K^2 / groups) taps each).  A workgroup walks its pixel
+// tiles in a fixed order and leaves one partial per value; bk_corr_final_kernel sums the partials in workgroup order.
+template <int K, int CP>
+__global__ __launch_bounds__(256) void bk_corr_kernel(const float* __restrict__ P, const float* __restrict__ Q,
+                                                      const float* __restrict__ qmask, float* __restrict__ part, int B, int H,
+                                                      int W, int flip, int db_mode) {
+  constexpr int KK = K * K, G = 256 / CP, NT = (KK + G - 1) / G, p = K / 2, LW = BK_TW + K - 1, LH = BK_TH + K - 1;
+  constexpr int U = NT > 12 ? 4 : 8;  // pixels per batch of loads (fewer where the taps already fill the registers)
+  __shared__ float ps[LH * LW];
+  const int tid = threadIdx.x, c = tid % CP, g = tid / CP;
+  int off[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const int tap = g * NT + j;
+    int kh = tap / K, kw = tap % K;
+    if (flip) { kh = K - 1 - kh; kw = K - 1 - kw; }
+    off[j] = tap < KK ? kh * LW + kw : 0;
+  }
+  float acc[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) acc[j] = 0.f;
+  float accb = 0.f;
+  const int tx_n = (W + BK_TW - 1) / BK_TW, ty_n = (H + BK_TH - 1) / BK_TH, ntiles = B * ty_n * tx_n;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int b = tile / (ty_n * tx_n), h0 = (tile / tx_n) % ty_n * BK_TH, w0 = tile % tx_n * BK_TW;
+    __syncthreads();
+    for (int i = tid; i < LH * LW; i += 256) {
+      const int hh = h0 + i / LW - p, ww = w0 + i % LW - p;
+      ps[i] = (hh >= 0 && hh < H && ww >= 0 && ww < W) ? P[((long)b * H + hh) * W + ww] : 0.f;
+    }
+    __syncthreads();
+    const int rows = min(BK_TH, H - h0), cols = min(BK_TW, W - w0);
+    for (int py = 0; py < rows; ++py)
+      for (int px0 = 0; px0 < cols; px0 += U) {  // U pixels at a time: their loads are in flight together
+        const long o = (((long)b * H + h0 + py) * W + w0 + px0) * CP + c;
+        float q[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const bool ok = px0 + u < cols;
+          const long ou = ok ? o + (long)u * CP : o;
+          float v = Q[ou];
+          if (qmask) v = qmask[ou] > 0.f ? v : 0.f;
+          q[u] = ok ? v : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int base = py * LW + px0 + u;  // px0 + u <= 31: inside the staged tile even past `cols`, where q is 0
+#pragma unroll
+          for (int j = 0; j < NT; ++j) acc[j] += ps[base + off[j]] * q[u];
+          accb += db_mode == 2 ? (px0 + u < cols ? ps[base + p * LW + p] : 0.f) : q[u];
+        }
+      }
+  }
+  float* out = part + (long)blockIdx.x * (KK + 1) * CP;
+#pragma unroll
+  for (int j = 0; j < NT; ++j)
+    if (g * NT + j < KK) out[(g * NT + j) * CP + c] = acc[j];
+  if (g == 0) out[KK * CP + c] = accb;
+}
+
+__global__ __launch_bounds__(256) void bk_corr_final_kernel(const float* __restrict__ part, int nparts, int KK, int cp,
+                                                            int channels, int db_mode, float* __restrict__ dw,
+                                                            float* __restrict__ db) {
+  const int i = blockIdx.x * 256 + threadIdx.x, n = (KK + 1) * cp;
+  if (i >= n) return;
+  float s = 0.f;
+  for (int k = 0; k < nparts; ++k) s += part[(long)k * n + i];
+  const int tap = i / cp, c = i % cp;
+  if (tap < KK) {
+    if (c < channels) dw[c * KK + tap] = s;
+  } else if (db) {
+    if (db_mode == 1 && c < channels) db[c] = s;
+    if (db_mode == 2 && c == 0) db[0] = s;
+  }
+}
+
+static int bk_corr_parts(int B, int H, int W) {
+  const long tiles = (long)B * ((H + BK_TH - 1) / BK_TH) * ((W + BK_TW - 1) / BK_TW);
+  return (int)(tiles < BK_PARTS ? tiles : BK_PARTS);
+}
+
+extern "C" size_t sisr_corrk_y_workspace_bytes(int B, int H, int W, int K, int cp) {
+  if (!bk_dims_ok(B, H, W) || !bk_k_ok(K) || !bk_cp_ok(cp)) return 0;
+  return sizeof(float) * (size_t)bk_corr_parts(B, H, W) * (K * K + 1) * cp;
+}
+
+template <int K>
+static void bk_corr_launch(int cp, int parts, hipStream_t s, const float* P, const float* Q, const float* qmask, float* ws,
+                           int B, int H, int W, int flip, int db_mode) {
+  if (cp == 64)
+    hipLaunchKernelGGL((bk_corr_kernel<K, 64>), dim3(parts), dim3(256), 0, s, P, Q, qmask, ws, B, H, W, flip, db_mode);
+  else
+    hipLaunchKernelGGL((bk_corr_kernel<K, 32>), dim3(parts), dim3(256), 0, s, P, Q, qmask, ws, B, H, W, flip, db_mode);
+}
+
+extern "C" int sisr_corrk_y(const float* P, const float* Q, const float* qmask, float* dw, float* db, int B, int H, int W,
+                            int K, int channels, int cp, int flip_taps, int db_mode, float* workspace, size_t workspace_bytes,
+                            void* stream) {
+  if (!P || !Q || !dw || !workspace || !bk_dims_ok(B, H, W) || channels < 1 || db_mode < 0 || db_mode > 2 ||
+      (db_mode && !db))
+    return SISR_ERR_ARG;
+  if (!bk_k_ok(K) || !bk_cp_ok(cp) || channels > cp) return SISR_ERR_UNSUPPORTED;
+  if (workspace_bytes < sisr_corrk_y_workspace_bytes(B, H, W, K, cp)) return SISR_ERR_ARG;
+  const int parts = bk_corr_parts(B, H, W);
+  hipStream_t s = (hipStream_t)stream;
+  switch (K) {
+    case 1: bk_corr_launch<1>(cp, parts, s, P, Q, qmask, workspace, B, H, W, flip_taps, db_mode); break;
+    case 3: bk_corr_launch<3>(cp, parts, s, P, Q, qmask, workspace, B, H, W, flip_taps, db_mode); break;
+    case 5: bk_corr_launch<5>(cp, parts, s, P, Q, qmask, workspace, B, H, W, flip_taps, db_mode); break;
+    case 7: bk_corr_launch<7>(cp, parts, s, P, Q, qmask, workspace, B, H, W, flip_taps, db_mode); break;
+    default: bk_corr_launch<9>(cp, parts, s, P, Q, qmask, workspace, B, H, W, flip_taps, db_mode); break;
+  }
+  int rc = sisr_check_launch();
+  if (rc) return rc;
+  const int n = (K * K + 1) * cp;
+  hipLaunchKernelGGL(bk_corr_final_kernel, dim3((n + 255) / 256), dim3(256), 0, s, workspace, parts, K * K, cp, channels,
+                     db_mode, dw, db);
+  return sisr_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------ K x K conv, fp32 MFMA
+// Packed weight: [tap][cin_p / 16][cout_p][16]: element (tap, ci, co) at ((tap * cin_p/16 + ci/16) * cout_p + co) * 16 + ci%16.
+__global__ __launch_bounds__(256) void bk_pack_kernel(const float* __restrict__ w, float* __restrict__ fwd,
+                                                      float* __restrict__ dgrad, int KK, int cout, int cin, int cop, int cip) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x, n = (long)KK * cop * cip;
+  if (e >= n) return;
+  const int kk = (int)(e % 16);
+  {  // forward: contraction over the weight's input channels
+    const int co = (int)(e / 16 % cop), cg = (int)(e / 16 / cop % (cip / 16)), tap = (int)(e / 16 / cop / (cip / 16));
+    const int ci = cg * 16 + kk;
+    fwd[e] = (co < cout && ci < cin) ? w[((long)co * cin + ci) * KK + tap] : 0.f;
+  }
+  if (dgrad) {  // input gradient: contraction over the weight's output channels, taps flipped
+    const int ci = (int)(e / 16 % cip), og = (int)(e / 16 / cip % (cop / 16)), tap = (int)(e / 16 / cip / (cop / 16));
+    const int co = og * 16 + kk;
+    dgrad[e] = (co < cout && ci < cin) ? w[((long)co * cin + ci) * KK + (KK - 1 - tap)] : 0.f;
+  }
+}
+
+extern "C" int sisr_pack_convk(const float* w, float* fwd, float* dgrad, int K, int cout, int cin, int cop, int cip,
+                               void* stream) {
+  if (!w || !fwd || cout < 1 || cin < 1) return SISR_ERR_ARG;
+  if (!bk_k_ok(K) || !bk_cp_ok(cop) || !bk_cp_ok(cip) || cout > cop || cin > cip) return SISR_ERR_UNSUPPORTED;
+  const long n = (long)K * K * cop * cip;
+  hipLaunchKernelGGL(bk_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, fwd, dgrad,
+                     K * K, cout, cin, cop, cip);
+  return sisr_check_launch();
+}
+
+// Wave v of the 4 computes rows 2v, 2v+1 of the 8 x 32 pixel tile: MT = 2 M-tiles of 32 pixels x NT N-tiles of 32 channels.
+template <int NT>
+__global__ __launch_bounds__(256) void bk_convk_mfma_kernel(const float* __restrict__ x, const float* __restrict__ in_mask,
+                                                            const float* __restrict__ wp, const float* __restrict__ bias,
+                                                            int nbias, const float* __restrict__ mask, float* __restrict__ y,
+                                                            int H, int W, int K, int cin_p, int relu) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // [LH * LW][BK_XS]
+  constexpr int cout_p = NT * 32;
+  const int p = K / 2, LW = BK_TW + K - 1, LH = BK_TH + K - 1;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, h = lane >> 5, i = lane & 31;
+  const int b = blockIdx.z, h0 = blockIdx.y * BK_TH, w0 = blockIdx.x * BK_TW;
+  f32x16 acc[2][NT];
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
+  const int groups = cin_p / 16;
+  for (int ch = 0; ch < cin_p / 32; ++ch) {
+    __syncthreads();
+    for (int idx = tid; idx < LH * LW * 8; idx += 256) {
+      const int pix = idx >> 3, q = idx & 7;
+      const int hh = h0 + pix / LW - p, ww = w0 + pix % LW - p;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (hh >= 0 && hh < H && ww >= 0 && ww < W) {
+        const long o = (((long)b * H + hh) * W + ww) * cin_p + ch * 32 + q * 4;
+        v = *reinterpret_cast<const f32x4*>(x + o);
+        if (in_mask) {
+          const f32x4 m = *reinterpret_cast<const f32x4*>(in_mask + o);
+          v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
+        }
+      }
+      *reinterpret_cast<f32x4*>(lds + pix * BK_XS + q * 4) = v;
+    }
+    __syncthreads();
+    for (int kh = 0; kh < K; ++kh)
+      for (int kw = 0; kw < K; ++kw) {
+        const int tap = kh * K + kw;
+        f32x4 bf[NT][4], af[2][4];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+          const f32x4* bp =
+              reinterpret_cast<const f32x4*>(wp + (((long)tap * groups + ch * 2 + h) * cout_p + nt * 32 + i) * 16);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) bf[nt][q] = bp[q];
+        }
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+          const f32x4* ap = reinterpret_cast<const f32x4*>(lds + ((wave * 2 + mt + kh) * LW + i + kw) * BK_XS + h * 16);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) af[mt][q] = ap[q];
+        }
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk)
+#pragma unroll
+          for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+              acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[mt][kk >> 2][kk & 3], bf[nt][kk >> 2][kk & 3],
+                                                                 acc[mt][nt], 0, 0, 0);
+      }
+  }
+  // D: column (lane & 31) = output channel, row (r & 3) + 8 (r >> 2) + 4 (lane >> 5) = pixel of the 32-pixel row segment
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt) {
+    const int hh = h0 + wave * 2 + mt;
+    if (hh >= H) continue;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const int co = nt * 32 + i;
+      const float bv = (bias && co < nbias) ? bias[co] : 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int ww = w0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        if (ww >= W) continue;
+        const long o = (((long)b * H + hh) * W + ww) * cout_p + co;
+        float v = acc[mt][nt][r] + bv;
+        if (relu) v = fmaxf(v, 0.f);
+        if (mask) v = mask[o] > 0.f ? v : 0.f;
+        y[o] = v;
+      }
+    }
+  }
+}
+
+static size_t bk_mfma_lds(int K) { return sizeof(float) * (size_t)(BK_TH + K - 1) * (BK_TW + K - 1) * BK_XS; }
+
+extern "C" int sisr_convk_mfma(const float* x, const float* in_mask, const float* packed, const float* bias, int nbias,
+                               const float* mask, float* y, int B, int H, int W, int K, int cin_p, int cout_p, int relu,
+                               void* stream) {
+  if (!x || !packed || !y || !bk_dims_ok(B, H, W) || nbias < 0) return SISR_ERR_ARG;
+  if (!bk_k_ok(K) || !bk_cp_ok(cin_p) || !bk_cp_ok(cout_p) || nbias > cout_p) return SISR_ERR_UNSUPPORTED;
+  if (!sisr_aligned16(x) || !sisr_aligned16(in_mask) || !sisr_aligned16(packed)) return SISR_ERR_ALIGN;
+  const dim3 grid((W + BK_TW - 1) / BK_TW, (H + BK_TH - 1) / BK_TH, B);
+  const size_t lds = bk_mfma_lds(K);  // 9 x 9: 90 KB
+  if (cout_p == 64) {
+    SISR_ALLOW_LDS(bk_convk_mfma_kernel<2>, bk_mfma_lds(BK_MAXK));
+    hipLaunchKernelGGL(bk_convk_mfma_kernel<2>, grid, dim3(256), lds, (hipStream_t)stream, x, in_mask, packed, bias, nbias,
+                       mask, y, H, W, K, cin_p, relu);
+  } else {
+    SISR_ALLOW_LDS(bk_convk_mfma_kernel<1>, bk_mfma_lds(BK_MAXK));
+    hipLaunchKernelGGL(bk_convk_mfma_kernel<1>, grid, dim3(256), lds, (hipStream_t)stream, x, in_mask, packed, bias, nbias,
+                       mask, y, H, W, K, cin_p, relu);
+  }
+  return sisr_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------ its weight gradient
+// Workgroup (tap, 32-channel chunk of Cin, slice s of the B*H image rows): D[co][ci] += sum_pixels dy[pix][co] x[pix + tap][ci],
+// two pixels per MFMA (lane half h takes pixel w0 + h).  The 4 waves take every 4th row of the slice; their tiles are summed
+// in wave order through LDS and written as slice s's partial.
+template <int MT>
+__global__ __launch_bounds__(256) void bk_wgradk_mfma_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                             const float* __restrict__ dymask, float* __restrict__ part,
+                                                             int B, int H, int W, int K, int cip, int S) {
+  __shared__ float red[4][MT][16 * 64];
+  constexpr int cop = MT * 32;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, h = lane >> 5, i = lane & 31;
+  const int tap = blockIdx.x, chunk = blockIdx.y, s = blockIdx.z, p = K / 2, kh = tap / K, kw = tap % K, KK = K * K;
+  const int rows = B * H, per = (rows + S - 1) / S, r_begin = s * per, r_end = min(rows, r_begin + per);
+  f32x16 acc[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
+  for (int R = r_begin + wave; R < r_end; R += 4) {
+    const int b = R / H, hx = R % H + kh - p;
+    if (hx < 0 || hx >= H) continue;  // wave-uniform
+    const float* dyr = dy + (long)R * W * cop;
+    const float* mr = dymask ? dymask + (long)R * W * cop : nullptr;
+    const float* xr = x + ((long)b * H + hx) * W * cip + chunk * 32 + i;
+    for (int wq = 0; wq < W; wq += 16) {  // eight pixel pairs at a time: their loads are in flight together
+      float av[8][MT], bv[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int wd = wq + 2 * u + h, wx = wd + kw - p;
+        const bool okd = wd < W, okx = okd && wx >= 0 && wx < W;
+        const float xv = xr[(long)(okx ? wx : 0) * cip];
+        bv[u] = okx ? xv : 0.f;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+          const long o = (long)(okd ? wd : 0) * cop + mt * 32 + i;
+          float a = dyr[o];
+          if (mr) a = mr[o] > 0.f ? a : 0.f;
+          av[u][mt] = okd ? a : 0.f;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][mt], bv[u], acc[mt], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) red[wave][mt][r * 64 + lane] = acc[mt][r];
+  __syncthreads();
+  float* out = part + (long)s * cop * cip * KK;
+  for (int e = tid; e < MT * 1024; e += 256) {
+    const int mt = e >> 10, r = (e >> 6) & 15, l = e & 63;
+    const float v = ((red[0][mt][e & 1023] + red[1][mt][e & 1023]) + red[2][mt][e & 1023]) + red[3][mt][e & 1023];
+    const int co = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), ci = chunk * 32 + (l & 31);
+    out[((long)co * cip + ci) * KK + tap] = v;
+  }
+}
+
+__global__ __launch_bounds__(256) void bk_wgradk_final_kernel(const float* __restrict__ part, int S, int KK, int cout, int cin,
+                                                              int cop, int cip, float* __restrict__ dw) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x, n = (long)cout * cin * KK;
+  if (e >= n) return;
+  const int tap = (int)(e % KK), ci = (int)(e / KK % cin), co = (int)(e / KK / cin);
+  const long src = ((long)co * cip + ci) * KK + tap, stride = (long)cop * cip * KK;
+  float sum = 0.f;
+  for (int k = 0; k < S; ++k) sum += part[k * stride + src];
+  dw[e] = sum;
+}
+
+// per-channel sum of a (masked) channels-last map: ordered partials per workgroup, then one ordered pass
+template <int CP>
+__global__ __launch_bounds__(256) void bk_colsum_kernel(const float* __restrict__ dy, const float* __restrict__ dymask,
+                                                        long npix, float* __restrict__ part) {
+  constexpr int G = 256 / CP;
+  __shared__ float red[256];
+  const int c = threadIdx.x % CP, g = threadIdx.x / CP;
+  float s = 0.f;
+  for (long pix = (long)blockIdx.x * G + g; pix < npix; pix += (long)gridDim.x * G) {
+    float v = dy[pix * CP + c];
+    if (dymask) v = dymask[pix * CP + c] > 0.f ? v : 0.f;
+    s += v;
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  if (g == 0) {
+    float t = red[c];
+    for (int k = 1; k < G; ++k) t += red[k * CP + c];
+    part[(long)blockIdx.x * CP + c] = t;
+  }
+}
+
+__global__ __launch_bounds__(64) void bk_colsum_final_kernel(const float* __restrict__ part, int nparts, int cp, int cout,
+                                                             float* __restrict__ db) {
+  const int c = threadIdx.x;
+  if (c >= cout) return;
+  float s = 0.f;
+  for (int k = 0; k < nparts; ++k) s += part[(long)k * cp + c];
+  db[c] = s;
+}
+
+static int bk_wgrad_slices(int B, int H, int K, int cip) {
+  const int rows = B * H, blocks = K * K * (cip / 32);
+  int S = 768 / blocks;
+  if (S < 1) S = 1;
+  if (S > 64) S = 64;
+  const int cap = (rows + 3) / 4;
+  return S < cap ? S : cap;
+}
+
+static int bk_colsum_parts(long npix, int cp) {
+  const long n = (npix + 256 / cp - 1) / (256 / cp);
+  return (int)(n < BK_PARTS ? n : BK_PARTS);
+}
+
+extern "C" size_t sisr_wgradk_mfma_workspace_bytes(int B, int H, int W, int K, int cin_p, int cout_p) {
+  if (!bk_dims_ok(B, H, W) || !bk_k_ok(K) || !bk_cp_ok(cin_p) || !bk_cp_ok(cout_p)) return 0;
+  return sizeof(float) * ((size_t)bk_wgrad_slices(B, H, K, cin_p) * cout_p * cin_p * K * K + (size_t)BK_PARTS * cout_p);
+}
+
+extern "C" int sisr_wgradk_mfma(const float* x, const float* dy, const float* dymask, float* dw, float* db, int B, int H,
+                                int W, int K, int cout, int cin, int cop, int cip, float* workspace, size_t workspace_bytes,
+                                void* stream) {
+  if (!x || !dy || !dw || !workspace || !bk_dims_ok(B, H, W) || cout < 1 || cin < 1) return SISR_ERR_ARG;
+  if (!bk_k_ok(K) || !bk_cp_ok(cop) || !bk_cp_ok(cip) || cout > cop || cin > cip) return SISR_ERR_UNSUPPORTED;
+  if (workspace_bytes < sisr_wgradk_mfma_workspace_bytes(B, H, W, K, cip, cop)) return SISR_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const int S = bk_wgrad_slices(B, H, K, cip), KK = K * K;
+  const dim3 grid(KK, cip / 32, S);
+  if (cop == 64)
+    hipLaunchKernelGGL(bk_wgradk_mfma_kernel<2>, grid, dim3(256), 0, s, x, dy, dymask, workspace, B, H, W, K, cip, S);
+  else
+    hipLaunchKernelGGL(bk_wgradk_mfma_kernel<1>, grid, dim3(256), 0, s, x, dy, dymask, workspace, B, H, W, K, cip, S);
+  int rc = sisr_check_launch();
+  if (rc) return rc;
+  const long n = (long)cout * cin * KK;
+  hipLaunchKernelGGL(bk_wgradk_final_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, workspace, S, KK, cout, cin,
+                     cop, cip, dw);
+  rc = sisr_check_launch();
+  if (rc || !db) return rc;
+  float* bpart = workspace + (size_t)S * cop * cip * KK;
+  const long npix = (long)B * H * W;
+  const int parts = bk_colsum_parts(npix, cop);
+  if (cop == 64)
+    hipLaunchKernelGGL(bk_colsum_kernel<64>, dim3(parts), dim3(256), 0, s, dy, dymask, npix, bpart);
+  else
+    hipLaunchKernelGGL(bk_colsum_kernel<32>, dim3(parts), dim3(256), 0, s, dy, dymask, npix, bpart);
+  rc = sisr_check_launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL(bk_colsum_final_kernel, dim3(1), dim3(64), 0, s, bpart, parts, cop, cout, db);
+  return sisr_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------ MSE loss
+#define MSE_BLOCKS 512
+
+__global__ __launch_bounds__(256) void bk_mse_partial_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                             float* __restrict__ grad, float two_inv_n, long n,
+                                                             float* __restrict__ part) {
+  __shared__ float red[256];
+  float s = 0.f;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const float d = a[i] - b[i];
+    s += d * d;
+    if (grad) grad[i] = d * two_inv_n;
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
+__global__ __launch_bounds__(256) void bk_mse_final_kernel(const float* __restrict__ part, int nparts, float inv_n,
+                                                           float* __restrict__ loss) {
+  __shared__ float red[256];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < nparts; i += 256) s += part[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *loss = red[0] * inv_n;
+}
+
+extern "C" size_t sisr_mse_loss_workspace_bytes() { return MSE_BLOCKS * sizeof(float); }
+
+extern "C" int sisr_mse_loss(const float* a, const float* b, long n, float* loss, float* grad, float* workspace,
+                             void* stream) {
+  if (!a || !b || !loss || !workspace || n <= 0) return SISR_ERR_ARG;
+  long blocks = (n + 255) / 256;
+  if (blocks > MSE_BLOCKS) blocks = MSE_BLOCKS;
+  const float inv_n = 1.0f / (float)n;
+  hipLaunchKernelGGL(bk_mse_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, grad,
+                     2.0f * inv_n, n, workspace);
+  int rc = sisr_check_launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL(bk_mse_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, workspace, (int)blocks, inv_n, loss);
+  return sisr_check_launch();
+}

@@ -286,18 +286,44 @@ def read_degradation_metadata(metadata_file, filenames):
     return out, keys
 
 
+def rgb_to_ycbcr(img, y_only=True, max_val=1, im_type='jpg'):
+    """(3, H, W) RGB tensor -> (1, H, W) Y or (3, H, W) YCbCr, BT.601: 'jpg' full range, anything else the 'png' studio
+    range (ref: sr_tools/image_manipulation.py:56-89, :121-157; the same expressions, so the same fp32 roundings)."""
+    if im_type == 'jpg':
+        bias_c = 128. * (max_val / 255)
+        y = (0.299 * img[0, :, :] + 0.587 * img[1, :, :] + 0.114 * img[2, :, :])
+        if y_only:
+            return torch.unsqueeze(y, 0)
+        cb = bias_c + (-0.168736 * img[0, :, :] - 0.331264 * img[1, :, :] + 0.5 * img[2, :, :])
+        cr = bias_c + (0.5 * img[0, :, :] - 0.418688 * img[1, :, :] - 0.081312 * img[2, :, :])
+    else:
+        bias_y = 16. * (max_val / 255)
+        bias_c = 128. * (max_val / 255)
+        y = bias_y + (65.481 * img[0, :, :] + 128.553 * img[1, :, :] + 24.966 * img[2, :, :]) / 255.
+        if y_only:
+            return torch.unsqueeze(y, 0)
+        cb = bias_c + (-37.797 * img[0, :, :] - 74.203 * img[1, :, :] + 112.0 * img[2, :, :]) / 255.
+        cr = bias_c + (112.0 * img[0, :, :] - 93.786 * img[1, :, :] - 18.214 * img[2, :, :]) / 255.
+    return torch.stack([y, cb, cr], 0)
+
+
 class SuperResImages(Dataset):
     def __init__(self, lr_dir=None, hr_dir=None, dataset=None, split=None, custom_split=None, recursive_search=False,
                  input='unmodified', colorspace='rgb', scale=4, degradation_metadata_file=None, metadata=None,
                  random_augments=None, random_crop=None, online_degradations=None, online_degradation_params=None,
-                 **unsupported):
+                 y_only=True, conv_type='jpg', **unsupported):
         super().__init__()
         if split not in ['train', 'eval', 'test', 'all', None]:
             raise RuntimeError('"Split" must be one of: train | eval | test | all | None')
         if input not in ['interp', 'unmodified']:
             raise RuntimeError('"lr_type" must be one of: interp | unmodified')  # ref: data_handler.py:193-194
-        if 'rgb' not in colorspace:
-            raise NotImplementedError('only RGB inputs are in scope (the Y-channel models SRCNN / VDSR are not)')
+        if 'rgb' not in colorspace and colorspace != 'ycbcr':
+            raise NotImplementedError("colorspace must be an RGB one or 'ycbcr' (got %r)" % (colorspace,))
+        if colorspace == 'ycbcr' and online_degradations:
+            raise NotImplementedError("online degradations produce RGB images: colorspace = 'ycbcr' does not go with them")
+        # ref: data_handler.py:392-423: a 'ycbcr' request converts both images right after ToTensor (before flips / crops);
+        # y_only keeps the luminance plane alone, (1, H, W)
+        self.ycbcr, self.y_only, self.conv_type = colorspace == 'ycbcr', y_only, conv_type
         if input == 'interp' and online_degradations:
             raise NotImplementedError("online degradations produce low-resolution images: input = 'interp' (LR images stored "
                                       "at HR size, SPARNet) does not go with them")
@@ -368,10 +394,10 @@ class SuperResImages(Dataset):
                 h, w = lr_im.height * self.scale, lr_im.width * self.scale
             if hr_im.width != w or hr_im.height != h:
                 hr_im = center_crop(hr_im, height=h, width=w)
-            hr_im = to_tensor(hr_im)
+            hr_im = self._colorspace(to_tensor(hr_im))
         else:
             hr_im = np.array(0)
-        lr_im = to_tensor(lr_im)
+        lr_im = self._colorspace(to_tensor(lr_im))
         if self.random_augment is not None:
             lr_im, hr_im = random_flip_rotate(lr_im, hr_im)
         if self.patch_crop is not None:
@@ -379,6 +405,9 @@ class SuperResImages(Dataset):
         return {'lr': lr_im, 'hr': hr_im, 'tag': image_name, 'hr_tag': base_name, 'mask': np.array(0),
                 'halfway_data': np.array(0), 'metadata': metadata, 'metadata_keys': self.metadata_keys,
                 'blur_kernels': np.array(0)}
+
+    def _colorspace(self, im):
+        return rgb_to_ycbcr(im, y_only=self.y_only, im_type=self.conv_type) if self.ycbcr else im
 
     def _degraded_item(self, base_name, index=None):
         """ref: data_handler.py:446-456 + the common tail of __getitem__: blur kernel drawn on the host (np.random), blur +
@@ -424,7 +453,9 @@ def sisr_data_setup(training_sets, eval_sets, batch_size=16, eval_batch_size=1, 
         return SuperResImages(lr_dir=ds['lr'], hr_dir=ds.get('hr'), dataset=ds.get('name'), split=split,
                               custom_split=custom, degradation_metadata_file=meta_file, metadata=ds.get('metadata'),
                               random_crop=ds.get('crop'), random_augments=ds.get('random_augment'),
-                              recursive_search=bool(ds.get('recursive_search')), **extra, **common)
+                              recursive_search=bool(ds.get('recursive_search')),
+                              y_only=split != 'eval',  # ref data_setup.py:75: Y alone for training, YCbCr for validation
+                              **extra, **common)
 
     train = [setup(d, 'train') for d in training_sets.values()]
     val = [setup(d, 'eval') for d in eval_sets.values()]

@@ -537,6 +537,11 @@ try:  # SPARNet / QSPARNet (sparnet.py)
     HANDLERS += [SPARNetHandler, QSPARNetHandler]
 except ImportError:
     pass
+try:  # SRCNN / VDSR (basic.py)
+    from .basic import SRCNNHandler, VDSRHandler
+    HANDLERS += [SRCNNHandler, VDSRHandler]
+except ImportError:
+    pass
 # registry key = class name minus 'Handler', lower-cased (ref: models/__init__.py:26-30)
 available_models = {h.__name__.split('Handler')[0].lower(): h for h in HANDLERS}
 
@@ -608,11 +613,24 @@ class ModelInterface:
 
     def net_run_and_process(self, lr=None, hr=None, **kwargs):
         if 'rgb' not in self.configuration['colorspace']:
-            raise NotImplementedError('Y-channel-only models (SRCNN/VDSR) are out of scope of the HIP path')
+            out_y, loss, timing = self._run_y(lr, hr, **kwargs)
+            return (*self._y_to_images(out_y, lr), loss, timing)
         out_rgb, loss, timing = self.model.run_eval(x=lr, y=hr, **kwargs)
         out_ycbcr = self.colorspace_convert(out_rgb, colorspace='rgb')
         out_rgb = self._standard_image_formatting(out_rgb.numpy())
         return out_rgb, out_ycbcr, loss, timing
+
+    def _run_y(self, lr, hr, **kwargs):
+        """The Y-channel models (SRCNN / VDSR; ref: models/__init__.py:146-151): `lr` is the interpolated image in YCbCr, the
+        net sees its Y channel only, the loss is taken against the reference's Y channel."""
+        f_ref = hr if hr is None else hr[:, 0, :, :].unsqueeze(1)
+        return self.model.run_eval(lr[:, 0, :, :].unsqueeze(1), y=f_ref, **kwargs)
+
+    def _y_to_images(self, out_y, lr):
+        """ref: models/__init__.py:152-154: the net's Y with the input's Cb / Cr -> (RGB, clipped YCbCr)."""
+        out_ycbcr = torch.stack([out_y.cpu().squeeze(1), lr[:, 1, :, :].cpu(), lr[:, 2, :, :].cpu()], 1)
+        out_rgb = self.colorspace_convert(out_ycbcr, colorspace='ycbcr')
+        return out_rgb, self._standard_image_formatting(out_ycbcr.numpy())
 
     def net_run_process_and_measure(self, lr=None, hr=None, metrics=(), max_value=1, **kwargs):
         """net_run_and_process plus per-image image-quality metrics of the output against `hr`, measured where the output
@@ -620,7 +638,14 @@ class ModelInterface:
         -> (rgb, ycbcr, loss, timing, {metric: [one value per image]}).  Measured here: 'SSIM' (Y channels, data_range
         `max_value`); PSNR stays with the callers, on the host."""
         if 'rgb' not in self.configuration['colorspace']:
-            raise NotImplementedError('Y-channel-only models (SRCNN/VDSR) are out of scope of the HIP path')
+            out_y, loss, timing = self._run_y(lr, hr, keep_on_device=True, **kwargs)
+            measured = {}
+            if 'SSIM' in metrics:  # one-channel planes, compared as given (sisr_ssim, channels == 1)
+                if hr is None:
+                    raise RuntimeError('Need a reference to calculate SSIM.')
+                measured['SSIM'] = batch_ssim(out_y.clamp(0, 1), hr[:, :1].to(device=out_y.device).clamp(0, 1),
+                                              max_value=max_value)
+            return (*self._y_to_images(out_y, lr), loss, timing, measured)
         out, loss, timing = self.model.run_eval(x=lr, y=hr, keep_on_device=True, **kwargs)
         measured = {}
         if 'SSIM' in metrics:
@@ -634,6 +659,8 @@ class ModelInterface:
 
     @staticmethod
     def colorspace_convert(image, colorspace='rgb'):
+        if colorspace == 'ycbcr':
+            return metrics.batch_ycbcr_to_rgb(image.numpy())
         if colorspace != 'rgb':
             raise NotImplementedError(colorspace)
         return metrics.batch_rgb_to_ycbcr(image.numpy())

@@ -184,6 +184,19 @@ _SIGS.update({  # image-quality metrics (csrc/metrics.hip)
     "sisr_ssim": (c_int, [P, P, c_int, c_int, c_int, c_int, c_double, P, P, c_size_t, P]),
 })
 
+_SIGS.update({  # SRCNN / VDSR building blocks: K x K convs, the Y-channel ends, MSE loss (csrc/basic.hip)
+    "sisr_convk_y2f": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "sisr_convk_f2y": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "sisr_corrk_y_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "sisr_corrk_y": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    "sisr_pack_convk": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "sisr_convk_mfma": (c_int, [P, P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "sisr_wgradk_mfma_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "sisr_wgradk_mfma": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    "sisr_mse_loss_workspace_bytes": (c_size_t, []),
+    "sisr_mse_loss": (c_int, [P, P, c_long, P, P, P, P]),
+})
+
 
 GM_MAXL = 4
 

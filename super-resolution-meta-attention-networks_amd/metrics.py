@@ -73,6 +73,15 @@ def rgb_to_ycbcr_jpg(img, max_val=1):
     return np.array([y, cb, cr])
 
 
+def ycbcr_to_rgb_jpg(img, max_val=1):
+    """C,H,W YCbCr -> (R, G, B): the inverse of rgb_to_ycbcr_jpg (ref: sr_tools/image_manipulation.py:100-105)."""
+    bias = 128. * (max_val / 255)
+    r = img[0] + 1.402 * img[2] - 1.402 * bias
+    g = img[0] - 0.344136 * img[1] - 0.714136 * img[2] + (0.714136 + 0.344136) * bias
+    b = img[0] + 1.772 * img[1] - 1.772 * bias
+    return np.array([r, g, b])
+
+
 def standard_image_formatting(im, min_value=0, max_value=1):
     return np.clip(np.copy(im), min_value, max_value)
 
@@ -82,6 +91,14 @@ def batch_rgb_to_ycbcr(batch):
     out = standard_image_formatting(np.asarray(batch))
     for i in range(out.shape[0]):
         out[i] = rgb_to_ycbcr_jpg(out[i])
+    return out
+
+
+def batch_ycbcr_to_rgb(batch):
+    """(N,3,H,W) YCbCr in [0,1] (clipped first) -> (N,3,H,W) RGB (ref: models/__init__.py:158-163, colorspace='ycbcr')."""
+    out = standard_image_formatting(np.asarray(batch))
+    for i in range(out.shape[0]):
+        out[i] = ycbcr_to_rgb_jpg(out[i])
     return out
 
 

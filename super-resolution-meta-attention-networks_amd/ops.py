@@ -21,6 +21,8 @@ Operators
   lam / csam / conv3x3_stack / stack_maps           HAN (ref: advanced/HAN_blocks.py, advanced/architectures.py:314-377)
   soca / nonlocal_block / nonlocal_attention        SAN (ref: advanced/SAN_blocks.py, advanced/mpncov.py)
   pixel_shuffle  nn.PixelShuffle on channels-last maps wider than 64 channels (64-wide: fused into the conv's store)
+  conv_y2f / conv_f2y / conv_kxk / mse_loss         SRCNN, VDSR: K x K convs, the Y-channel ends, nn.MSELoss
+                 (ref: basic/architectures.py:6-77, basic/handlers.py:14)
 """
 import os
 
@@ -3257,3 +3259,223 @@ class _L1Loss(Function):
 
 def l1_loss(a, b):
     return _L1Loss.apply(a, b)
+
+
+# ----------------------------------------------------------------------------- SRCNN / VDSR pieces (csrc/basic.hip)
+# K x K convolutions (odd K <= 9, padding K // 2).  Maps between layers are channels-last with 32 or 64 channels (real channels
+# first, the rest zero); the image ends are contiguous (B, 1, H, W).  Every operator with a ReLU applies its own mask to the
+# gradient it receives (on the operand loads of its gradient kernels), so the operators compose freely with conv_chain.
+def _pad_width(c):
+    if c > 64:
+        raise NotImplementedError(f"the K x K kernels take maps of at most 64 channels, got {c}")
+    return 32 if c <= 32 else 64
+
+
+def _check_k(weight):
+    K = weight.shape[2]
+    if weight.shape[3] != K or K % 2 == 0 or K > 9:
+        raise NotImplementedError(f"the K x K kernels take square odd kernels up to 9 x 9, got {tuple(weight.shape[2:])}")
+    return K
+
+
+def _check_map(x, what):
+    if x.shape[1] not in (32, 64):
+        raise NotImplementedError(f"{what}: the input map must be zero-padded to 32 or 64 channels, got {x.shape[1]}")
+    return _cl(x)
+
+
+def _corrk_y(P_, Q, qmask, dw, db, B, H, W, K, channels, cp, flip, db_mode):
+    L = hip.lib()
+    nb = L.sisr_corrk_y_workspace_bytes(B, H, W, K, cp)
+    ws = hip.workspace(Q.device, nb)
+    hip.check(L.sisr_corrk_y(hip.ptr(P_), hip.ptr(Q), hip.ptr(qmask), hip.ptr(dw), hip.ptr(db), B, H, W, K, channels, cp,
+                             int(flip), int(db_mode), hip.ptr(ws), nb, hip.stream()), "sisr_corrk_y")
+
+
+class _ConvY2F(Function):
+    """(B,1,H,W) image -> channels-last map of _pad_width(cout) channels: conv K x K + bias (+ ReLU).  The first layer of a
+    network: it returns no input gradient (ref: basic/architectures.py:45-52 conv_0)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        _fp32_only("conv_y2f")
+        if ctx.needs_input_grad[0]:
+            raise NotImplementedError("conv_y2f is the network-input layer and returns no input gradient")
+        B, one, H, W = x.shape
+        co = weight.shape[0]
+        if one != 1 or weight.shape[1] != 1:
+            raise NotImplementedError("conv_y2f takes a one-channel image and a (cout, 1, K, K) weight")
+        K, cp = _check_k(weight), _pad_width(co)
+        x, w = x.contiguous(), weight.contiguous()
+        y = _empty_cl(B, cp, H, W, x.device)
+        hip.check(hip.lib().sisr_convk_y2f(hip.ptr(x), hip.ptr(w), hip.ptr(bias), None, hip.ptr(y), B, H, W, K, co, cp,
+                                           int(relu), 0, hip.stream()), "sisr_convk_y2f")
+        ctx.save_for_backward(x, y if relu else None, weight)
+        ctx.cfg = (B, H, W, K, co, cp)
+        ctx.bias = bias
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        global IN_BACKWARD
+        IN_BACKWARD = True
+        try:
+            x, y, weight = ctx.saved_tensors
+            B, H, W, K, co, cp = ctx.cfg
+            dy = _cl(dy)
+            dw = _grad_buf(weight)
+            db = _grad_buf(ctx.bias) if ctx.bias is not None else None
+            _corrk_y(x, dy, y, dw, db, B, H, W, K, co, cp, 0, 1 if db is not None else 0)
+            return None, dw, db, None
+        finally:
+            IN_BACKWARD = False
+
+
+def conv_y2f(x, weight, bias=None, relu=False):
+    return _ConvY2F.apply(x, weight, bias, bool(relu))
+
+
+class _ConvF2Y(Function):
+    """Channels-last map (32 or 64 channels) -> (B,1,H,W) image: conv K x K + bias (+ residual image, VDSR's `out + x`;
+    ref: basic/architectures.py:67-77).  Input gradient: sisr_convk_y2f with flipped taps."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual):
+        _fp32_only("conv_f2y")
+        B, cp, H, W = x.shape
+        ci = weight.shape[1]
+        if weight.shape[0] != 1 or ci > cp:
+            raise NotImplementedError("conv_f2y takes a (1, cin, K, K) weight with cin within the map's channels")
+        K = _check_k(weight)
+        x, w = _check_map(x, "conv_f2y"), weight.contiguous()
+        res = residual.contiguous() if residual is not None else None
+        y = torch.empty((B, 1, H, W), device=x.device, dtype=torch.float32)
+        hip.check(hip.lib().sisr_convk_f2y(hip.ptr(x), hip.ptr(w), hip.ptr(bias), hip.ptr(res), hip.ptr(y), B, H, W, K, ci, cp,
+                                           hip.stream()), "sisr_convk_f2y")
+        ctx.save_for_backward(x, weight)
+        ctx.cfg = (B, H, W, K, ci, cp)
+        ctx.bias = bias
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        global IN_BACKWARD
+        IN_BACKWARD = True
+        try:
+            x, weight = ctx.saved_tensors
+            B, H, W, K, ci, cp = ctx.cfg
+            dy = dy.contiguous()
+            dx = dw = db = None
+            if ctx.needs_input_grad[0]:
+                dx = _empty_cl(B, cp, H, W, dy.device)
+                hip.check(hip.lib().sisr_convk_y2f(hip.ptr(dy), hip.ptr(weight.contiguous()), None, None, hip.ptr(dx), B, H, W,
+                                                   K, ci, cp, 0, 1, hip.stream()), "sisr_convk_y2f(dgrad)")
+            want_db = ctx.bias is not None and ctx.needs_input_grad[2]
+            if ctx.needs_input_grad[1] or want_db:  # one launch makes both; a frozen weight's gradient is dropped
+                dwb = _grad_buf(weight) if ctx.needs_input_grad[1] else torch.empty_like(weight)
+                db = _grad_buf(ctx.bias) if want_db else None
+                _corrk_y(dy, x, None, dwb, db, B, H, W, K, ci, cp, 1, 2 if want_db else 0)
+                dw = dwb if ctx.needs_input_grad[1] else None
+            return dx, dw, db, (dy if ctx.needs_input_grad[3] else None)
+        finally:
+            IN_BACKWARD = False
+
+
+def conv_f2y(x, weight, bias=None, residual=None):
+    return _ConvF2Y.apply(x, weight, bias, residual)
+
+
+def pack_convk(weight, need_dgrad=True):
+    """OIHW weight -> (forward packing, input-gradient packing | None) of sisr_convk_mfma, zero-padded to 32 / 64 channels."""
+    co, ci = weight.shape[0], weight.shape[1]
+    K, cop, cip = _check_k(weight), _pad_width(co), _pad_width(ci)
+    n = K * K * cop * cip
+    buf = torch.empty((2 if need_dgrad else 1, n), device=weight.device, dtype=torch.float32)
+    hip.check(hip.lib().sisr_pack_convk(hip.ptr(weight.contiguous()), hip.ptr(buf[0]), hip.ptr(buf[1]) if need_dgrad else None,
+                                        K, co, ci, cop, cip, hip.stream()), "sisr_pack_convk")
+    return buf[0], (buf[1] if need_dgrad else None)
+
+
+def convk_mfma(x, packed, bias, nbias, y, B, H, W, K, cin_p, cout_p, relu=False, mask=None, in_mask=None):
+    hip.check(hip.lib().sisr_convk_mfma(hip.ptr(x), hip.ptr(in_mask), hip.ptr(packed), hip.ptr(bias), int(nbias), hip.ptr(mask),
+                                        hip.ptr(y), B, H, W, K, cin_p, cout_p, int(relu), hip.stream()), "sisr_convk_mfma")
+
+
+class _ConvKxK(Function):
+    """K x K conv + bias (+ ReLU) between channels-last maps of 32 / 64 (padded) channels on the fp32 matrix cores
+    (ref: basic/architectures.py:45-52, the inner layers).  Backward: the input gradient is the same kernel on the flipped /
+    transposed packing; both gradient kernels read dy through the ReLU mask."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        _fp32_only("conv_kxk")
+        B, cip, H, W = x.shape
+        co, ci = weight.shape[0], weight.shape[1]
+        K, cop = _check_k(weight), _pad_width(co)
+        x = _check_map(x, "conv_kxk")
+        if _pad_width(ci) != cip:
+            raise RuntimeError(f"conv_kxk: weight takes {ci} channels, the map has {cip}")
+        pf, pd = pack_convk(weight, need_dgrad=ctx.needs_input_grad[0])
+        y = _empty_cl(B, cop, H, W, x.device)
+        convk_mfma(x, pf, bias, co if bias is not None else 0, y, B, H, W, K, cip, cop, relu=relu)
+        ctx.save_for_backward(x, y if relu else None, weight, pd)
+        ctx.cfg = (B, H, W, K, co, ci, cop, cip)
+        ctx.bias = bias
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        global IN_BACKWARD
+        IN_BACKWARD = True
+        try:
+            x, y, weight, pd = ctx.saved_tensors
+            B, H, W, K, co, ci, cop, cip = ctx.cfg
+            dy = _cl(dy)
+            L = hip.lib()
+            dx = dw = db = None
+            want_db = ctx.bias is not None and ctx.needs_input_grad[2]
+            if ctx.needs_input_grad[1] or want_db:  # one call makes both; a frozen weight's gradient is dropped
+                dwb = _grad_buf(weight) if ctx.needs_input_grad[1] else torch.empty_like(weight)
+                db = _grad_buf(ctx.bias) if want_db else None
+                nb = L.sisr_wgradk_mfma_workspace_bytes(B, H, W, K, cip, cop)
+                ws = hip.workspace(dy.device, nb)
+                hip.check(L.sisr_wgradk_mfma(hip.ptr(x), hip.ptr(dy), hip.ptr(y), hip.ptr(dwb), hip.ptr(db), B, H, W, K, co, ci,
+                                             cop, cip, hip.ptr(ws), nb, hip.stream()), "sisr_wgradk_mfma")
+                dw = dwb if ctx.needs_input_grad[1] else None
+            if ctx.needs_input_grad[0]:
+                dx = _empty_cl(B, cip, H, W, dy.device)
+                convk_mfma(dy, pd, None, 0, dx, B, H, W, K, cop, cip, in_mask=y)
+            return dx, dw, db, None
+        finally:
+            IN_BACKWARD = False
+
+
+def conv_kxk(x, weight, bias=None, relu=False):
+    return _ConvKxK.apply(x, weight, bias, bool(relu))
+
+
+# ----------------------------------------------------------------------------- MSE loss
+class _MSELoss(Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        a, b = a.contiguous(), b.contiguous()
+        if a.shape != b.shape:
+            raise RuntimeError(f"mse_loss shape mismatch {tuple(a.shape)} vs {tuple(b.shape)}")
+        L = hip.lib()
+        pa, pb = hip.ptr(a), hip.ptr(b)  # (refuses CPU tensors before anything touches a device)
+        loss = torch.empty((), device=a.device, dtype=torch.float32)
+        grad = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        ws = hip.workspace(a.device, L.sisr_mse_loss_workspace_bytes())
+        hip.check(L.sisr_mse_loss(pa, pb, a.numel(), hip.ptr(loss), hip.ptr(grad), hip.ptr(ws),
+                                  hip.stream()), "sisr_mse_loss")
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, go):
+        (grad,) = ctx.saved_tensors
+        return grad * go, None
+
+
+def mse_loss(a, b):
+    return _MSELoss.apply(a, b)
