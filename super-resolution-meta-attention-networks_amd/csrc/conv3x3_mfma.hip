@@ -993,7 +993,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_p4_kernel(ConvParams p, in
 //   A fragments: built by the wave itself, straight from the halo.  Lane (n, q) IS the A-operand slot (tile (mb, n), ci piece
 //           4G + q): per step (xr, G) it reads its 4 x 2 halo pieces (rows 2mb + {ra, rb}, columns 2n .. 2n + 3; the halo's
 //           col & 15 key keeps every ds_read_b128 lane group on 16 distinct 16-B bank groups), forms B^T d B in registers (32
-//           adds) and feeds 32 MFMAs (4 xc x 2 nb x 4 e).  Step s + 1 is read and transformed under the MFMAs of step s.
+//           adds, two to a v_pk_add_f32 on the (.xy, .zw) halves of the four ci of a piece: sisr_pk4_add / sisr_pk4_sub, as
+//           are the fold's and the bias add) and feeds 32 MFMAs (4 xc x 2 nb x 4 e).  Step s + 1 is read and transformed under the MFMAs of step s.
 //           No LDS beside the halo and no barrier inside the K loop: two per tile (halo free / next halo visible)
 //   epilogue: p4's arithmetic per output pixel (bias added after the transform), stores and partial sums masked to the
 //           image; GAP / DOT partials in p4's slot layout (one per (2-row strip, 32 columns)).
@@ -1134,15 +1135,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj) {
         const f32x4 da = raw[2 * jj], db = raw[2 * jj + 1];
-        rr[2 * hc + jj] = xr == 0 ? da - db : (xr == 1 ? db + da : (xr == 2 ? da - db : db - da));
+        rr[2 * hc + jj] = xr == 0 ? sisr_pk4_sub(da, db) : (xr == 1 ? sisr_pk4_add(db, da) : (xr == 2 ? sisr_pk4_sub(da, db) : sisr_pk4_sub(db, da)));
       }
     };
     auto cols_step = [&](int s) {
       f32x4* a = av[s & 1];
-      a[0] = rr[0] - rr[2];
-      a[1] = rr[1] + rr[2];
-      a[2] = rr[2] - rr[1];
-      a[3] = rr[1] - rr[3];
+      a[0] = sisr_pk4_sub(rr[0], rr[2]);
+      a[1] = sisr_pk4_add(rr[1], rr[2]);
+      a[2] = sisr_pk4_sub(rr[2], rr[1]);
+      a[3] = sisr_pk4_sub(rr[1], rr[3]);
     };
     read_half(0, 0);
     rows_half(0, 0);
@@ -1193,14 +1194,22 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
       }
       if (G == 3) {
         // ---- fold row xr of A^T M A: T = (m0 + m1 + m2, m1 - m2 - m3); y0 += T (xr 0..2), y1 += T (1), -= T (2, 3)
+        // (the packed adds are inline assembly, whose reads of MFMA results the compiler's hazard handling does not see:
+        // the twelve that do not touch the last-written acc[3] stand first, more than the 11 wait states an 8-pass MFMA
+        // result needs before a vector read)
+        f32x4 t0[2], t1[2];
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) t0[nb] = sisr_pk4_add(sisr_pk4_add(acc[0][nb], acc[1][nb]), acc[2][nb]);
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) t1[nb] = sisr_pk4_sub(acc[1][nb], acc[2][nb]);
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) t1[nb] = sisr_pk4_sub(t1[nb], acc[3][nb]);
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
-          const f32x4 t0 = acc[0][nb] + acc[1][nb] + acc[2][nb];
-          const f32x4 t1 = acc[1][nb] - acc[2][nb] - acc[3][nb];
-          if (xr == 0) { y[nb][0][0] = t0; y[nb][0][1] = t1; }
-          if (xr == 1) { y[nb][0][0] += t0; y[nb][0][1] += t1; y[nb][1][0] = t0; y[nb][1][1] = t1; }
-          if (xr == 2) { y[nb][0][0] += t0; y[nb][0][1] += t1; y[nb][1][0] -= t0; y[nb][1][1] -= t1; }
-          if (xr == 3) { y[nb][1][0] -= t0; y[nb][1][1] -= t1; }
+          if (xr == 0) { y[nb][0][0] = t0[nb]; y[nb][0][1] = t1[nb]; }
+          if (xr == 1 || xr == 2) { y[nb][0][0] = sisr_pk4_add(y[nb][0][0], t0[nb]); y[nb][0][1] = sisr_pk4_add(y[nb][0][1], t1[nb]); }
+          if (xr == 1) { y[nb][1][0] = t0[nb]; y[nb][1][1] = t1[nb]; }
+          if (xr >= 2) { y[nb][1][0] = sisr_pk4_sub(y[nb][1][0], t0[nb]); y[nb][1][1] = sisr_pk4_sub(y[nb][1][1], t1[nb]); }
           // the fold happens here: sunk towards the epilogue it would keep every row's 32 accumulators live instead
 #pragma unroll
           for (int i = 0; i < (xr == 0 ? 1 : 2); ++i) asm volatile("" : "+v"(y[nb][i][0]), "+v"(y[nb][i][1]));
@@ -1237,13 +1246,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
               if (DOT) dt[i][j][r] = sisr_buf_load1(rdt, vo, so);
             }
         float gs = 0.f;
+        const f32x4 bv4 = {bv[nb], bv[nb], bv[nb], bv[nb]};
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int j = 0; j < 2; ++j)
+          for (int j = 0; j < 2; ++j) {
+            const f32x4 yb = sisr_pk4_add(y[nb][i][j], bv4);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              float a = y[nb][i][j][r] + bv[nb];
+              float a = yb[r];
               if (p.relu) a = fmaxf(a, 0.f);
               if (scaled) a *= os;
               if (MASK) a = mk[i][j][r] > 0.f ? a : 0.f;
@@ -1254,6 +1265,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
                 gs = DOT ? __builtin_fmaf(a, dt[i][j][r], gs) : gs + a;
               }
             }
+          }
         gs += __shfl_xor(gs, 16);
         gsum[nb] = gs + __shfl_xor(gs, 32);
       }

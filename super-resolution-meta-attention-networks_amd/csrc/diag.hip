@@ -61,11 +61,15 @@ extern "C" int sisr_diag_mfma_peak(int blocks, int iters, float* out, unsigned l
 // spread over the eight MFMA gaps.  Time per iteration minus the COUNT = 0 time, divided by COUNT = what a filler adds.
 //   1 v_add_f32   2 v_and_b32   3 s_add_u32   4 ds_read_b128   5 global_load_dwordx4 (L2-resident)   6 ds_write_b128
 //   7 global_store_dword   8 v_mov_b32   9 s_nop 0   10 v_pk_add_f32   11 v_lshl_add_u64   12 buffer_load_dwordx4 (saddr form)
-template <int KIND, int COUNT>
+//   13 v_pk_add_f32 neg_lo:[0,1] neg_hi:[0,1]   14 v_pk_add_f32 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]
+//   (the packed subtraction and the half-selecting form of the Winograd transforms)
+// MF = 1: the eight MFMAs are v_mfma_f32_16x16x4_f32 on four accumulators (the Winograd conv's K loop) instead.
+template <int KIND, int COUNT, int MF = 0>
 __global__ __launch_bounds__(256) void mfma_fill_kernel(int iters, float* __restrict__ out, const float* __restrict__ src,
                                                         unsigned long long* __restrict__ clk) {
   __shared__ __attribute__((aligned(16))) float lds[256 * 4 + 64];
   f32x16 acc0 = {0}, acc1 = {0};
+  f32x4 c4[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
   float a = threadIdx.x * 1e-3f, b = 1.0f + blockIdx.x * 1e-6f;
   float f0 = a, f1 = b;
   unsigned u0 = threadIdx.x, u1 = blockIdx.x;
@@ -82,7 +86,8 @@ __global__ __launch_bounds__(256) void mfma_fill_kernel(int iters, float* __rest
   for (int i = 0; i < iters; ++i) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      if (e & 1) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(b, a, acc1, 0, 0, 0);
+      if (MF == 1) c4[e & 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(e & 1 ? b : a, e & 1 ? a : b, c4[e & 3], 0, 0, 0);
+      else if (e & 1) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(b, a, acc1, 0, 0, 0);
       else acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc0, 0, 0, 0);
 #pragma unroll
       for (int k = 0; k < (COUNT + 7 - e) / 8; ++k) {
@@ -98,6 +103,8 @@ __global__ __launch_bounds__(256) void mfma_fill_kernel(int iters, float* __rest
         if (KIND == 10) asm volatile("v_pk_add_f32 %0, %0, %0" : "+v"(w0));
         if (KIND == 11) asm volatile("v_lshl_add_u64 %0, %0, 0, %0" : "+v"(w0));
         if (KIND == 12) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(q0) : "v"(lofs), "s"(src));
+        if (KIND == 13) asm volatile("v_pk_add_f32 %0, %0, %0 neg_lo:[0,1] neg_hi:[0,1]" : "+v"(w0));
+        if (KIND == 14) asm volatile("v_pk_add_f32 %0, %0, %0 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]" : "+v"(w0));
       }
     }
     // memory fillers: let a few iterations' worth stay in flight (issue cost, not latency, is what is measured)
@@ -112,6 +119,8 @@ __global__ __launch_bounds__(256) void mfma_fill_kernel(int iters, float* __rest
   float s = f0 + (float)u0 + (float)s0 + q0[0] + q0[3] + (float)(unsigned)w0;
 #pragma unroll
   for (int r = 0; r < 16; ++r) s += acc0[r] + acc1[r];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) s += c4[r][0] + c4[r][1] + c4[r][2] + c4[r][3];
   *op = s;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     clk[0] = t1 - t0;
@@ -119,14 +128,19 @@ __global__ __launch_bounds__(256) void mfma_fill_kernel(int iters, float* __rest
   }
 }
 
+// kind + 100: the same filler beside v_mfma_f32_16x16x4_f32.  The add kinds (1, 10, 13, 14) also come at the counts of the
+// Winograd kernels' K loops per eight MFMAs: 22 scalar or 11 packed (weight gradient), 10 scalar or 5 packed (conv).
 extern "C" int sisr_diag_mfma_fill(int blocks, int iters, int kind, int count, float* out, const float* src,
                                    unsigned long long* clk, void* stream) {
   if (blocks <= 0 || iters <= 0 || !out || !src || !clk) return SISR_ERR_ARG;
-#define FILL(K, C) \
-  if (kind == K && count == C) { hipLaunchKernelGGL((mfma_fill_kernel<K, C>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, iters, out, src, clk); return sisr_check_launch(); }
-#define FILLK(K) FILL(K, 8) FILL(K, 16) FILL(K, 32)
-  FILL(1, 0)
-  FILLK(1) FILLK(2) FILLK(3) FILLK(4) FILLK(5) FILLK(6) FILLK(7) FILLK(8) FILLK(9) FILLK(10) FILLK(11) FILLK(12)
+#define FILL(K, C, MF) \
+  if (kind == K + 100 * MF && count == C) { hipLaunchKernelGGL((mfma_fill_kernel<K, C, MF>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, iters, out, src, clk); return sisr_check_launch(); }
+#define FILLK(K) FILL(K, 8, 0) FILL(K, 16, 0) FILL(K, 32, 0)
+#define FILLA(K) FILL(K, 5, 0) FILL(K, 10, 0) FILL(K, 11, 0) FILL(K, 22, 0) FILL(K, 5, 1) FILL(K, 8, 1) FILL(K, 10, 1) FILL(K, 11, 1) FILL(K, 16, 1) FILL(K, 22, 1)
+  FILL(1, 0, 0) FILL(1, 0, 1)
+  FILLK(1) FILLK(2) FILLK(3) FILLK(4) FILLK(5) FILLK(6) FILLK(7) FILLK(8) FILLK(9) FILLK(10) FILLK(11) FILLK(12) FILLK(13) FILLK(14)
+  FILLA(1) FILLA(10) FILLA(13) FILLA(14)
+#undef FILLA
 #undef FILLK
 #undef FILL
   return SISR_ERR_UNSUPPORTED;

@@ -42,6 +42,34 @@ __device__ __forceinline__ f32x4 sisr_mul_add4(f32x4 a, f32x4 b, f32x4 c) {
   return p + c;
 }
 
+// Two fp32 adds in one instruction (v_pk_add_f32 on a register pair; (lo, hi) = (.x, .y)).  Beside the fp32 MFMA every
+// vector instruction costs its full issue time, a packed one about as much as a scalar one (tools/mfma_fill.py --winograd),
+// and the Winograd transforms are nothing but adds.  hipcc keeps a packed add only where nobody reads the halves one by
+// one -- MFMA operands are read exactly so -- and never a packed subtraction; hence inline assembly.  Each half is the
+// IEEE add of the scalar form: a - b is a + (-b), and the source modifiers are exact.
+// The compiler's hazard handling does not look inside: keep the result two instructions away from an MFMA that reads it
+// as A / B, and a read of an MFMA result behind that MFMA's wait states (8-pass: 11, 16-pass: 19).
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 sisr_pk_add(f32x2 a, f32x2 b) {  // (a.x + b.x, a.y + b.y)
+  f32x2 r;
+  asm volatile("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ f32x2 sisr_pk_sub(f32x2 a, f32x2 b) {  // (a.x - b.x, a.y - b.y)
+  f32x2 r;
+  asm volatile("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+// ... and the f32x4 sum / difference as two of them, on (.xy, .zw)
+__device__ __forceinline__ f32x4 sisr_pk4_add(f32x4 a, f32x4 b) {
+  const f32x2 lo = sisr_pk_add(a.xy, b.xy), hi = sisr_pk_add(a.zw, b.zw);
+  return (f32x4){lo.x, lo.y, hi.x, hi.y};
+}
+__device__ __forceinline__ f32x4 sisr_pk4_sub(f32x4 a, f32x4 b) {
+  const f32x2 lo = sisr_pk_sub(a.xy, b.xy), hi = sisr_pk_sub(a.zw, b.zw);
+  return (f32x4){lo.x, lo.y, hi.x, hi.y};
+}
+
 // Buffer addressing.  Beside the fp32 MFMA stream a vector-memory instruction with a 64-bit per-lane address
 // (`global_load_dwordx4 v, v[a:a+1], off`) costs its SIMD 30-40 cycles, and every VALU instruction that builds such an
 // address ~4.5 more; the same access as SGPR resource + 32-bit lane offset + SGPR offset (`buffer_load_dwordx4 v, voff,

@@ -495,12 +495,13 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_full_geo_kernel(WgradPara
 //   wave w = (ci half w >> 1, co half w & 1): 16 persistent 32 x 32 accumulators (256 registers, one per xi), K index
 //         (lane >> 5) = block parity, one wave per SIMD.  K-step ks (16 per tile) covers blocks 2 ks and 2 ks + 1: lane
 //         (i, kk) reads the raw 4 x 4 patch of block 2 ks + kk, channel ci half * 32 + i, and the raw 2 x 2 dY' block of
-//         channel co half * 32 + i (20 ds_read_b32, 32 consecutive floats per 32-lane half: no bank conflict), forms its 16
-//         V and 16 M values itself (32 + 12 adds, rows first, then columns) and issues 16 v_mfma_f32_32x32x2_f32, one per
-//         xi.  Per accumulator the K order is ks ascending with block 2 ks + kk in lane slot kk, as when V and M were
-//         staged through LDS chunks, so the sums are the same bit for bit.
+//         channel co half * 32 + i (10 ds_read2st64_b32, 32 consecutive floats per 32-lane half: no bank conflict), forms
+//         its 16 V and 16 M values itself (32 + 12 adds, rows first, then columns, as 22 v_pk_add_f32 on the register pairs
+//         the reads return) and issues 16 v_mfma_f32_32x32x2_f32, one per xi.  Per accumulator the K order is ks ascending
+//         with block 2 ks + kk in lane slot kk, as when V and M were staged through LDS chunks, so the sums are the same bit
+//         for bit.
 //   budget per tile and SIMD: 16 x 16 MFMAs = 16.4 K cycles (direct form on the same pixels: 36.9 K); the reads and adds of
-//         step ks + 1 sit between step ks's MFMAs (sched_group_barrier), two barriers per tile around the commit
+//         step ks + 1 stand between step ks's MFMAs (source order, fenced), two barriers per tile around the commit
 //   epilogue: per lane the 16 dU registers of an element are folded to the nine taps (dg = G^T dU G, coefficients
 //         +-1 and 1/2) and stored as the dense kernel's quadrant slab; bias slabs and the second stage are unchanged.
 #define W4_TH 4
@@ -508,6 +509,23 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_full_geo_kernel(WgradPara
 #define W4G_X (W4_HH * WH_W * 64)  // floats
 #define W4G_Y (W4_TH * WT_W * 64)
 #define W4G_LDS ((W4G_X + W4G_Y) * 4)  // bytes: 84992
+
+// The half-selecting forms of the packed add (sisr_common.h) that the Winograd weight gradient's column transforms take
+__device__ __forceinline__ f32x2 pk_add_nl(f32x2 a, f32x2 b) {  // (a.x - b.x, a.y + b.x)
+  f32x2 r;
+  asm volatile("v_pk_add_f32 %0, %1, %2 op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ f32x2 pk_hh_sub(f32x2 a, f32x2 b) {  // (a.y - b.x, a.y - b.y)
+  f32x2 r;
+  asm volatile("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ f32x2 pk_h_pm_l(f32x2 a) {  // (a.y + a.x, a.y - a.x)
+  f32x2 r;
+  asm volatile("v_pk_add_f32 %0, %1, %1 op_sel:[1,0] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a));
+  return r;
+}
 
 __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -544,6 +562,9 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
     f32x4 y[W4_TH][2];
   };
   Stage st;
+  // staging thread (c8, pcol): channels [4 c8, 4 c8 + 4) and [32 + 4 c8, 32 + 4 c8 + 4) of pixel column pcol, so that the
+  // eight lanes of a pixel write 128 contiguous bytes with each ds_write_b128 (8 channels per lane would be 16 B at a
+  // 32-B stride: a two-way bank conflict)
   const int c8 = tid & 7, pcol = tid >> 3;
   const int eidx = tid % 96, er = eidx >> 4, eside = (eidx >> 3) & 1, ec8 = eidx & 7;  // edge columns: 6 x 2 x 8 items
   auto decode = [&](int tile, int& b, int& h0, int& w0) {
@@ -558,25 +579,25 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
     decode(tile, b, h0, w0);
     const sisr_rsrc_t rx = sisr_rsrc(p.x + (long)b * p.xv.sB + p.xv.chunk(cc));
     const sisr_rsrc_t ry = sisr_rsrc(p.dy + (long)b * p.yv.sB + p.yv.chunk(cq));
-    const unsigned vx = (unsigned)(min(w0 + pcol, W - 1) * (int)p.xv.sW + c8 * 8) * 4u;
-    const unsigned vy = (unsigned)(min(w0 + pcol, W - 1) * (int)p.yv.sW + c8 * 8) * 4u;
+    const unsigned vx = (unsigned)(min(w0 + pcol, W - 1) * (int)p.xv.sW + c8 * 4) * 4u;
+    const unsigned vy = (unsigned)(min(w0 + pcol, W - 1) * (int)p.yv.sW + c8 * 4) * 4u;
 #pragma unroll
     for (int r = 0; r < W4_HH; ++r) {
       const unsigned so = (unsigned)(min(max(h0 - 1 + r, 0), H - 1) * (int)p.xv.sH) * 4u;  // scalar
       st.x[r][0] = sisr_buf_load4(rx, vx, so);
-      st.x[r][1] = sisr_buf_load4(rx, vx + 16u, so);
+      st.x[r][1] = sisr_buf_load4(rx, vx + 128u, so);
     }
     {
       const int gwe = min(max(eside ? w0 + WT_W : w0 - 1, 0), W - 1);
-      const unsigned ve = (unsigned)(min(max(h0 - 1 + er, 0), H - 1) * (int)p.xv.sH + gwe * (int)p.xv.sW + ec8 * 8) * 4u;
+      const unsigned ve = (unsigned)(min(max(h0 - 1 + er, 0), H - 1) * (int)p.xv.sH + gwe * (int)p.xv.sW + ec8 * 4) * 4u;
       st.xe[0] = sisr_buf_load4(rx, ve, 0u);
-      st.xe[1] = sisr_buf_load4(rx, ve + 16u, 0u);
+      st.xe[1] = sisr_buf_load4(rx, ve + 128u, 0u);
     }
 #pragma unroll
     for (int r = 0; r < W4_TH; ++r) {
       const unsigned so = (unsigned)(min(h0 + r, H - 1) * (int)p.yv.sH) * 4u;  // scalar
       st.y[r][0] = sisr_buf_load4(ry, vy, so);
-      st.y[r][1] = sisr_buf_load4(ry, vy + 16u, so);
+      st.y[r][1] = sisr_buf_load4(ry, vy + 128u, so);
     }
   };
   auto commit = [&](int tile) {
@@ -597,28 +618,28 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
       st.xe[0] = sisr_keep_if(st.xe[0], oke);
       st.xe[1] = sisr_keep_if(st.xe[1], oke);
     }
-    float* lx = ldx + (pcol + 1) * 64 + c8 * 8;
+    float* lx = ldx + (pcol + 1) * 64 + c8 * 4;
 #pragma unroll
     for (int r = 0; r < W4_HH; ++r) {
       *reinterpret_cast<f32x4*>(lx + r * (WH_W * 64)) = st.x[r][0];
-      *reinterpret_cast<f32x4*>(lx + r * (WH_W * 64) + 4) = st.x[r][1];
+      *reinterpret_cast<f32x4*>(lx + r * (WH_W * 64) + 32) = st.x[r][1];
     }
     if (tid < 96) {
-      float* le = ldx + (er * WH_W + (eside ? WH_W - 1 : 0)) * 64 + ec8 * 8;
+      float* le = ldx + (er * WH_W + (eside ? WH_W - 1 : 0)) * 64 + ec8 * 4;
       *reinterpret_cast<f32x4*>(le) = st.xe[0];
-      *reinterpret_cast<f32x4*>(le + 4) = st.xe[1];
+      *reinterpret_cast<f32x4*>(le + 32) = st.xe[1];
     }
     if (affine) {
       f32x4 s4a = {1.f, 1.f, 1.f, 1.f}, s4b = s4a, t4a = {0.f, 0.f, 0.f, 0.f}, t4b = t4a;
       if (p.dy_scale) {
-        const float* sp = p.dy_scale + (long)b * Cout + cq * 64 + c8 * 8;
+        const float* sp = p.dy_scale + (long)b * Cout + cq * 64 + c8 * 4;
         s4a = *reinterpret_cast<const f32x4*>(sp);
-        s4b = *reinterpret_cast<const f32x4*>(sp + 4);
+        s4b = *reinterpret_cast<const f32x4*>(sp + 32);
       }
       if (p.dy_shift) {
-        const float* tp = p.dy_shift + (long)b * Cout + cq * 64 + c8 * 8;
+        const float* tp = p.dy_shift + (long)b * Cout + cq * 64 + c8 * 4;
         t4a = *reinterpret_cast<const f32x4*>(tp);
-        t4b = *reinterpret_cast<const f32x4*>(tp + 4);
+        t4b = *reinterpret_cast<const f32x4*>(tp + 32);
       }
 #pragma unroll
       for (int r = 0; r < W4_TH; ++r) {
@@ -634,11 +655,11 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
         st.y[r][1] = sisr_keep_if(st.y[r][1], ok);
       }
     }
-    float* ly = ldy + pcol * 64 + c8 * 8;
+    float* ly = ldy + pcol * 64 + c8 * 4;
 #pragma unroll
     for (int r = 0; r < W4_TH; ++r) {
       *reinterpret_cast<f32x4*>(ly + r * (WT_W * 64)) = st.y[r][0];
-      *reinterpret_cast<f32x4*>(ly + r * (WT_W * 64) + 4) = st.y[r][1];
+      *reinterpret_cast<f32x4*>(ly + r * (WT_W * 64) + 32) = st.y[r][1];
     }
     if (do_bias) {
 #pragma unroll
@@ -650,119 +671,135 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
   };
 
   // K-step ks: this lane's block 2 ks + kk = (row ks >> 3, column 2 (ks & 7) + kk); raw 4 x 4 patch of its ci channel and
-  // raw 2 x 2 dY' block of its co channel (the lane base carries kk and the channel, the rest is a constant per step)
+  // raw 2 x 2 dY' block of its co channel (the lane base carries kk and the channel, the rest is a constant per step).
+  // Columns (j, j + 1) of a row are one ds_read2st64_b32, i.e. one register pair: d[r][c] = (d[r][2c], d[r][2c + 1]).
   const float* const xl = ldx + kk * (2 * 64) + cih * 32 + i;
   const float* const yl = ldy + kk * (2 * 64) + coh * 32 + i;
   struct Raw {
-    float d[4][4], y[2][2];
+    f32x2 d[4][2], y[2];
   };
   auto fetch = [&](int ks, Raw& rw) {
     const int br = ks >> 3, bc = ks & 7;
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
+    for (int c = 0; c < 2; ++c)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) rw.d[r][j] = xl[((2 * br + r) * WH_W + 4 * bc + j) * 64];
+      for (int r = 0; r < 4; ++r) {
+        const float* q = xl + ((2 * br + r) * WH_W + 4 * bc + 2 * c) * 64;
+        rw.d[r][c] = (f32x2){q[0], q[64]};
+      }
 #pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) rw.y[r][j] = yl[((2 * br + r) * WT_W + 4 * bc + j) * 64];
+    for (int r = 0; r < 2; ++r) {
+      const float* q = yl + ((2 * br + r) * WT_W + 4 * bc) * 64;
+      rw.y[r] = (f32x2){q[0], q[64]};
+    }
   };
   // V = B^T d B (rows 0: d0 - d2, 1: d1 + d2, 2: d2 - d1, 3: d1 - d3, then the same over columns) and M = A dY' A^T with
-  // A's last row negated (rows 0: y0, 1: y0 + y1, 2: y0 - y1, 3: y1, then over columns); index xi = xr * 4 + xc
-  auto transform = [&](const Raw& rw, float (&V)[16], float (&M)[16]) {
-    float rr[4][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      rr[0][j] = rw.d[0][j] - rw.d[2][j];
-      rr[1][j] = rw.d[1][j] + rw.d[2][j];
-      rr[2][j] = rw.d[2][j] - rw.d[1][j];
-      rr[3][j] = rw.d[1][j] - rw.d[3][j];
+  // A's last row negated (rows 0: y0, 1: y0 + y1, 2: y0 - y1, 3: y1, then over columns); index xi = xr * 4 + xc.
+  // The adds are issued two floats at a time (v_pk_add_f32: beside the fp32 MFMA every vector instruction costs its full
+  // issue time, a packed one no more than a scalar one), 22 instructions for the 44 adds of a step:
+  //   k  0 ..  7  rows of V on the column pairs (0, 1) and (2, 3)
+  //   k  8 .. 15  per row xr: va = (V0, V1) = (r0 - r2, r1 + r2) and vb = (-V2, V3) = (r1 - r2, r1 - r3)
+  //   k 16 .. 17  rows 1 and 2 of M on the pair (0, 1); rows 0 and 3 are the raw registers
+  //   k 18 .. 21  per row xr: mc = (M1, -M2) = (y1 + y0, y1 - y0); M0 and M3 are the row's own registers
+  // Column 2 of V and of M are both held NEGATED: b - a is -(a - b) to the bit (but for the sign of a zero, which no
+  // product or sum downstream can tell), so (-V2)(-M2) is the same product and every other value is the same add.
+  struct Ops {
+    f32x2 va[4], vb[4], ry[4], mc[4];
+  };
+  f32x2 rr[4][2];
+  auto transform_op = [&](int k, const Raw& rw, Ops& o) {
+    if (k < 8) {
+      const int c = k >> 2, r = k & 3;
+      rr[r][c] = r == 0 ? sisr_pk_sub(rw.d[0][c], rw.d[2][c]) : r == 1 ? sisr_pk_add(rw.d[1][c], rw.d[2][c])
+               : r == 2 ? sisr_pk_sub(rw.d[2][c], rw.d[1][c]) : sisr_pk_sub(rw.d[1][c], rw.d[3][c]);
+    } else if (k < 16) {
+      const int xr = (k - 8) >> 1;
+      if (k & 1) o.vb[xr] = pk_hh_sub(rr[xr][0], rr[xr][1]);
+      else o.va[xr] = pk_add_nl(rr[xr][0], rr[xr][1]);
+    } else if (k == 16) {
+      o.ry[0] = rw.y[0];
+      o.ry[3] = rw.y[1];
+      o.ry[1] = sisr_pk_add(rw.y[0], rw.y[1]);
+    } else if (k == 17) {
+      o.ry[2] = sisr_pk_sub(rw.y[0], rw.y[1]);
+    } else {
+      o.mc[k - 18] = pk_h_pm_l(o.ry[k - 18]);
     }
-#pragma unroll
-    for (int xr = 0; xr < 4; ++xr) {
-      V[xr * 4 + 0] = rr[xr][0] - rr[xr][2];
-      V[xr * 4 + 1] = rr[xr][1] + rr[xr][2];
-      V[xr * 4 + 2] = rr[xr][2] - rr[xr][1];
-      V[xr * 4 + 3] = rr[xr][1] - rr[xr][3];
-    }
-    float ry[4][2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      ry[0][j] = rw.y[0][j];
-      ry[1][j] = rw.y[0][j] + rw.y[1][j];
-      ry[2][j] = rw.y[0][j] - rw.y[1][j];
-      ry[3][j] = rw.y[1][j];
-    }
-#pragma unroll
-    for (int xr = 0; xr < 4; ++xr) {
-      M[xr * 4 + 0] = ry[xr][0];
-      M[xr * 4 + 1] = ry[xr][0] + ry[xr][1];
-      M[xr * 4 + 2] = ry[xr][0] - ry[xr][1];
-      M[xr * 4 + 3] = ry[xr][1];
-    }
+  };
+  auto mfma = [&](int t, const Ops& o) {
+    const int xr = t >> 2, xc = t & 3;
+    const float a = xc == 0 ? o.va[xr].x : xc == 1 ? o.va[xr].y : xc == 2 ? o.vb[xr].x : o.vb[xr].y;
+    const float b = xc == 0 ? o.ry[xr].x : xc == 1 ? o.mc[xr].x : xc == 2 ? o.mc[xr].y : o.ry[xr].y;
+    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[t], 0, 0, 0);
   };
 
   // ---- per tile 16 K-steps of two blocks, 16 MFMAs each (one per transform point).  Step ks + 1's raw values are
-  // requested behind step ks's first MFMAs and transformed between the others, so V / M alternate between two register
-  // sets.  Once step 15's values are read no wave needs the raw image: the next tile is committed in front of step 15's
-  // MFMAs and its step 0 is fetched and transformed between them (read, unused, from the stale image after the last tile).
-  float V[2][16], M[2][16];
-  auto step_order = [&]() {  // reads behind the first two MFMAs, two MFMAs for them to land, then the 44 adds four to a gap
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 5, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-#pragma unroll
-    for (int t = 4; t < 15; ++t) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-  };
+  // requested behind step ks's first MFMAs and transformed between the others, so the operands alternate between two
+  // register sets.  The packed adds are inline assembly, which the scheduler's instruction groups do not count: reads and
+  // adds stand in source order between the MFMAs, every group fenced by a scheduling barrier.  An add and the MFMA that
+  // reads its result are always at least one MFMA apart.  Once step 15's values are read no wave needs the raw image:
+  // the next tile is committed in front of step 15's MFMAs and its step 0 is fetched and transformed between them (read,
+  // unused, from the stale image after the last tile).
+  Ops ops[2];
   if (t_begin < t_end) {
     issue(t_begin);
     commit(t_begin);
     __syncthreads();
     Raw rw;
     fetch(0, rw);
-    transform(rw, V[0], M[0]);
+#pragma unroll
+    for (int k = 0; k < 22; ++k) transform_op(k, rw, ops[0]);
   }
   for (int tile = t_begin; tile < t_end; tile += t_step) {
     const bool has_next = tile + t_step < t_end;  // uniform
     if (has_next) issue(tile + t_step);
 #pragma unroll
-    for (int ks = 0; ks < 15; ++ks) {
+    for (int ks = 0; ks < 15; ++ks) {  // reads behind the first MFMA, three MFMAs for them to land, then two adds to a gap
       const int cur = ks & 1, nxt = cur ^ 1;
       Raw rw;
+      __builtin_amdgcn_sched_barrier(0);
+      mfma(0, ops[cur]);
+      __builtin_amdgcn_sched_barrier(0);
       fetch(ks + 1, rw);
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int t = 0; t < 16; ++t)
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(V[cur][t], M[cur][t], acc[t], 0, 0, 0);
-      transform(rw, V[nxt], M[nxt]);
-      step_order();
+      for (int t = 1; t < 4; ++t) mfma(t, ops[cur]);
+#pragma unroll
+      for (int t = 4; t < 15; ++t) {
+        __builtin_amdgcn_sched_barrier(0);
+        mfma(t, ops[cur]);
+        __builtin_amdgcn_sched_barrier(0);
+        transform_op(2 * (t - 4), rw, ops[nxt]);
+        transform_op(2 * (t - 4) + 1, rw, ops[nxt]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      mfma(15, ops[cur]);
+      __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();  // no wave reads the raw image again
     if (has_next) commit(tile + t_step);
 #pragma unroll
-    for (int t = 0; t < 8; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(V[1][t], M[1][t], acc[t], 0, 0, 0);
+    for (int t = 0; t < 8; ++t) mfma(t, ops[1]);
     __builtin_amdgcn_sched_barrier(0);  // the commit's LDS writes drain under those eight MFMAs
     __syncthreads();  // the next raw image is committed
     {
       Raw rw;
+      mfma(8, ops[1]);
+      __builtin_amdgcn_sched_barrier(0);
       fetch(0, rw);
+      __builtin_amdgcn_sched_barrier(0);
+      mfma(9, ops[1]);
+      mfma(10, ops[1]);
 #pragma unroll
-      for (int t = 8; t < 16; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(V[1][t], M[1][t], acc[t], 0, 0, 0);
-      transform(rw, V[0], M[0]);
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 10, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      for (int t = 11; t < 16; ++t) {  // 22 adds in five gaps: 5, 5, 4, 4, 4; the last MFMA behind the last add
+        const int k0 = t < 13 ? 5 * (t - 11) : 10 + 4 * (t - 13), k1 = t < 13 ? k0 + 5 : k0 + 4;
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int t = 0; t < 5; ++t) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 9, 0);
+        for (int k = k0; k < k1; ++k) transform_op(k, rw, ops[0]);
+        __builtin_amdgcn_sched_barrier(0);
+        mfma(t, ops[1]);
       }
+      __builtin_amdgcn_sched_barrier(0);
     }
   }
 
@@ -797,8 +834,8 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
     *reinterpret_cast<f32x4*>(red + tid * 8) = bsa;
     *reinterpret_cast<f32x4*>(red + tid * 8 + 4) = bsb;
     __syncthreads();
-    if (tid < 64) {  // channel tid = c8 * 8 + e lives in the threads with (tid & 7) == c8
-      const int cc8 = tid >> 3, e = tid & 7;
+    if (tid < 64) {  // channel tid = 32 (e >> 2) + 4 c8 + (e & 3) lives in the threads with (tid & 7) == c8, as their value e
+      const int cc8 = (tid & 31) >> 2, e = (tid & 3) + 4 * (tid >> 5);
       float s = 0.f;
       for (int k = 0; k < 32; ++k) s += red[(k * 8 + cc8) * 8 + e];
       p.bias_slabs[((long)blockIdx.x * p.cout_chunks + cq) * 64 + tid] = s;

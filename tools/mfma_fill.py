@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Diagnostic: what one more instruction of a given kind costs next to the fp32 MFMA stream (diagnostic library).
-Per kind: added shader cycles per filler instruction and SIMD, at 1 and 3 waves per SIMD."""
+Per kind: added shader cycles per filler instruction and SIMD, at 1 to 3 waves per SIMD.
+  --winograd   only the adds of the Winograd kernels at their own densities: scalar and packed (plain, negated, half-selecting)
+               per 8 v_mfma_f32_32x32x2_f32 at one wave per SIMD (weight gradient: 22 scalar / 11 packed) and per 8
+               v_mfma_f32_16x16x4_f32 at two (conv: 10 scalar / 5 packed)"""
 import json
 import os
 import sys
@@ -15,7 +18,8 @@ L = hip.lib()
 dev = torch.device("cuda:0")
 KINDS = {1: "v_add_f32", 2: "v_and_b32", 3: "s_add_u32", 4: "ds_read_b128", 5: "global_load_dwordx4 (vaddr)", 6: "ds_write_b128",
          7: "global_store_dword", 8: "v_mov_b32", 9: "s_nop", 10: "v_pk_add_f32", 11: "v_lshl_add_u64",
-         12: "global_load_dwordx4 (saddr)"}
+         12: "global_load_dwordx4 (saddr)", 13: "v_pk_add_f32 neg_lo neg_hi", 14: "v_pk_add_f32 op_sel neg_lo neg_hi"}
+MFMAS = {0: "v_mfma_f32_32x32x2_f32", 1: "v_mfma_f32_16x16x4_f32"}
 src = torch.zeros(1 << 16, device=dev)
 iters = 4000
 
@@ -36,6 +40,17 @@ def run(wps, kind, count):
     # whole-launch time -> shader cycles one SIMD spends per loop iteration of ALL its waves
     return e0.elapsed_time(e1) * 1e6 * ghz / iters, ghz
 
+
+if "--winograd" in sys.argv[1:]:
+    for mf, wps, scalar, packed in ((0, 1, 22, 11), (0, 2, 22, 11), (1, 1, 10, 5), (1, 2, 10, 5), (1, 2, 16, 8)):
+        base, ghz = run(wps, 1 + 100 * mf, 0)
+        print(json.dumps({"mfma": MFMAS[mf], "waves_per_simd": wps, "kind": "none", "simd_cycles_per_iter": base, "GHz": ghz}), flush=True)
+        for kind, count in ((1, scalar), (10, packed), (13, packed), (14, packed), (10, scalar)):
+            cyc, _ = run(wps, kind + 100 * mf, count)
+            print(json.dumps({"mfma": MFMAS[mf], "waves_per_simd": wps, "kind": KINDS[kind], "per_8_mfma": count,
+                              "simd_cycles_per_iter": round(cyc, 1), "added_simd_cycles_per_filler": round((cyc - base) / (wps * count), 2)}),
+                  flush=True)
+    sys.exit(0)
 
 for wps in (1, 2, 3):
     base, ghz = run(wps, 1, 0)
