@@ -63,6 +63,8 @@ extern "C" int sisr_diag_mfma_peak(int blocks, int iters, float* out, unsigned l
 //   7 global_store_dword   8 v_mov_b32   9 s_nop 0   10 v_pk_add_f32   11 v_lshl_add_u64   12 buffer_load_dwordx4 (saddr form)
 //   13 v_pk_add_f32 neg_lo:[0,1] neg_hi:[0,1]   14 v_pk_add_f32 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]
 //   (the packed subtraction and the half-selecting form of the Winograd transforms)
+//   15 v_pk_fma_f32 (the row step of the weight gradient's one-row-per-wave map: d_a + s * d_b, s = +-1 in a register pair)
+//   16 ds_read2st64_b32 (its raw reads: two floats 64 apart per lane)
 // MF = 1: the eight MFMAs are v_mfma_f32_16x16x4_f32 on four accumulators (the Winograd conv's K loop) instead.
 template <int KIND, int COUNT, int MF = 0>
 __global__ __launch_bounds__(256) void mfma_fill_kernel(int iters, float* __restrict__ out, const float* __restrict__ src,
@@ -77,6 +79,8 @@ __global__ __launch_bounds__(256) void mfma_fill_kernel(int iters, float* __rest
   f32x4 q0 = {0.f, 0.f, 0.f, 0.f};
   unsigned long long w0 = threadIdx.x;
   const unsigned lofs = threadIdx.x * 16;
+  const unsigned lofs4 = threadIdx.x * 4;
+  unsigned long long w1 = 0;
   const float* gp = src + threadIdx.x * 4;
   float* op = out + (long)blockIdx.x * 256 + threadIdx.x;
   lds[threadIdx.x] = a;
@@ -105,10 +109,12 @@ __global__ __launch_bounds__(256) void mfma_fill_kernel(int iters, float* __rest
         if (KIND == 12) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(q0) : "v"(lofs), "s"(src));
         if (KIND == 13) asm volatile("v_pk_add_f32 %0, %0, %0 neg_lo:[0,1] neg_hi:[0,1]" : "+v"(w0));
         if (KIND == 14) asm volatile("v_pk_add_f32 %0, %0, %0 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]" : "+v"(w0));
+        if (KIND == 15) asm volatile("v_pk_fma_f32 %0, %0, %0, %0" : "+v"(w0));
+        if (KIND == 16) asm volatile("ds_read2st64_b32 %0, %1 offset1:1" : "=v"(w1) : "v"(lofs4));
       }
     }
     // memory fillers: let a few iterations' worth stay in flight (issue cost, not latency, is what is measured)
-    if ((KIND == 4 || KIND == 6) && (i & 3) == 3) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if ((KIND == 4 || KIND == 6 || KIND == 16) && (i & 3) == 3) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if ((KIND == 5 || KIND == 7 || KIND == 12) && (i & 3) == 3 && COUNT <= 8) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if ((KIND == 5 || KIND == 7 || KIND == 12) && (i & 1) == 1 && COUNT == 16) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if ((KIND == 5 || KIND == 7 || KIND == 12) && COUNT == 32) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -116,7 +122,7 @@ __global__ __launch_bounds__(256) void mfma_fill_kernel(int iters, float* __rest
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   const unsigned long long t1 = __builtin_amdgcn_s_memtime();
   const unsigned long long r1 = __builtin_amdgcn_s_memrealtime();
-  float s = f0 + (float)u0 + (float)s0 + q0[0] + q0[3] + (float)(unsigned)w0;
+  float s = f0 + (float)u0 + (float)s0 + q0[0] + q0[3] + (float)(unsigned)w0 + (float)(unsigned)w1;
 #pragma unroll
   for (int r = 0; r < 16; ++r) s += acc0[r] + acc1[r];
 #pragma unroll
@@ -130,6 +136,7 @@ __global__ __launch_bounds__(256) void mfma_fill_kernel(int iters, float* __rest
 
 // kind + 100: the same filler beside v_mfma_f32_16x16x4_f32.  The add kinds (1, 10, 13, 14) also come at the counts of the
 // Winograd kernels' K loops per eight MFMAs: 22 scalar or 11 packed (weight gradient), 10 scalar or 5 packed (conv).
+// Kinds 10, 15 and 16 also at 5 and 6 per eight: the packed adds / fmas and the reads of the one-row-per-wave weight gradient.
 extern "C" int sisr_diag_mfma_fill(int blocks, int iters, int kind, int count, float* out, const float* src,
                                    unsigned long long* clk, void* stream) {
   if (blocks <= 0 || iters <= 0 || !out || !src || !clk) return SISR_ERR_ARG;
@@ -140,6 +147,7 @@ extern "C" int sisr_diag_mfma_fill(int blocks, int iters, int kind, int count, f
   FILL(1, 0, 0) FILL(1, 0, 1)
   FILLK(1) FILLK(2) FILLK(3) FILLK(4) FILLK(5) FILLK(6) FILLK(7) FILLK(8) FILLK(9) FILLK(10) FILLK(11) FILLK(12) FILLK(13) FILLK(14)
   FILLA(1) FILLA(10) FILLA(13) FILLA(14)
+  FILL(10, 6, 0) FILL(15, 5, 0) FILL(15, 6, 0) FILL(16, 5, 0) FILL(16, 6, 0)
 #undef FILLA
 #undef FILLK
 #undef FILL

@@ -491,24 +491,32 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_full_geo_kernel(WgradPara
 //   tile: 4 x 32 output pixels = 2 x 16 blocks (K = 32 per tile and transform point); staged like the dense kernel
 //         (issue the next tile's loads before this tile's K loops, commit them to LDS once the raw image is free):
 //         x halo 6 x 34 x 64 (52.2 KB) and dY' 4 x 32 x 64 (32.8 KB), fp32, [row][col][64 ch]
-//         (85.0 KB of LDS in all; V and M never go to LDS)
-//   wave w = (ci half w >> 1, co half w & 1): 16 persistent 32 x 32 accumulators (256 registers, one per xi), K index
-//         (lane >> 5) = block parity, one wave per SIMD.  K-step ks (16 per tile) covers blocks 2 ks and 2 ks + 1: lane
-//         (i, kk) reads the raw 4 x 4 patch of block 2 ks + kk, channel ci half * 32 + i, and the raw 2 x 2 dY' block of
-//         channel co half * 32 + i (10 ds_read2st64_b32, 32 consecutive floats per 32-lane half: no bank conflict), forms
-//         its 16 V and 16 M values itself (32 + 12 adds, rows first, then columns, as 22 v_pk_add_f32 on the register pairs
-//         the reads return) and issues 16 v_mfma_f32_32x32x2_f32, one per xi.  Per accumulator the K order is ks ascending
-//         with block 2 ks + kk in lane slot kk, as when V and M were staged through LDS chunks, so the sums are the same bit
-//         for bit.
+//         (85.0 KB, and 24 KB of +0 behind it: 107.0 KB of LDS in all; V and M never go to LDS)
+//   wave xr = transform row xr: the four points xi = 4 xr + xc for all 64 ci x 64 co, in 16 persistent 32 x 32 accumulators
+//         (256 registers) indexed (xc, ci half, co half); K index (lane >> 5) = block parity, one wave per SIMD.  K-step ks
+//         (16 per tile) covers blocks 2 ks and 2 ks + 1: lane (i, kk) reads, for the channels i and 32 + i of block
+//         2 ks + kk, only the two raw patch rows (ra, rb) that row xr of B^T d needs and the dY' rows that row xr of A dY'
+//         needs (12 ds_read2st64_b32, 32 consecutive floats per 32-lane half: no bank conflict), forms d_ra + s d_rb and
+//         y_a + s y_b with s = +-1 in a register (v_pk_fma_f32: exact, the IEEE add or subtraction of the two operands; the
+//         waves whose row of A has one entry read y_b = +0 from the zero area, x + (-0) = x), then the column steps as
+//         before: 12 packed instructions for its 8 V and 8 M values, each of which feeds two of the step's 16
+//         v_mfma_f32_32x32x2_f32.  No transform value is built twice in a workgroup (with a wave per (ci half, co half)
+//         quadrant every V and M was built by two waves: 22 packed adds per lane and step).  The four waves run ONE
+//         instruction stream; they differ in four LDS bases and in s.  Per accumulator the K order is ks ascending with
+//         block 2 ks + kk in lane slot kk and every V / M value is the same add of the same operands as in the quadrant
+//         form, so the sums are the same bit for bit.
 //   budget per tile and SIMD: 16 x 16 MFMAs = 16.4 K cycles (direct form on the same pixels: 36.9 K); the reads and adds of
 //         step ks + 1 stand between step ks's MFMAs (source order, fenced), two barriers per tile around the commit
-//   epilogue: per lane the 16 dU registers of an element are folded to the nine taps (dg = G^T dU G, coefficients
-//         +-1 and 1/2) and stored as the dense kernel's quadrant slab; bias slabs and the second stage are unchanged.
+//   epilogue: the four rows of an element live in four waves; a quadrant at a time they are exchanged through LDS (64 KB
+//         over the dead raw image, [xr][xc][r / 4][lane][4], b128 both ways), wave w folds the registers [4 w, 4 w + 4) of
+//         the quadrant to the nine taps (dg = G^T dU G, coefficients +-1 and 1/2, rows first) and stores them at the dense
+//         kernel's quadrant-slab addresses; bias slabs and the second stage are unchanged.
 #define W4_TH 4
 #define W4_HH (W4_TH + 2)
 #define W4G_X (W4_HH * WH_W * 64)  // floats
 #define W4G_Y (W4_TH * WT_W * 64)
-#define W4G_LDS ((W4G_X + W4G_Y) * 4)  // bytes: 84992
+#define W4G_Z 6144  // floats of +0 behind the image: what the K loop's largest dY' offset (5888) + lane base (191) + 64 can reach
+#define W4G_LDS ((W4G_X + W4G_Y + W4G_Z) * 4)  // bytes: 109568
 
 // The half-selecting forms of the packed add (sisr_common.h) that the Winograd weight gradient's column transforms take
 __device__ __forceinline__ f32x2 pk_add_nl(f32x2 a, f32x2 b) {  // (a.x - b.x, a.y + b.x)
@@ -521,6 +529,11 @@ __device__ __forceinline__ f32x2 pk_hh_sub(f32x2 a, f32x2 b) {  // (a.y - b.x, a
   asm volatile("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
+__device__ __forceinline__ f32x2 pk_fma(f32x2 s, f32x2 b, f32x2 a) {  // (a.x + s.x b.x, a.y + s.y b.y)
+  f32x2 r;
+  asm volatile("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(s), "v"(b), "v"(a));
+  return r;
+}
 __device__ __forceinline__ f32x2 pk_h_pm_l(f32x2 a) {  // (a.y + a.x, a.y - a.x)
   f32x2 r;
   asm volatile("v_pk_add_f32 %0, %1, %1 op_sel:[1,0] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a));
@@ -531,10 +544,11 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* const ldx = lds;
   float* const ldy = lds + W4G_X;
+  float* const ldz = lds + W4G_X + W4G_Y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int pair = blockIdx.y;
   const int cq = pair % p.cout_chunks, cc = pair / p.cout_chunks;
-  const int cih = __builtin_amdgcn_readfirstlane(wave >> 1), coh = __builtin_amdgcn_readfirstlane(wave & 1);
+  const int xr = __builtin_amdgcn_readfirstlane(wave);  // this wave's transform row
   const int i = lane & 31, kk = lane >> 5;
   const int H = p.H, W = p.W;
   const bool do_bias = p.bias_slabs && cc == 0;
@@ -545,6 +559,7 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
 #pragma unroll
   for (int t = 0; t < 16; ++t) acc[t] = (f32x16){0};
   f32x4 bsa = {0.f, 0.f, 0.f, 0.f}, bsb = bsa;
+  for (int k = tid; k < W4G_Z / 4; k += 256) reinterpret_cast<f32x4*>(ldz)[k] = (f32x4){0.f, 0.f, 0.f, 0.f};  // +0, never written again
 
   const int tiles_w = p.tiles_w, tiles_h = (H + W4_TH - 1) / W4_TH;
   const int tiles_per_img = tiles_w * tiles_h;
@@ -670,74 +685,93 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
     }
   };
 
-  // K-step ks: this lane's block 2 ks + kk = (row ks >> 3, column 2 (ks & 7) + kk); raw 4 x 4 patch of its ci channel and
-  // raw 2 x 2 dY' block of its co channel (the lane base carries kk and the channel, the rest is a constant per step).
-  // Columns (j, j + 1) of a row are one ds_read2st64_b32, i.e. one register pair: d[r][c] = (d[r][2c], d[r][2c + 1]).
-  const float* const xl = ldx + kk * (2 * 64) + cih * 32 + i;
-  const float* const yl = ldy + kk * (2 * 64) + coh * 32 + i;
+  // K-step ks: this lane's block 2 ks + kk = (row ks >> 3, column 2 (ks & 7) + kk).  Wave xr needs row xr of B^T d and of
+  // A dY' only: rows (ra, rb) of the raw 4 x 4 patch with d_ra + s d_rb, s = +-1, and rows (ya, yb) of the raw 2 x 2 dY' block
+  // with y_ya + s y_yb, for the channels i and 32 + i (the lane bases carry kk, the channel and the wave's rows; the rest is
+  // a constant per step, the same for every wave):
+  //   xr  ra rb  s    ya  yb
+  //   0   0  2  -1    0   zero area     y0 + (-1)(+0) = y0 + (-0) = y0, for every y0, zeros of either sign included
+  //   1   1  2  +1    0   1
+  //   2   2  1  -1    0   1
+  //   3   1  3  -1    1   zero area
+  // s is a register pair, the row step v_pk_fma_f32: s d_rb is exact, so the result is the IEEE add or subtraction of the
+  // same two operands.  Columns (j, j + 1) of a row are one ds_read2st64_b32, i.e. one register pair.
+  const int ra = xr == 0 ? 0 : xr == 2 ? 2 : 1, rb = xr == 2 ? 1 : xr == 3 ? 3 : 2;
+  const float sg = xr == 1 ? 1.f : -1.f;
+  const f32x2 sgn = {sg, sg};
+  // (one base per channel, opaque to the compiler: every offset from it is then a multiple of 64 floats, the unit of
+  // ds_read2st64_b32's two offsets; folded into one base, the 32-float channel step forces an address add per read)
+  typedef const float __attribute__((address_space(3))) * lds_f32_ptr;
+  lds_f32_ptr xla[2], xlb[2], yla[2], ylb[2];
+#pragma unroll
+  for (int ch = 0; ch < 2; ++ch) {
+    const int lb = kk * (2 * 64) + 32 * ch + i;
+    xla[ch] = (lds_f32_ptr)(ldx + ra * (WH_W * 64) + lb);
+    xlb[ch] = (lds_f32_ptr)(ldx + rb * (WH_W * 64) + lb);
+    yla[ch] = (lds_f32_ptr)(ldy + (xr == 3 ? WT_W * 64 : 0) + lb);
+    ylb[ch] = (lds_f32_ptr)((xr == 1 || xr == 2 ? ldy + WT_W * 64 : ldz) + lb);
+    asm volatile("" : "+v"(xla[ch]), "+v"(xlb[ch]), "+v"(yla[ch]), "+v"(ylb[ch]));
+  }
   struct Raw {
-    f32x2 d[4][2], y[2];
+    f32x2 da[2][2], db[2][2], ya[2], yb[2];  // [channel i | 32 + i][column pair]
   };
   auto fetch = [&](int ks, Raw& rw) {
     const int br = ks >> 3, bc = ks & 7;
 #pragma unroll
-    for (int c = 0; c < 2; ++c)
+    for (int ch = 0; ch < 2; ++ch)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float* q = xl + ((2 * br + r) * WH_W + 4 * bc + 2 * c) * 64;
-        rw.d[r][c] = (f32x2){q[0], q[64]};
+      for (int c = 0; c < 2; ++c) {
+        const int o = (2 * br * WH_W + 4 * bc + 2 * c) * 64;
+        rw.da[ch][c] = (f32x2){xla[ch][o], xla[ch][o + 64]};
+        rw.db[ch][c] = (f32x2){xlb[ch][o], xlb[ch][o + 64]};
       }
 #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const float* q = yl + ((2 * br + r) * WT_W + 4 * bc) * 64;
-      rw.y[r] = (f32x2){q[0], q[64]};
+    for (int ch = 0; ch < 2; ++ch) {
+      const int o = (2 * br * WT_W + 4 * bc) * 64;
+      rw.ya[ch] = (f32x2){yla[ch][o], yla[ch][o + 64]};
+      rw.yb[ch] = (f32x2){ylb[ch][o], ylb[ch][o + 64]};
     }
   };
-  // V = B^T d B (rows 0: d0 - d2, 1: d1 + d2, 2: d2 - d1, 3: d1 - d3, then the same over columns) and M = A dY' A^T with
-  // A's last row negated (rows 0: y0, 1: y0 + y1, 2: y0 - y1, 3: y1, then over columns); index xi = xr * 4 + xc.
-  // The adds are issued two floats at a time (v_pk_add_f32: beside the fp32 MFMA every vector instruction costs its full
-  // issue time, a packed one no more than a scalar one), 22 instructions for the 44 adds of a step:
-  //   k  0 ..  7  rows of V on the column pairs (0, 1) and (2, 3)
-  //   k  8 .. 15  per row xr: va = (V0, V1) = (r0 - r2, r1 + r2) and vb = (-V2, V3) = (r1 - r2, r1 - r3)
-  //   k 16 .. 17  rows 1 and 2 of M on the pair (0, 1); rows 0 and 3 are the raw registers
-  //   k 18 .. 21  per row xr: mc = (M1, -M2) = (y1 + y0, y1 - y0); M0 and M3 are the row's own registers
+  // Row xr of V = B^T d B (rows 0: d0 - d2, 1: d1 + d2, 2: d2 - d1, 3: d1 - d3, then the same over columns) and of
+  // M = A dY' A^T with A's last row negated (rows 0: y0, 1: y0 + y1, 2: y0 - y1, 3: y1, then over columns), for both
+  // channels, two floats per instruction (beside the fp32 MFMA every vector instruction costs its full issue time, a packed
+  // one no more than a scalar one), 12 instructions for the 24 adds of a step:
+  //   k  0 ..  3  row step of V per channel and column pair (0, 1), (2, 3)
+  //   k  4 ..  7  per channel: va = (V0, V1) = (r0 - r2, r1 + r2) and vb = (-V2, V3) = (r1 - r2, r1 - r3)
+  //   k  8 ..  9  row step of M per channel on the pair (0, 1)
+  //   k 10 .. 11  per channel: mc = (M1, -M2) = (y1 + y0, y1 - y0); M0 and M3 are the row's own registers
   // Column 2 of V and of M are both held NEGATED: b - a is -(a - b) to the bit (but for the sign of a zero, which no
   // product or sum downstream can tell), so (-V2)(-M2) is the same product and every other value is the same add.
   struct Ops {
-    f32x2 va[4], vb[4], ry[4], mc[4];
+    f32x2 va[2], vb[2], ry[2], mc[2];
   };
-  f32x2 rr[4][2];
+  f32x2 rr[2][2];
   auto transform_op = [&](int k, const Raw& rw, Ops& o) {
-    if (k < 8) {
-      const int c = k >> 2, r = k & 3;
-      rr[r][c] = r == 0 ? sisr_pk_sub(rw.d[0][c], rw.d[2][c]) : r == 1 ? sisr_pk_add(rw.d[1][c], rw.d[2][c])
-               : r == 2 ? sisr_pk_sub(rw.d[2][c], rw.d[1][c]) : sisr_pk_sub(rw.d[1][c], rw.d[3][c]);
-    } else if (k < 16) {
-      const int xr = (k - 8) >> 1;
-      if (k & 1) o.vb[xr] = pk_hh_sub(rr[xr][0], rr[xr][1]);
-      else o.va[xr] = pk_add_nl(rr[xr][0], rr[xr][1]);
-    } else if (k == 16) {
-      o.ry[0] = rw.y[0];
-      o.ry[3] = rw.y[1];
-      o.ry[1] = sisr_pk_add(rw.y[0], rw.y[1]);
-    } else if (k == 17) {
-      o.ry[2] = sisr_pk_sub(rw.y[0], rw.y[1]);
+    if (k < 4) {
+      const int ch = k >> 1, c = k & 1;
+      rr[ch][c] = pk_fma(sgn, rw.db[ch][c], rw.da[ch][c]);
+    } else if (k < 8) {
+      const int ch = (k - 4) >> 1;
+      if (k & 1) o.vb[ch] = pk_hh_sub(rr[ch][0], rr[ch][1]);
+      else o.va[ch] = pk_add_nl(rr[ch][0], rr[ch][1]);
+    } else if (k < 10) {
+      o.ry[k - 8] = pk_fma(sgn, rw.yb[k - 8], rw.ya[k - 8]);
     } else {
-      o.mc[k - 18] = pk_h_pm_l(o.ry[k - 18]);
+      o.mc[k - 10] = pk_h_pm_l(o.ry[k - 10]);
     }
   };
-  auto mfma = [&](int t, const Ops& o) {
-    const int xr = t >> 2, xc = t & 3;
-    const float a = xc == 0 ? o.va[xr].x : xc == 1 ? o.va[xr].y : xc == 2 ? o.vb[xr].x : o.vb[xr].y;
-    const float b = xc == 0 ? o.ry[xr].x : xc == 1 ? o.mc[xr].x : xc == 2 ? o.mc[xr].y : o.ry[xr].y;
+  auto mfma = [&](int t, const Ops& o) {  // accumulator t = (xc, ci half, co half)
+    const int xc = t >> 2, cih = (t >> 1) & 1, coh = t & 1;
+    const float a = xc == 0 ? o.va[cih].x : xc == 1 ? o.va[cih].y : xc == 2 ? o.vb[cih].x : o.vb[cih].y;
+    const float b = xc == 0 ? o.ry[coh].x : xc == 1 ? o.mc[coh].x : xc == 2 ? o.mc[coh].y : o.ry[coh].y;
     acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[t], 0, 0, 0);
   };
 
-  // ---- per tile 16 K-steps of two blocks, 16 MFMAs each (one per transform point).  Step ks + 1's raw values are
-  // requested behind step ks's first MFMAs and transformed between the others, so the operands alternate between two
-  // register sets.  The packed adds are inline assembly, which the scheduler's instruction groups do not count: reads and
-  // adds stand in source order between the MFMAs, every group fenced by a scheduling barrier.  An add and the MFMA that
-  // reads its result are always at least one MFMA apart.  Once step 15's values are read no wave needs the raw image:
+  // ---- per tile 16 K-steps of two blocks, 16 MFMAs each (four transform points x four quadrants).  Step ks + 1's raw
+  // values are requested behind step ks's first MFMA and transformed between the others, so the operands alternate between
+  // two register sets.  The packed instructions are inline assembly, which the scheduler's instruction groups do not count:
+  // reads and adds stand in source order between the MFMAs, every group fenced by a scheduling barrier.  An add and the MFMA
+  // that reads its result are always at least one MFMA apart.  Once step 15's values are read no wave needs the raw image:
   // the next tile is committed in front of step 15's MFMAs and its step 0 is fetched and transformed between them (read,
   // unused, from the stale image after the last tile).
   Ops ops[2];
@@ -748,13 +782,13 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
     Raw rw;
     fetch(0, rw);
 #pragma unroll
-    for (int k = 0; k < 22; ++k) transform_op(k, rw, ops[0]);
+    for (int k = 0; k < 12; ++k) transform_op(k, rw, ops[0]);
   }
   for (int tile = t_begin; tile < t_end; tile += t_step) {
     const bool has_next = tile + t_step < t_end;  // uniform
     if (has_next) issue(tile + t_step);
 #pragma unroll
-    for (int ks = 0; ks < 15; ++ks) {  // reads behind the first MFMA, three MFMAs for them to land, then two adds to a gap
+    for (int ks = 0; ks < 15; ++ks) {  // reads behind the first MFMA, three MFMAs for them to land, then four adds to a gap
       const int cur = ks & 1, nxt = cur ^ 1;
       Raw rw;
       __builtin_amdgcn_sched_barrier(0);
@@ -765,15 +799,16 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
 #pragma unroll
       for (int t = 1; t < 4; ++t) mfma(t, ops[cur]);
 #pragma unroll
-      for (int t = 4; t < 15; ++t) {
+      for (int t = 4; t < 7; ++t) {  // V's row steps, V's column steps, M: behind MFMAs 4, 5 and 6
         __builtin_amdgcn_sched_barrier(0);
         mfma(t, ops[cur]);
         __builtin_amdgcn_sched_barrier(0);
-        transform_op(2 * (t - 4), rw, ops[nxt]);
-        transform_op(2 * (t - 4) + 1, rw, ops[nxt]);
+#pragma unroll
+        for (int k = 4 * (t - 4); k < 4 * (t - 3); ++k) transform_op(k, rw, ops[nxt]);
       }
       __builtin_amdgcn_sched_barrier(0);
-      mfma(15, ops[cur]);
+#pragma unroll
+      for (int t = 7; t < 16; ++t) mfma(t, ops[cur]);
       __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();  // no wave reads the raw image again
@@ -791,8 +826,8 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
       mfma(9, ops[1]);
       mfma(10, ops[1]);
 #pragma unroll
-      for (int t = 11; t < 16; ++t) {  // 22 adds in five gaps: 5, 5, 4, 4, 4; the last MFMA behind the last add
-        const int k0 = t < 13 ? 5 * (t - 11) : 10 + 4 * (t - 13), k1 = t < 13 ? k0 + 5 : k0 + 4;
+      for (int t = 11; t < 16; ++t) {  // 12 adds in five gaps: 3, 3, 2, 2, 2; the last MFMA behind the last add
+        const int k0 = t < 13 ? 3 * (t - 11) : 6 + 2 * (t - 13), k1 = t < 13 ? k0 + 3 : k0 + 2;
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int k = k0; k < k1; ++k) transform_op(k, rw, ops[0]);
@@ -804,9 +839,12 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
   }
 
   // ---- fold dg = G^T dU G per element (rows of G: (1,0,0), (1/2,1/2,1/2), (1/2,-1/2,1/2), (0,0,1); the last with the sign
-  // of M's negated row), store the quadrant slab in the dense kernel's layout
+  // of M's negated row), store the quadrant slabs in the dense kernel's layout.  The four rows of an element live in the
+  // four waves: one quadrant at a time they are exchanged through LDS (the raw image is dead) as [xr][xc][r / 4][lane][4]
+  // (64 KB; 16-byte lane stride: ds_write_b128 / ds_read_b128 without a bank conflict), and wave w folds the registers
+  // r in [4 w, 4 w + 4) of the quadrant.
   {
-    float* out = p.slabs + ((long)blockIdx.x * ((long)gridDim.y * 4) + pair * 4 + cih * 2 + coh) * SLAB;
+    float* const ex = lds;
     auto fold = [](float u0, float u1, float u2, float u3, float& f0, float& f1, float& f2) {
       const float h = 0.5f * (u1 + u2);
       f0 = u0 + h;
@@ -814,17 +852,36 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
       f2 = h - u3;
     };
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float rw[3][4];
+    for (int q = 0; q < 4; ++q) {  // quadrant (ci half q >> 1, co half q & 1)
+      __syncthreads();  // the raw image (q = 0) or the previous quadrant has been read by every wave
 #pragma unroll
-      for (int xc = 0; xc < 4; ++xc) fold(acc[xc][r], acc[4 + xc][r], acc[8 + xc][r], acc[12 + xc][r], rw[0][xc], rw[1][xc], rw[2][xc]);
+      for (int xc = 0; xc < 4; ++xc)
 #pragma unroll
-      for (int kh = 0; kh < 3; ++kh) {
-        float g0, g1, g2;
-        fold(rw[kh][0], rw[kh][1], rw[kh][2], rw[kh][3], g0, g1, g2);
-        out[((kh * 3 + 0) * 16 + r) * 64 + lane] = g0;
-        out[((kh * 3 + 1) * 16 + r) * 64 + lane] = g1;
-        out[((kh * 3 + 2) * 16 + r) * 64 + lane] = g2;
+        for (int rq = 0; rq < 4; ++rq) {
+          const f32x16& v = acc[xc * 4 + q];
+          *reinterpret_cast<f32x4*>(ex + (((xr * 4 + xc) * 4 + rq) * 64 + lane) * 4) =
+              (f32x4){v[4 * rq], v[4 * rq + 1], v[4 * rq + 2], v[4 * rq + 3]};
+        }
+      __syncthreads();
+      f32x4 u[4][4];  // [row][column] of the transform points, four registers each
+#pragma unroll
+      for (int yr = 0; yr < 4; ++yr)
+#pragma unroll
+        for (int xc = 0; xc < 4; ++xc) u[yr][xc] = *reinterpret_cast<const f32x4*>(ex + (((yr * 4 + xc) * 4 + xr) * 64 + lane) * 4);
+      float* out = p.slabs + ((long)blockIdx.x * ((long)gridDim.y * 4) + pair * 4 + q) * SLAB + (4 * xr) * 64 + lane;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float rw[3][4];
+#pragma unroll
+        for (int xc = 0; xc < 4; ++xc) fold(u[0][xc][e], u[1][xc][e], u[2][xc][e], u[3][xc][e], rw[0][xc], rw[1][xc], rw[2][xc]);
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh) {
+          float g0, g1, g2;
+          fold(rw[kh][0], rw[kh][1], rw[kh][2], rw[kh][3], g0, g1, g2);
+          out[((kh * 3 + 0) * 16 + e) * 64] = g0;
+          out[((kh * 3 + 1) * 16 + e) * 64] = g1;
+          out[((kh * 3 + 2) * 16 + e) * 64] = g2;
+        }
       }
     }
   }
