@@ -417,6 +417,18 @@ int sisr_noise_quant(const float* blur, const float* noise, float sigma, unsigne
 int sisr_pil_resample(const unsigned char* in, void* out, const int* bounds, const int* coef, int ksize, int C, int Hin,
                       int Win, int Hout, int Wout, int vertical, int to_float, void* stream);
 
+/* ---- bicubic pre-up-sampling of an LR batch for the evaluator (csrc/interp.hip) ------------------------------------
+ * ref: SISR/evaluation/standard_eval.py:146-164 (_low_res_prep: ToPILImage -> resize(x scale, BICUBIC) -> ToTensor;
+ * _high_res_prep: BT.601 'jpg' YCbCr).  One launch for the batch, no workspace: lr [B][C][h][w] fp32 is quantised as
+ * ToPILImage does (byte(v * 255), truncating), run through both passes of libImaging/Resample.c's 8-bit resampler (as
+ * sisr_pil_resample; the horizontal rows of a 32 x 32 output tile stay in LDS) and written as rgb = byte / 255 and / or
+ * ycbcr = metrics.rgb_to_ycbcr_jpg(rgb) with that function's fp32 roundings (no fma), [B][C][H][W] fp32 each; either output
+ * may be null, not both.  H = s h and W = s w for one integer s >= 1; bounds_* / coef_* are device copies of the host
+ * tables for (w -> W) and (h -> H), whose ksize is 5 at every such scale.  SISR_ERR_ARG: null pointers, non-positive sizes;
+ * SISR_ERR_UNSUPPORTED: other size ratios, ycbcr with C != 3, ksize != 5, more than 65535 tile rows or B * ceil(C / 3) > 65535. */
+int sisr_pil_upsample(const float* lr, float* rgb, float* ycbcr, const int* bounds_h, const int* coef_h, const int* bounds_v,
+                      const int* coef_v, int ksize, int B, int C, int h, int w, int H, int W, void* stream);
+
 /* ---- SPARNet / QSPARNet pieces (csrc/sparnet.hip) --------------------------------------------------------------
  * ref: SPARNet/blocks.py:69-103 ConvLayer ([nearest x2] -> ReflectionPad2d(1) -> Conv2d(3x3, stride 1 | 2) -> [BatchNorm2d]
  * -> [LeakyReLU(0.2)]), :106-174 ResidualBlock, :177-243 HourGlassBlock.  Maps are NHWC with C a multiple of 64 (channels

@@ -19,7 +19,7 @@ import torch
 
 from . import metrics as M
 from . import parallel
-from .data import SuperResImages, sisr_data_setup
+from .data import SuperResImages, rgb_to_ycbcr, sisr_data_setup
 from .handlers import ModelInterface, create_dir_if_empty
 
 
@@ -192,9 +192,48 @@ def train_sisr(parameters, experiment_name=None, **overrides):
     return exp.run_experiment()
 
 
+def _low_res_prep(lr, scale):
+    """ref: standard_eval.py:146-158: each image of a (B, 3, h, w) fp32 host batch through ToPILImage (`mul(255).byte()`), PIL's
+    `resize((w * scale, h * scale), BICUBIC)` and ToTensor -> (B, 3, h * scale, w * scale) fp32.  The host form of
+    degrade.pil_bicubic_upsample: used when the models run on the CPU, and what the device kernel is tested against."""
+    from PIL import Image
+    from .data import to_tensor
+    out = torch.empty(*lr.shape[0:2], lr.shape[2] * scale, lr.shape[3] * scale)
+    for i in range(lr.shape[0]):
+        image = Image.fromarray(lr[i].mul(255).byte().permute(1, 2, 0).contiguous().numpy())
+        out[i] = to_tensor(image.resize((image.width * scale, image.height * scale), resample=Image.BICUBIC))
+    return out
+
+
+def _interpolated(lr, scale, device, want_ycbcr, timing):
+    """The interpolated RGB batch, its YCbCr form (or None) and the seconds it took (or None): on `device` from the uploaded LR
+    batch (one launch for both), or on the host (ref: standard_eval.py:236-241)."""
+    tic = None
+    if device is not None:
+        from . import degrade
+        lr = lr.to(device)
+        if timing:
+            torch.cuda.synchronize(device)
+            tic = time.perf_counter()
+        out = degrade.pil_bicubic_upsample(lr, scale, rgb=True, ycbcr=want_ycbcr)
+        rgb, ycbcr = out if want_ycbcr else (out, None)
+        if timing:
+            torch.cuda.synchronize(device)
+    else:
+        if timing:
+            tic = time.perf_counter()
+        rgb = _low_res_prep(lr, scale)
+        ycbcr = torch.from_numpy(M.batch_rgb_to_ycbcr(rgb.numpy())) if want_ycbcr else None
+    return rgb, ycbcr, time.perf_counter() - tic if timing else None
+
+
 def eval_sisr(config=None, **kw):
     """ref: net_eval.py:64-74 / standard_eval.py full_image_protocol: per-image and average Y-PSNR CSVs, plus Y-SSIM
-    columns when the config's `metrics` lists 'SSIM' (ref: standard_eval.py:268-271)."""
+    columns when the config's `metrics` lists 'SSIM' (ref: standard_eval.py:268-271).  Each model is given the input its
+    configuration names (ref: standard_eval.py:254-260): the LR batch as read, that batch bicubic-up-sampled x scale
+    ('interp' models), or the up-sampled batch in YCbCr (the Y-channel models).  The up-sampled batch is made once per batch
+    (on the device when the models run there), or read from `lr_dir_interp`.  `lr_baseline = true` adds 'LR' rows: the
+    up-sampled image itself against the HR image (the reference always writes them)."""
     import pandas as pd
     cfg = dict(_load_toml(config)) if config is not None else {}
     cfg.update({k: v for k, v in kw.items() if v is not None})
@@ -202,26 +241,71 @@ def eval_sisr(config=None, **kw):
     os.makedirs(out_dir, exist_ok=True)
     scale = cfg.get('scale', 4)
     models = [ModelInterface(cfg['model_loc'], name, gpu='single' if cfg.get('gpu') else 'off',
-                             sp_gpu=cfg.get('sp_gpu', 0), mode='eval', load_epoch=ep if ep in ('best', 'last') else int(ep),
-                             scale=scale) for name, ep in cfg['model_and_epoch']]
+                             sp_gpu=cfg.get('sp_gpu', 0), mode='eval', load_epoch=ep if ep in ('best', 'last') else int(ep))
+              for name, ep in cfg['model_and_epoch']]
+    for m in models:
+        # A network fed the up-sampled image maps it to one of the same size whatever `scale` it was configured with (it
+        # describes the crops of its training set: 1 where those were cut from interpolated images); the others must match.
+        if m.configuration['input'] == 'unmodified' and scale != m.metadata['internal_params']['scale']:
+            raise Exception('The model loaded has been trained for a different scale, '
+                            'and cannot produce the requested images.')
     lr_dir = cfg['lr_dir']
     meta = cfg.get('metadata_file') or os.path.join(lr_dir, 'degradation_metadata.csv')
     if not os.path.isfile(meta):
         meta = None
-    data = SuperResImages(lr_dir, cfg.get('hr_dir'), split='all' if cfg.get('full_directory') else (cfg.get('data_split') or 'eval'),
+    split = 'all' if cfg.get('full_directory') else (cfg.get('data_split') or 'eval')
+    data = SuperResImages(lr_dir, cfg.get('hr_dir'), split=split,
                           dataset=cfg.get('dataset_name'), scale=scale, degradation_metadata_file=meta,
                           recursive_search=bool(cfg.get('recursive')))
     loader = torch.utils.data.DataLoader(dataset=data, batch_size=cfg.get('batch_size', 1))
     with_ssim = 'SSIM' in (cfg.get('metrics') or ())
+    timing = cfg.get('time_models', True)
+    baseline = bool(cfg.get('lr_baseline'))
+    y_models = [m for m in models if 'rgb' not in m.configuration['colorspace']]
+    need_interp = baseline or bool(y_models) or any(m.configuration['input'] != 'unmodified' for m in models)
+    need_ycbcr = baseline or bool(y_models)
+    device = next((torch.device('cuda', m.device) for m in models if m.device != torch.device('cpu')), None)
+    stored = None
+    if need_interp and cfg.get('lr_dir_interp'):  # ready-made interpolated images, in step with the LR loader
+        stored = iter(torch.utils.data.DataLoader(
+            dataset=SuperResImages(cfg['lr_dir_interp'], cfg.get('hr_dir'), split=split, dataset=cfg.get('dataset_name'),
+                                   scale=scale, input='interp', recursive_search=bool(cfg.get('recursive'))),
+            batch_size=cfg.get('batch_size', 1)))
     rows = []
     for batch in loader:
         y_proc = ModelInterface.colorspace_convert(batch['hr'], colorspace='rgb')
+        interp = interp_ycbcr = None
+        if stored is not None:
+            interp, up_secs = next(stored)['lr'], None
+            if need_ycbcr:
+                interp_ycbcr = torch.from_numpy(M.batch_rgb_to_ycbcr(interp.numpy()))
+        elif need_interp:
+            interp, interp_ycbcr, up_secs = _interpolated(batch['lr'], scale, device, need_ycbcr, timing)
+        if baseline:
+            lr_y = interp_ycbcr[:, :1]
+            if with_ssim:
+                lr_ssim = M.batch_ssim(lr_y, torch.from_numpy(y_proc[:, :1]), max_value=1)
+            lr_y = lr_y.cpu().numpy()
+            for i, tag in enumerate(batch['tag']):
+                row = {'Image_Name': tag, 'Model': 'LR', 'PSNR': M.psnr(lr_y[i, 0], y_proc[i, 0], 1)}
+                if with_ssim:
+                    row['SSIM'] = lr_ssim[i]
+                row['runtime'] = up_secs
+                rows.append(row)
         for m in models:
+            feed = batch
+            if m in y_models:
+                # the Y-channel branch reads the reference's Y from channel 0 of `hr` (loss, SSIM): hand it the HR image as
+                # the validation set of such a model does, in YCbCr (data.SuperResImages, colorspace = 'ycbcr')
+                feed = {**batch, 'lr': interp_ycbcr,
+                        'hr': torch.stack([rgb_to_ycbcr(im, y_only=False) for im in batch['hr']])}
+            elif m.configuration['input'] != 'unmodified':
+                feed = {**batch, 'lr': interp}
             if with_ssim:  # SSIM on the device output (data_range 1), outside the timed window
-                rgb, ycbcr, _, secs, measured = m.net_run_process_and_measure(**batch, metrics=['SSIM'], max_value=1,
-                                                                              timing=cfg.get('time_models', True))
+                rgb, ycbcr, _, secs, measured = m.net_run_process_and_measure(**feed, metrics=['SSIM'], max_value=1,
+                                                                              timing=timing)
             else:
-                rgb, ycbcr, _, secs = m.net_run_and_process(**batch, timing=cfg.get('time_models', True))
+                rgb, ycbcr, _, secs = m.net_run_and_process(**feed, timing=timing)
             for i, tag in enumerate(batch['tag']):
                 row = {'Image_Name': tag, 'Model': m.experiment, 'PSNR': M.psnr(ycbcr[i, 0], y_proc[i, 0], 1)}
                 if with_ssim:

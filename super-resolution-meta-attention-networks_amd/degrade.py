@@ -12,6 +12,9 @@ Pixels stay on the device: csrc/degrade.hip blurs the planar fp32 HR image with 
 as ToPILImage does (`mul(255).byte()`), then runs PIL's two 8-bit fixed-point resample passes with coefficient tables
 computed here exactly as libImaging/Resample.c computes them -- the LR image is bit-identical to PIL's for the same
 uint8 input.  There is no CPU path: the tensors must live on a HIP device.
+
+The same resampler run the other way (`pil_bicubic_upsample`, csrc/interp.hip) is the evaluator's bicubic pre-up-sampling
+of an LR batch for the interpolated-input models (ref: Code/SISR/evaluation/standard_eval.py:146-164).
 """
 import math
 
@@ -190,6 +193,34 @@ def pil_bicubic_downsample(u8, scale, to_float=True):
     hip.check(L.sisr_pil_resample(tmp.data_ptr(), out.data_ptr(), bv.data_ptr(), cv.data_ptr(), ksv, C, H, w, h, w, 1,
                                   int(to_float), hip.stream()), "sisr_pil_resample(v)")
     return out
+
+
+def pil_bicubic_upsample(lr, scale, rgb=True, ycbcr=False):
+    """The evaluator's pre-up-sampling (ref: evaluation/standard_eval.py:146-164) of a (B, 3, h, w) fp32 device batch, one
+    launch: per image ToPILImage -> `resize((w * s, h * s), BICUBIC)` -> ToTensor, bit for bit, and / or that image in
+    BT.601 'jpg' YCbCr with the fp32 roundings of metrics.rgb_to_ycbcr_jpg.  -> the requested (B, 3, s h, s w) device
+    tensors: one tensor, or (rgb, ycbcr) when both are asked for."""
+    if not lr.is_cuda:
+        raise RuntimeError("degrade.pil_bicubic_upsample: the batch must be on a HIP device (no CPU path)")
+    if lr.dim() != 4 or lr.dtype != torch.float32:
+        raise ValueError(f"pil_bicubic_upsample takes a (B, C, h, w) fp32 batch; got {lr.dtype} {tuple(lr.shape)}")
+    if not (rgb or ycbcr):
+        raise ValueError("pil_bicubic_upsample: ask for rgb, ycbcr or both")
+    scale = int(scale)
+    B, C, h, w = lr.shape
+    H, W = h * scale, w * scale
+    dev = lr.device
+    lr = lr.contiguous()
+    with torch.cuda.device(dev):
+        bh, ch, ksh = _device_table(w, W, dev)
+        bv, cv, ksv = _device_table(h, H, dev)
+        assert ksh == ksv
+        out_rgb = torch.empty((B, C, H, W), device=dev, dtype=torch.float32) if rgb else None
+        out_ycc = torch.empty((B, C, H, W), device=dev, dtype=torch.float32) if ycbcr else None
+        hip.check(hip.lib().sisr_pil_upsample(hip.ptr(lr), hip.ptr(out_rgb), hip.ptr(out_ycc), bh.data_ptr(), ch.data_ptr(),
+                                              bv.data_ptr(), cv.data_ptr(), ksh, B, C, h, w, H, W, hip.stream()),
+                  "sisr_pil_upsample")
+    return (out_rgb, out_ycc) if rgb and ycbcr else (out_rgb if rgb else out_ycc)
 
 
 def center_crop_box(height, width, scale):

@@ -124,6 +124,9 @@ _SIGS.update({  # on-the-fly degradation (csrc/degrade.hip)
     "sisr_pil_resample": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "sisr_noise_quant": (c_int, [P, P, c_float, P, c_long, P]),
 })
+_SIGS.update({  # the evaluator's bicubic pre-up-sampling (csrc/interp.hip)
+    "sisr_pil_upsample": (c_int, [P] * 7 + [c_int] * 7 + [P]),
+})
 _SIGS.update({  # around the non-local attention (csrc/nonlocal.hip)
     "sisr_nl_project_fwd": (c_int, [P] * 8 + [c_long, P]),
     "sisr_nl_project_bwd_parts": (c_int, [c_long]),
