@@ -616,6 +616,20 @@ int sisr_wgradk_mfma(const float* x, const float* dy, const float* dymask, float
 size_t sisr_mse_loss_workspace_bytes(void);
 int sisr_mse_loss(const float* a, const float* b, long n, float* loss, float* grad, float* workspace, void* stream);
 
+/* ---- geometric self-ensemble around a network (csrc/ensemble.hip) -----------------------------------------------------
+ * The eight flips / transposes of an image batch as two batches a network runs as they are, and the mean of its eight
+ * outputs with each mapped back (the "+" protocol of the EDSR / RCAN / HAN / SAN papers).  All maps contiguous NCHW fp32;
+ * batches are variant-major: image i of variant k is entry k * n + i.  upright (4n, c, h, w), k = 0..3: the image, its
+ * columns reversed, its rows reversed, both reversed; turned (4n, c, w, h): the same four operations applied to the
+ * transposed image.
+ * sisr_dihedral_fan: a pure copy, every output element bit-identical to its source.
+ * sisr_dihedral_merge: out (n, c, H, W) from upright (4n, c, H, W) and turned (4n, c, W, H), variant k mapped back as u_k / t_k:
+ *   out = (((u0 + u1) + (u2 + u3)) + ((t0 + t1) + (t2 + t3))) * 0.125f, plain fp32 adds in this order.
+ * One launch each, any h, w, c >= 1 (16-byte accesses where the row length and the pointers allow them).  Refused before
+ * any launch: null pointers, n, c, h or w <= 0 (-1); more than 2^31 - 1 tiles of 64 x 64 (-4). */
+int sisr_dihedral_fan(const float* x, int n, int c, int h, int w, float* upright, float* turned, void* stream);
+int sisr_dihedral_merge(const float* upright, const float* turned, int n, int c, int H, int W, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -233,7 +233,9 @@ def eval_sisr(config=None, **kw):
     configuration names (ref: standard_eval.py:254-260): the LR batch as read, that batch bicubic-up-sampled x scale
     ('interp' models), or the up-sampled batch in YCbCr (the Y-channel models).  The up-sampled batch is made once per batch
     (on the device when the models run there), or read from `lr_dir_interp`.  `lr_baseline = true` adds 'LR' rows: the
-    up-sampled image itself against the HR image (the reference always writes them)."""
+    up-sampled image itself against the HR image (the reference always writes them).  `self_ensemble = true` evaluates
+    every model with the geometric self-ensemble (run_eval(self_ensemble=True), the papers' "+" rows): its rows and its image
+    folder carry the name '<experiment>+'; the LR rows are unaffected."""
     import pandas as pd
     cfg = dict(_load_toml(config)) if config is not None else {}
     cfg.update({k: v for k, v in kw.items() if v is not None})
@@ -261,6 +263,8 @@ def eval_sisr(config=None, **kw):
     with_ssim = 'SSIM' in (cfg.get('metrics') or ())
     timing = cfg.get('time_models', True)
     baseline = bool(cfg.get('lr_baseline'))
+    plus = {'self_ensemble': True} if cfg.get('self_ensemble') else {}
+    label = (lambda m: m.experiment + '+') if plus else (lambda m: m.experiment)
     y_models = [m for m in models if 'rgb' not in m.configuration['colorspace']]
     need_interp = baseline or bool(y_models) or any(m.configuration['input'] != 'unmodified' for m in models)
     need_ycbcr = baseline or bool(y_models)
@@ -303,18 +307,18 @@ def eval_sisr(config=None, **kw):
                 feed = {**batch, 'lr': interp}
             if with_ssim:  # SSIM on the device output (data_range 1), outside the timed window
                 rgb, ycbcr, _, secs, measured = m.net_run_process_and_measure(**feed, metrics=['SSIM'], max_value=1,
-                                                                              timing=timing)
+                                                                              timing=timing, **plus)
             else:
-                rgb, ycbcr, _, secs = m.net_run_and_process(**feed, timing=timing)
+                rgb, ycbcr, _, secs = m.net_run_and_process(**feed, timing=timing, **plus)
             for i, tag in enumerate(batch['tag']):
-                row = {'Image_Name': tag, 'Model': m.experiment, 'PSNR': M.psnr(ycbcr[i, 0], y_proc[i, 0], 1)}
+                row = {'Image_Name': tag, 'Model': label(m), 'PSNR': M.psnr(ycbcr[i, 0], y_proc[i, 0], 1)}
                 if with_ssim:
                     row['SSIM'] = measured['SSIM'][i]
                 row['runtime'] = secs
                 rows.append(row)
             if cfg.get('save_im'):
                 from PIL import Image
-                d = os.path.join(out_dir, m.experiment)
+                d = os.path.join(out_dir, label(m))
                 os.makedirs(d, exist_ok=True)
                 for i, tag in enumerate(batch['tag']):
                     Image.fromarray((rgb[i].transpose(1, 2, 0) * 255).round().astype(np.uint8)).save(

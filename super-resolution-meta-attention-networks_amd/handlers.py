@@ -22,7 +22,7 @@ import torch
 from torch import nn, optim
 
 from . import architectures as A
-from . import metrics, ops
+from . import ensemble, metrics, ops
 from .metrics import batch_ssim
 
 
@@ -319,7 +319,14 @@ class BaseModel(nn.Module):
         if self.learning_rate_scheduler is not None:
             self.learning_rate_scheduler.step()
 
-    def run_eval(self, x, y=None, request_loss=False, tag=None, timing=False, keep_on_device=False, *args, **kwargs):
+    def run_eval(self, x, y=None, request_loss=False, tag=None, timing=False, keep_on_device=False, *args,
+                 self_ensemble=False, **kwargs):
+        """self_ensemble: the geometric self-ensemble (the papers' "+" rows; ensemble.py) in place of the plain forward: the
+        network runs on the eight flips / transposes of `x` as two batches of 4n and the outputs, mapped back, are averaged.
+        `x` is what reaches the forward (concatenated metadata planes included); `extra_channels` follows it -- (B, M, 1, 1)
+        vectors repeated, maps of x's size flipped along -- with its VALUES unchanged: a degradation code describes the
+        un-flipped image, exact for isotropic blur codes and QPI, the protocol's usual caveat for anisotropic kernels.  The
+        `timing` window holds fan, both forwards and merge; a requested loss is taken on the merged output."""
         self.net.eval()
         tic = toc = None
         with torch.no_grad():
@@ -330,7 +337,10 @@ class BaseModel(nn.Module):
             try:
                 if x.is_cuda:
                     ops.pack_all(self.net, A.conv_weights)
-                out = self.run_model(x, image_names=tag, **kwargs)
+                if self_ensemble:
+                    out = self._run_ensemble(x, tag, kwargs)
+                else:
+                    out = self.run_model(x, image_names=tag, **kwargs)
             finally:
                 ops.invalidate_packs()
             if timing:
@@ -346,6 +356,15 @@ class BaseModel(nn.Module):
 
     def run_model(self, x, *args, **kwargs):
         return self.net.forward(x)
+
+    def _run_ensemble(self, x, tag, kwargs):
+        """run_model under ensemble.self_ensemble: two calls at batch 4n, each with its share of `extra_channels`"""
+        kw = dict(kwargs)
+        extra = kw.pop('extra_channels', None)
+
+        def forward(t, e):
+            return self.run_model(t, image_names=tag, **({} if e is None else {'extra_channels': e}), **kw)
+        return ensemble.self_ensemble(forward, x, extra)
 
     def print_parameters(self, verbose=False):
         total = 0

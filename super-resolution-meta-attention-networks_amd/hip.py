@@ -200,6 +200,11 @@ _SIGS.update({  # SRCNN / VDSR building blocks: K x K convs, the Y-channel ends,
     "sisr_mse_loss": (c_int, [P, P, c_long, P, P, P, P]),
 })
 
+_SIGS.update({  # geometric self-ensemble: the eight flips / transposes of a batch and the mean of eight outputs (csrc/ensemble.hip)
+    "sisr_dihedral_fan": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
+    "sisr_dihedral_merge": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P]),
+})
+
 
 GM_MAXL = 4
 

@@ -27,6 +27,7 @@ import torch
 from torch import nn
 
 from . import architectures as A
+from . import ensemble
 from . import ops
 from .handlers import BaseModel, QModel
 
@@ -239,15 +240,20 @@ def forward_chop(run, x, scale, max_pixels, shave=10):
 class _ChoppedEval:
     """run_eval of the SAN handlers: always through forward_chop (ref: advanced/handlers.py:120-129)."""
 
-    def _chopped_eval(self, x, y, request_loss, timing, keep_on_device, run):
+    def _chopped_eval(self, x, y, request_loss, timing, keep_on_device, run, self_ensemble=False, extra_channels=None):
+        """run(tile, extra) -> the network's output for an LR tile.  self_ensemble: forward_chop on each of the two batches of
+        ensemble.self_ensemble in place of forward_chop on `x` (BaseModel.run_eval has the protocol and its metadata caveat)."""
         self.net.eval()
+
+        def chop(t, e):
+            return forward_chop(lambda tile: run(tile, e), t, self.scale, self.max_combined_im_size)
         tic = toc = None
         with torch.no_grad():
             x = x.to(device=self.device)
             if timing:
                 torch.cuda.synchronize()
                 tic = time.perf_counter()
-            out = forward_chop(run, x, self.scale, self.max_combined_im_size)
+            out = ensemble.self_ensemble(chop, x, extra_channels) if self_ensemble else chop(x, extra_channels)
             if timing:
                 torch.cuda.synchronize()
                 toc = time.perf_counter()
@@ -274,8 +280,9 @@ class SANHandler(_ChoppedEval, BaseModel):
         self.model_name = 'san'
 
     def run_eval(self, x, y=None, request_loss=False, metadata=None, metadata_keys=None, timing=False,
-                 keep_on_device=False, *args, **kwargs):
-        return self._chopped_eval(x, y, request_loss, timing, keep_on_device, lambda t: self.net.forward(t))
+                 keep_on_device=False, *args, self_ensemble=False, **kwargs):
+        return self._chopped_eval(x, y, request_loss, timing, keep_on_device, lambda t, e: self.net.forward(t),
+                                  self_ensemble=self_ensemble)
 
 
 class QSANHandler(_ChoppedEval, QModel):
@@ -294,9 +301,9 @@ class QSANHandler(_ChoppedEval, QModel):
         self.model_name = 'qsan'
 
     def run_eval(self, x, y=None, request_loss=False, metadata=None, metadata_keys=None, timing=False,
-                 keep_on_device=False, extra_channels=None, *args, **kwargs):
+                 keep_on_device=False, extra_channels=None, *args, self_ensemble=False, **kwargs):
         if extra_channels is None:
             extra_channels = self.generate_channels(x, metadata, metadata_keys)
         extra_channels = extra_channels.to(self.device)
-        return self._chopped_eval(x, y, request_loss, timing, keep_on_device,
-                                  lambda t: self.net.forward(t, metadata=extra_channels))
+        return self._chopped_eval(x, y, request_loss, timing, keep_on_device, lambda t, e: self.net.forward(t, metadata=e),
+                                  self_ensemble=self_ensemble, extra_channels=extra_channels)
