@@ -326,7 +326,8 @@ size_t sisr_l1_loss_workspace_bytes(void);
 int sisr_l1_loss(const float* a, const float* b, long n, float* loss, float* grad, float* workspace, void* stream);
 /* torch.optim.Adam's update over one flat range (parameters, gradients, exp_avg, exp_avg_sq laid out alike):
  * one_minus_beta*, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t) computed by the host in double;
- * gradients are read as g * grad_scale */
+ * gradients are read as g * grad_scale.  p, g, m and v must be 16-byte aligned (SISR_ERR_ALIGN, -2, otherwise: the
+ * body moves float4; a tail of n % 4 floats is updated one by one); a null pointer or n <= 0 is SISR_ERR_ARG. */
 int sisr_adam_flat(float* p, const float* g, float* m, float* v, long n, float beta2, float one_minus_beta1,
                    float one_minus_beta2, float eps, float step_size, float bc2_sqrt, float grad_scale, void* stream);
 
@@ -523,14 +524,16 @@ int sisr_spar_combine_bwd(const float* dy, const float* x, const float* att, flo
  * sisr_sft_combine_fwd: out = [relu](x * sigmoid(y2[:, :64]) + y2[:, 64:]); x / out with pixel strides (floats), y2
  *   [npix][128]; md (nullable) [npix][64] is copied into out's second 64-channel chunk.  _bwd: dx [npix][64], dy2.
  * sisr_map64: 64-channel maps with pixel strides: op 0 copy, 1 a + b, 2 LeakyReLU(a), 3 b * LeakyReLU'(a), 4 a * b,
- *   5 ReLU(a), 6 b * ReLU'(a), 7 a * (b's channel 0, broadcast).
+ *   5 ReLU(a), 6 b * ReLU'(a), 7 a * (b's channel 0, broadcast).  out may be a itself (same stride): op 2 is used so.
+ *   Strides are multiples of 4 floats and >= 64, except b's under op 7, which reads one float per pixel.
  * sisr_conv9_*: 9x9 conv 64 -> 3 (OIHW weight), x NHWC [B][H][W][64], y NCHW; dgrad optionally masked by LeakyReLU'
  *   of `leaky_mask` (the activated map that fed the conv); wgrad: ordered two-stage sums (dw OIHW, db).
  * sisr_clamp01: backward == 0: out = clamp(a, 0, 1); else out = grad * [0 <= a <= 1]. */
 int sisr_sft_compose(float* mul_w1, float* mul_b1, float* add_w1, float* add_b1, float* mul_w2, float* mul_b2, float* add_w2,
                      float* add_b2, float* WA, float* bA, float* WB, float* bB, int M, int split, void* stream);
 /* all SFT layers of a network in one launch: table = n records of 12 device pointers (the arguments of sisr_sft_compose in
- * order) + int M + int pad, sisr_sft_compose_record_bytes() each, in device memory */
+ * order) + int M + int split, sisr_sft_compose_record_bytes() each, in device memory.  The record's split field is
+ * ignored: this entry point always composes (parameters -> merged tensors). */
 size_t sisr_sft_compose_record_bytes(void);
 int sisr_sft_compose_many(const void* table, int n, void* stream);
 int sisr_sft_combine_fwd(const float* x, long x_stride, const float* y2, const float* md, float* out, long out_stride,

@@ -14,10 +14,13 @@
 #define BT 32                 // output tile edge
 #define BL_MAX 21             // largest blur kernel edge (reference default and maximum used: 21)
 
-__device__ __forceinline__ int reflect_index(int i, int n) {  // nn.ReflectionPad2d: -1 -> 1, n -> n-2
+// nn.ReflectionPad2d: -1 -> 1, n -> n-2.  Clamped into the image: the staged tile of an edge block reaches past the
+// reflection of rows / columns no output of the block reads (more than l - 1 - l / 2 beyond the image), where one
+// reflection leaves an index below 0; every index an output does read lies within one reflection and is unchanged.
+__device__ __forceinline__ int reflect_index(int i, int n) {
   if (i < 0) i = -i;
   if (i >= n) i = 2 * n - 2 - i;
-  return i;
+  return min(max(i, 0), n - 1);
 }
 
 // x: [C][H][W] fp32, k: [l][l] fp32 (cross-correlation, as F.conv2d), y: [C][H][W] uint8 = (uint8)(conv * 255)

@@ -16,6 +16,11 @@
 
 __device__ __forceinline__ float sft_sigmoid(float z) { return 1.f / (1.f + expf(-z)); }
 
+// The SFT pre-activation x * s + a as ONE fused multiply-add, written out: the forward kernel clamps it and the backward
+// kernel recomputes it for the ReLU mask, so both must round it alike where it lies within rounding of zero.  Left as
+// `x * s + a`, fusing would be the compiler's choice in each kernel separately.
+__device__ __forceinline__ float sft_pre(float x, float s, float a) { return __builtin_fmaf(x, s, a); }
+
 static unsigned sft_blocks(long n) {
   long b = (n + 255) / 256;
   return (unsigned)(b < 1 ? 1 : (b > 65535 ? 65535 : b));
@@ -123,7 +128,7 @@ __global__ __launch_bounds__(256) void sft_combine_fwd_kernel(const float* __res
     f32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float v = xv[e] * sft_sigmoid(mv[e]) + av[e];
+      const float v = sft_pre(xv[e], sft_sigmoid(mv[e]), av[e]);
       o[e] = relu ? fmaxf(v, 0.f) : v;
     }
     *reinterpret_cast<f32x4*>(out + p * os + c4) = o;
@@ -148,7 +153,7 @@ __global__ __launch_bounds__(256) void sft_combine_bwd_kernel(const float* __res
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float s = sft_sigmoid(mv[e]);
-      const float pre = xv[e] * s + av[e];
+      const float pre = sft_pre(xv[e], s, av[e]);
       const float ge = (relu && !(pre > 0.f)) ? 0.f : g[e];
       gx[e] = ge * s;
       gm[e] = ge * xv[e] * s * (1.f - s);
@@ -184,12 +189,14 @@ extern "C" int sisr_sft_combine_bwd(const float* dout, long dout_stride, const f
 // ------------------------------------------------------------------ strided 64-channel helpers
 // op 0: out = a                      (copy: metadata chunk fill)
 // op 1: out = a + b                  (fea_mid + fea_bef; gradient sums)
-// op 2: out = leaky(a)               (a > 0 ? a : 0.2 a)
+// op 2: out = leaky(a)               (a > 0 ? a : 0.2 a; the SFTMD head runs it in place, out == a, after its 3-channel conv)
 // op 3: out = b * (a > 0 ? 1 : 0.2)  (LeakyReLU backward: a = the activation's output, b = incoming gradient)
 // op 4: out = a * b                  (WeakSft with as many maps as features, and its input gradient)
 // op 5: out = relu(a)
 // op 6: out = a > 0 ? b : 0          (ReLU backward: a = the activation's output)
 // op 7: out = a * b[channel 0]       (WeakSft with one map: b's first channel broadcast over the 64 features)
+// The pointers are deliberately not __restrict__: out may be a itself (same stride: every thread reads its float4 before it
+// writes that same float4, and no other thread touches it).
 __global__ __launch_bounds__(256) void map64_kernel(const float* a, long as, const float* b, long bs,
                                                     float* out, long os, long npix, int op) {
   const long total = npix * 16;
@@ -227,6 +234,7 @@ extern "C" int sisr_map64(const float* a, long a_stride, const float* b, long b_
                           int op, void* stream) {
   if (!a || !out || npix <= 0 || op < 0 || op > 7 || ((op == 1 || op == 3 || op == 4 || op == 6 || op == 7) && !b)) return SISR_ERR_ARG;
   if ((a_stride & 3) || (out_stride & 3) || (b && (b_stride & 3)) || a_stride < 64 || out_stride < 64) return SISR_ERR_ARG;
+  if (b && op != 7 && b_stride < 64) return SISR_ERR_ARG;  // every op but 7 reads 64 channels of b per pixel
   if (!sisr_aligned16(a) || !sisr_aligned16(b) || !sisr_aligned16(out)) return SISR_ERR_ALIGN;
   hipLaunchKernelGGL(map64_kernel, dim3(sft_blocks(npix * 16)), dim3(256), 0, (hipStream_t)stream, a, a_stride, b, b_stride, out,
                      out_stride, npix, op);

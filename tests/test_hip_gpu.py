@@ -476,6 +476,32 @@ def test_pixel_shuffle_gather_and_its_adjoint(C, r):
     cot = rnd(*want.shape, seed=91)
     out.backward(cot.to(DEV))
     assert torch.equal(xg.grad.cpu(), torch.nn.functional.pixel_unshuffle(cot, r))
+    _pixel_shuffle_cl_into_nan(C, r)
+
+
+def _pixel_shuffle_cl_into_nan(C, r, B=2, H=5, W=7):
+    """sisr_pixel_shuffle_cl called directly, both directions into NaN-pre-filled buffers, on distinct values: every
+    element is written, with the value plain indexing puts there (tests/_glue.py); r = 1: both are the identity"""
+    import _glue as R
+    hip = sisr_amd.hip
+    x = torch.arange(1, B * H * W * C * r * r + 1, dtype=torch.float32).reshape(B, H, W, C * r * r)
+    y = torch.full((B, H * r, W * r, C), float("nan"), device=DEV)
+    xd = x.to(DEV)
+    hip.check(hip.lib().sisr_pixel_shuffle_cl(xd.data_ptr(), y.data_ptr(), B, H, W, C, r, 0, hip.stream()), "sisr_pixel_shuffle_cl")
+    assert torch.equal(y.cpu(), R.pixel_shuffle_cl_ref(x, C, r))
+    back = torch.full((B, H, W, C * r * r), float("nan"), device=DEV)
+    hip.check(hip.lib().sisr_pixel_shuffle_cl(y.data_ptr(), back.data_ptr(), B, H, W, C, r, 1, hip.stream()),
+              "sisr_pixel_shuffle_cl(adjoint)")
+    assert torch.equal(back, xd) and torch.equal(back.cpu(), R.pixel_unshuffle_cl_ref(y.cpu(), C, r))
+    if r == 1:
+        assert torch.equal(y.cpu().reshape(-1), x.reshape(-1))
+
+
+@pytest.mark.parametrize("r", [1, 2, 3])
+@pytest.mark.parametrize("C", [1, 3, 64, 256])
+def test_pixel_shuffle_cl_writes_every_element_of_a_nan_buffer(C, r):
+    _pixel_shuffle_cl_into_nan(C, r)
+    _pixel_shuffle_cl_into_nan(C, r, B=1, H=1, W=1)
 
 
 def test_stack_maps_and_its_backward():
@@ -488,6 +514,23 @@ def test_stack_maps_and_its_backward():
     stack.backward(cot)
     for k, m in enumerate(maps):
         assert torch.equal(m.grad, cot[:, k].permute(0, 3, 1, 2))
+    # sisr_stack_maps called directly into NaN-pre-filled buffers: slot k holds the map, every other slot is still NaN; the
+    # reverse reads slot k only (the other slots of its source are NaN) and writes the whole map
+    hip, nan = sisr_amd.hip, float("nan")
+    for N in (2, 11):
+        for k in (0, N - 1):
+            for hw in (1, 17):
+                B = 2
+                m = torch.arange(1, B * hw * 64 + 1, dtype=torch.float32, device=DEV).reshape(B, hw, 64) + 1000 * k
+                st = torch.full((B, N, hw, 64), nan, device=DEV)
+                hip.check(hip.lib().sisr_stack_maps(m.data_ptr(), st.data_ptr(), B, hw, N, k, 0, hip.stream()), "sisr_stack_maps")
+                assert torch.equal(st[:, k], m), (N, k, hw)
+                others = [j for j in range(N) if j != k]
+                assert bool(st[:, others].isnan().all()), (N, k, hw)
+                g = torch.full((B, hw, 64), nan, device=DEV)
+                hip.check(hip.lib().sisr_stack_maps(st.data_ptr(), g.data_ptr(), B, hw, N, k, 1, hip.stream()),
+                          "sisr_stack_maps(unstack)")
+                assert torch.equal(g, m), (N, k, hw)
 
 
 def test_edsr_paper_width_vs_oracle():
