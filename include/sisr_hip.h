@@ -93,9 +93,16 @@ size_t sisr_ca_tail_bytes(void);
  *   8  64 -> 128 block-diagonal (output chunk q contracts input channels 32q .. 32q+31 only), plain epilogue;
  *   9  128 -> 64 whose input channels >= 80 are zero (second chunk: first 16 channels only), LeakyReLU epilogue;
  *  10  128 -> 64, the transpose of 8 (input chunk c feeds output channels 32c .. 32c+31 only), LeakyReLU' mask, no bias.
- * 11 / 12 (64 -> 64 only): the Winograd F(2x2,3x3) weights follow the direct packing (wpacked + 36864 floats, written by
- *   sisr_pack_conv3x3_many for jobs with r | 0x100); 11 behaves as 0 but runs the Winograd form of the persistent kernel
- *   from more than 8 x 128^2 output pixels per launch on (SISR_CONV_WINOGRAD=0: never), 12 as 7 with the Winograd form forced. */
+ * 11 / 12: the Winograd F(2x2,3x3) weights U = G g G^T follow the whole direct packing (wpacked + cin * cout * 9 floats, written
+ *   by sisr_pack_conv3x3_many for jobs with r | 0x100); 11 behaves as 0 but runs the Winograd form of the persistent kernel
+ *   from more than 8 x 128^2 output pixels per launch on (SISR_CONV_WINOGRAD=0: never), 12 as 7 with the Winograd form forced.
+ *   Shapes: 64 -> 64 in every form the persistent kernel serves, and 64 -> 64 r^2 / 64 r^2 -> 64, r >= 2 (the upsampler's
+ *   conv stored through a shuffle view and its input gradient read through one: xview and yview may differ) in the plain form: bias or none, alpha, ReLU, and none of res / mask / in_scale / in_shift /
+ *   out_scale / gap_partial / gate / dot / head / LeakyReLU; any other combination at those shapes runs the direct form.
+ *   Other channel counts: SISR_ERR_ARG.
+ *   U layout: one block of 65536 floats per pair of 64-channel chunks, block (q, c) at (q * cin / 64 + c) * 65536 -- the
+ *   (output chunk, input chunk) order and the channel maps of the direct packing -- each [xi 16][G 4][q4 4][co 64][e 4] for
+ *   transform point xi = 4 xr + xc and input channel 16 G + 4 q4 + e of the chunk. */
 /* gate_add / gate_out / dot (all nullable; 64 -> 64, x and y in one layout) fuse the gated-residual chain of
  * RCAB / QRCAB stacks (ref: advanced/architectures.py:68-71, :107-110) into the neighbouring convs:
  *   gate_add + gate_out : the conv reads  x * in_scale[b,c] + gate_add  (the previous block's `res * y + x`) and

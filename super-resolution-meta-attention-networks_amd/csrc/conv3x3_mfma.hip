@@ -998,8 +998,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_p4_kernel(ConvParams p, in
 //           No LDS beside the halo and no barrier inside the K loop: two per tile (halo free / next halo visible)
 //   epilogue: p4's arithmetic per output pixel (bias added after the transform), stores and partial sums masked to the
 //           image; GAP / DOT partials in p4's slot layout (one per (2-row strip, 32 columns)).
-template <bool AFFINE, bool MASK, bool RES, bool GATE, bool DOT>
+// CHUNKS (plain form only: bias, ReLU, alpha): any cin_chunks x cout_chunks, x and y through their own views -- the
+//   upsampler's 64 -> 64 r^2 conv stored through view_shuffle and its 64 r^2 -> 64 input gradient read through it.  A tile
+//   is walked as cout_chunks x cin_chunks items (q, c), c innermost; item (q, c) runs the 16 steps on U block q * cin_chunks
+//   + c (65536 floats apart) over the halo of input chunk c.  The output transform is linear, so the items of one q fold
+//   A^T M A into the same y registers (accumulated from zero) and the epilogue runs once per q, after the last c, with bias
+//   [co * bias_n + q * bias_q] and p.yv.chunk(q).  The halo is restaged (and the two barriers taken) only where the next
+//   item reads another one: with one input chunk it is staged once per tile and the prefetch rides on the last q's K loop.
+template <bool AFFINE, bool MASK, bool RES, bool GATE, bool DOT, bool CHUNKS = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, int total_tiles, const float* __restrict__ wu) {
+  static_assert(!CHUNKS || !(AFFINE || MASK || RES || GATE || DOT), "the chunked form is the plain one");
   constexpr int THv = 4, HHv = 6;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1008,9 +1016,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
   const int n = lane & 15, q = lane >> 4;
   const int H = p.H, W = p.W;
   const int co = coh * 32 + n;  // N block nb adds 16
-  const float bv[2] = {p.bias ? p.bias[co * p.bias_n] : 0.f, p.bias ? p.bias[(co + 16) * p.bias_n] : 0.f};
-  const sisr_rsrc_t rw = sisr_rsrc(wu);
+  float bv[2] = {(!CHUNKS && p.bias) ? p.bias[co * p.bias_n] : 0.f, (!CHUNKS && p.bias) ? p.bias[(co + 16) * p.bias_n] : 0.f};
+  sisr_rsrc_t rw = sisr_rsrc(wu);
   const unsigned boff = (unsigned)(q * 64 + co) * 16u;  // N block nb: + 256 B
+  const int cc = CHUNKS ? p.cin_chunks : 1, n_items = CHUNKS ? p.cin_chunks * p.cout_chunks : 1;
 
   const int nwg = gridDim.x;
   int t_begin = blockIdx.x, t_end = total_tiles, t_step = nwg;
@@ -1031,10 +1040,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
   // a kernel-wide array would be one live range around the tile loop)
   const int c4 = tid & 15, pcol = tid >> 4;
   typedef f32x4 halo_regs_t[HHv][3];
-  auto issue = [&](halo_regs_t& v, int tile, int r0, int r1) {  // halo rows [r0, r1)
+  auto issue = [&](halo_regs_t& v, int tile, int chunk, int r0, int r1) {  // halo rows [r0, r1) of input chunk `chunk`
     int b, h0, w0;
     decode(tile, b, h0, w0);
-    const sisr_rsrc_t rx = sisr_rsrc(p.x + (long)b * p.xv.sB);
+    const sisr_rsrc_t rx = sisr_rsrc(p.x + (long)b * p.xv.sB + (CHUNKS ? p.xv.chunk(chunk) : 0L));
 #pragma unroll
     for (int r = r0; r < r1; ++r) {
       const unsigned ro = (unsigned)(min(max(h0 - 1 + r, 0), H - 1) * (int)p.xv.sH) * 4u;
@@ -1100,21 +1109,34 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
 
   if (t_begin < t_end) {
     halo_regs_t v;
-    issue(v, t_begin, 0, HHv);
+    issue(v, t_begin, 0, 0, HHv);
     commit(v, t_begin);
   }
   __syncthreads();
-  for (int tile = t_begin; tile < t_end; tile += t_step) {
-    const bool has_next = tile + t_step < t_end;
+  f32x4 y[2][2][2];  // [nb][out row i][out col j], registers = the lane's four tiles 4q + reg
+  // one loop over (tile, item): nested, the epilogue's per-tile addresses would be hoisted over the items' K loops
+  for (int tile = t_begin, item = 0; tile < t_end; tile = (CHUNKS && item + 1 < n_items) ? tile : tile + t_step,
+           item = (CHUNKS && item + 1 < n_items) ? item + 1 : 0) {
+    // item = (output chunk oq, input chunk ic); the next item's halo is another one where the input chunk or the tile moves
+    const int oq = CHUNKS ? item / cc : 0, ic = CHUNKS ? item - oq * cc : 0;
+    const bool last_item = item + 1 == n_items, last_ic = ic + 1 == cc;
+    const int ntile = last_item ? tile + t_step : tile, nic = last_ic ? 0 : ic + 1;
+    const bool has_next = (last_item ? tile + t_step < t_end : true) && (!CHUNKS || cc > 1 || last_item);
     int b, h0, w0;
     decode(tile, b, h0, w0);
+    if (CHUNKS) {
+      rw = sisr_rsrc(wu + (long)item * (16 * 64 * 64));
+      if (ic == 0) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) y[k >> 2][(k >> 1) & 1][k & 1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      }
+    }
     // step s = xr * 4 + G; weight load t = (s * 4 + xc) * 2 + nb: B fragment U[xi = 4 xr + xc][G], 4 KB apart per (xi, G)
 #define W4_LOAD_B(t) \
   sisr_buf_load4(rw, boff, (unsigned)((((((t) >> 5) * 4 + (((t) >> 1) & 3)) * 4 + (((t) >> 3) & 3)) * 4096) + ((t) & 1) * 256))
     f32x4 bq[8];
 #pragma unroll
     for (int t = 0; t < 6; ++t) bq[t] = W4_LOAD_B(t);
-    f32x4 y[2][2][2];  // [nb][out row i][out col j], registers = the lane's four tiles 4q + reg
     f32x4 acc[4][2];   // [xc][nb] of the current xr
     f32x4 raw[4], rr[4], av[2][4];
     halo_regs_t v;  // the next tile's staged halo: written (steps 12, 14) and read (commit) under has_next only, else undefined
@@ -1156,8 +1178,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
       const int xr = s >> 2, G = s & 3;
       // the next tile's halo is requested in two halves, at steps 12 and 14 of 16 (few registers held across the K loop),
       // and written to LDS right after the loop
-      if (s == 12 && has_next) issue(v, tile + t_step, 0, 3);
-      if (s == 14 && has_next) issue(v, tile + t_step, 3, HHv);
+      if (s == 12 && has_next) issue(v, ntile, nic, 0, 3);
+      if (s == 14 && has_next) issue(v, ntile, nic, 3, HHv);
       // step s + 1 is read and transformed under the MFMAs of step s, half the columns at a time
       if (s + 1 < 16) read_half(s + 1, 0);
 #pragma unroll
@@ -1206,23 +1228,32 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
         for (int nb = 0; nb < 2; ++nb) t1[nb] = sisr_pk4_sub(t1[nb], acc[3][nb]);
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
-          if (xr == 0) { y[nb][0][0] = t0[nb]; y[nb][0][1] = t1[nb]; }
+          if (CHUNKS) {  // accumulated from zero (ic == 0) over the input chunks
+            if (xr == 0) { y[nb][0][0] = sisr_pk4_add(y[nb][0][0], t0[nb]); y[nb][0][1] = sisr_pk4_add(y[nb][0][1], t1[nb]); }
+            if (xr == 1) { y[nb][1][0] = sisr_pk4_add(y[nb][1][0], t0[nb]); y[nb][1][1] = sisr_pk4_add(y[nb][1][1], t1[nb]); }
+          } else {
+            if (xr == 0) { y[nb][0][0] = t0[nb]; y[nb][0][1] = t1[nb]; }
+            if (xr == 1) { y[nb][1][0] = t0[nb]; y[nb][1][1] = t1[nb]; }
+          }
           if (xr == 1 || xr == 2) { y[nb][0][0] = sisr_pk4_add(y[nb][0][0], t0[nb]); y[nb][0][1] = sisr_pk4_add(y[nb][0][1], t1[nb]); }
-          if (xr == 1) { y[nb][1][0] = t0[nb]; y[nb][1][1] = t1[nb]; }
           if (xr >= 2) { y[nb][1][0] = sisr_pk4_sub(y[nb][1][0], t0[nb]); y[nb][1][1] = sisr_pk4_sub(y[nb][1][1], t1[nb]); }
           // the fold happens here: sunk towards the epilogue it would keep every row's 32 accumulators live instead
 #pragma unroll
-          for (int i = 0; i < (xr == 0 ? 1 : 2); ++i) asm volatile("" : "+v"(y[nb][i][0]), "+v"(y[nb][i][1]));
+          for (int i = 0; i < ((xr == 0 && !CHUNKS) ? 1 : 2); ++i) asm volatile("" : "+v"(y[nb][i][0]), "+v"(y[nb][i][1]));
         }
       }
     }
 #undef W4_LOAD_B
-    __syncthreads();  // every wave is done with this tile's halo
-    if (has_next) commit(v, tile + t_step);
+    if (!CHUNKS || has_next) __syncthreads();  // every wave is done with this tile's halo
+    if (has_next) commit(v, ntile);
     // ---- epilogue: pixel (h0 + 2 mb + i, w0 + 8 q + 2 reg + j), channel co + 16 nb
-    {
+    if (!CHUNKS || last_ic) {
+      if (CHUNKS && p.bias) {
+        bv[0] = p.bias[co * p.bias_n + oq * p.bias_q];
+        bv[1] = p.bias[(co + 16) * p.bias_n + oq * p.bias_q];
+      }
       const bool scaled = p.out_scale != nullptr || p.alpha != 1.0f;
-      const sisr_rsrc_t ry = sisr_rsrc(p.y + (long)b * p.yv.sB);
+      const sisr_rsrc_t ry = sisr_rsrc(p.y + (long)b * p.yv.sB + (CHUNKS ? p.yv.chunk(oq) : 0L));
       const sisr_rsrc_t rmk = sisr_rsrc(MASK ? p.mask + (long)b * p.yv.sB : p.y);
       const sisr_rsrc_t rrs = sisr_rsrc(RES ? p.res + (long)b * p.yv.sB : p.y);
       const sisr_rsrc_t rdt = sisr_rsrc(DOT ? p.dot + (long)b * p.yv.sB : p.y);
@@ -1276,7 +1307,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
         for (int nb = 0; nb < 2; ++nb) p.gap[(((long)b * parts) + (th * p.tiles_w + tw) * 2 + mb) * 64 + co + 16 * nb] = gsum[nb];
       }
     }
-    __syncthreads();  // the next tile's halo is in LDS
+    if (!CHUNKS || has_next) __syncthreads();  // the next tile's halo is in LDS
   }
 }
 
@@ -2490,8 +2521,12 @@ struct PackJob {
   int cout, cin, r, first_block;  // r | SISR_PACK_WINOGRAD: see below
   int co_real, ci_real;  // > 0: w is (co_real, ci_real, 3, 3) and is packed as its zero-padded (cout, cin, 3, 3) twin (SPARNet)
 };
-// fp32 64 -> 64 jobs (r = 1) with this flag also write the Winograd F(2x2,3x3) weights U = G g G^T of both orders right
-// behind the direct packings (pf + 36864, pd + 36864; layout: conv3x3_c64_w4_kernel), from 16 more blocks of the job.
+// fp32 jobs with this flag also write the Winograd F(2x2,3x3) weights U = G g G^T of both orders right behind the whole
+// direct packings (pf + cout * cin * 9, pd + the same; layout of one 64 x 64 block: conv3x3_c64_w4_kernel), from 16 more
+// blocks of the job per pair of 64-channel chunks.  Jobs that carry it: 64 -> 64 (r = 1, one block) and the fused-shuffle
+// upsampler convs (r > 1, cin = 64, cout = 64 r^2: r^2 blocks).  Block (q, c) -- the direct packing's chunk pair, with the
+// direct packing's channel maps: forward, output chunk q = original channels n r^2 + q; input gradient, input chunk c =
+// original output channels k r^2 + c, taps flipped and roles swapped -- lies (q * cin_chunks + c) * 65536 floats in.
 #define SISR_PACK_WINOGRAD 0x100
 #define SISR_WINO_FLOATS (16 * 64 * 64)
 
@@ -2526,15 +2561,21 @@ __global__ __launch_bounds__(256) void pack_conv3x3_many_kernel(const PackJob* _
     // U[xr][xc] = sum G[xr][kh] g[kh][kw] G[xc][kw] (columns first), G = {{1, 0, 0}, {1/2, 1/2, 1/2}, {1/2, -1/2, 1/2}, {0, 0, 1}};
     // dgrad: g = the flipped, role-swapped weight
     const long k = idx - (total + 255) / 256 * 256;
-    if (k >= 64 * 64 || cout != 64 || cin != 64) return;
-    const int co = (k >> 2) & 63, ci = (int)(k >> 8) * 4 + (k & 3);
-    const long u0 = k;
+    const int rr = r * r, oc = cout >> 6, ic = cin >> 6;
+    if (k >= (long)oc * ic * 64 * 64 || cin != 64 || cout != 64 * rr) return;
+    const int pr = (int)(k >> 12), kk = (int)(k & 4095);  // chunk pair, element of its 64 x 64 block
+    const int co = (kk >> 2) & 63, ci = (kk >> 8) * 4 + (kk & 3);
+    const long u0 = (long)pr * SISR_WINO_FLOATS + kk;
     auto gmul = [](int x, float a, float b, float c) {  // row x of G times (a, b, c)
       return x == 0 ? a : (x == 3 ? c : (x == 1 ? 0.5f * (a + b + c) : 0.5f * (a - b + c)));
     };
     for (int dir = 0; dir < 2; ++dir) {
       float g9[9];
-      for (int t = 0; t < 9; ++t) g9[t] = dir == 0 ? w.at(co, ci, t) : w.at(ci, co, 8 - t);
+      // forward: pair (q = pr / ic, c = pr % ic), o = (co, q), i = c * 64 + ci; dgrad: pair (q = pr / oc, c = pr % oc),
+      // output = original input channel q * 64 + co, input = original output (ci, c)
+      const long fo = (long)co * rr + pr / ic, fi = (long)(pr % ic) * 64 + ci;
+      const long go = (long)ci * rr + pr % oc, gi = (long)(pr / oc) * 64 + co;
+      for (int t = 0; t < 9; ++t) g9[t] = dir == 0 ? w.at(fo, fi, t) : w.at(go, gi, 8 - t);
       float* dst = static_cast<float*>(dir == 0 ? jb.pf : jb.pd) + total + u0;
       for (int xc = 0; xc < 4; ++xc) {
         float rk[3];
@@ -2637,7 +2678,8 @@ static inline bool sisr_use_persistent(int variant, long nblk) {
 // The Winograd form (conv3x3_c64_w4_kernel) replaces the persistent one where the caller asserts that the packed weight
 // carries the transform (select 11: where it pays, 12: forced, with the persistent form forced as by 7), from more than
 // 8 x 128^2 output pixels per launch up: below that, gate heads and batched weight gradients change how a batch is
-// launched, and both forms must run one kernel.  SISR_CONV_WINOGRAD=0 switches it off per call.
+// launched, and both forms must run one kernel.  SISR_CONV_WINOGRAD=0 switches it off per call.  The same rule selects the
+// chunked instantiation for the plain form of the fused-shuffle upsampler convs and of their input gradients.
 #define SISR_WINO_MIN_PIXELS (8L * 128 * 128)
 static inline bool sisr_use_winograd(bool avail, bool force, long pixels) {
   if (!avail) return false;
@@ -2681,12 +2723,17 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
                                 const float* gate_add, float* gate_out, const float* dot, int B, int H, int W, int cin,
                                 int cout, const void* ca_tail, int select, void* stream) {
   if (!x || !wpacked || !y || !xview || !yview || B <= 0 || H <= 0 || W <= 0) return SISR_ERR_ARG;
-  // 11 / 12: the Winograd weights follow the direct packing (64 -> 64 only); otherwise as 0 / 7
+  // 11 / 12: the Winograd weights follow the direct packing (64 -> 64, or the shapes of a conv with a fused PixelShuffle(r)
+  // and of its input gradient, 64 -> 64 r^2 and 64 r^2 -> 64: the chunked plain form); otherwise as 0 / 7
   const bool wino_avail = select == 11 || select == 12, wino_force = select == 12;
   if (wino_avail) {
-    if (cin != 64 || cout != 64) return SISR_ERR_ARG;
+    const int wide = cin > cout ? cin : cout;
+    int r = 1;
+    while (64 * r * r < wide) ++r;
+    if ((cin != 64 && cout != 64) || wide != 64 * r * r) return SISR_ERR_ARG;
     select = wino_force ? 7 : 0;
   }
+  const bool wino_chunked = wino_avail && (cin != 64 || cout != 64);
   const sisr_ca_tail_host* head = static_cast<const sisr_ca_tail_host*>(ca_tail);
   if (head) {  // gate head: computed by this launch's workgroups from the previous launch's partial sums
     if (!head->head || cin != 64 || cout != 64 || !head->head_part || head->head_parts <= 0 || head->hidden < 1 ||
@@ -2836,6 +2883,15 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
       const size_t lb = V4_HALO_BYTES;
       if (ksel == 1) hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, false, false, false, false, 1>), g, dim3(256), lb, st, p);
       else hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, false, false, false, true, 2>), g, dim3(256), lb, st, p);
+      return sisr_check_launch();
+    }
+    if (wino_chunked && !aff && !in_shift && !msk && !rs && !leaky && !head && !out_scale && !gap_partial &&
+        sisr_use_persistent(variant, nblk) && sisr_use_winograd(true, wino_force, (long)B * H * W)) {
+      // chunked Winograd form (plain epilogue, x and y through their own views); every other form at these shapes runs direct
+      const dim3 gp((unsigned)(nblk < 512 ? nblk : 512));
+      const size_t lbp = HALO_H * HALO_W * 64 * sizeof(float);
+      const float* wu = wpacked + (long)cin * cout * 9;
+      hipLaunchKernelGGL((conv3x3_c64_w4_kernel<false, false, false, false, false, true>), gp, dim3(256), lbp, st, p, (int)nblk, wu);
       return sisr_check_launch();
     }
     if (!(in_shift && !in_scale) && !(aff && !msk) && !(msk && rs) && !leaky && !head && cin == 64 && cout == 64 &&

@@ -174,7 +174,7 @@ _STEP_PACKS = {}
 
 
 _PACK_WINOGRAD = 0x100  # PackJob.r flag (conv3x3_mfma.hip: SISR_PACK_WINOGRAD)
-WINOGRAD_FLOATS = 16 * 64 * 64  # transformed 64 -> 64 weight, behind the 64 * 64 * 9 direct packing
+WINOGRAD_FLOATS = 16 * 64 * 64  # transformed 64 x 64 weight block, behind the whole direct packing: one per pair of chunks
 SELECT_WINOGRAD, SELECT_WINOGRAD_FORCE = 11, 12  # `select` codes: the packed weight carries the transform (auto / forced)
 
 
@@ -188,10 +188,12 @@ class _PackPlan:
         # a weight whose channel counts are not multiples of 64 (SPARNet) is packed as its zero-padded twin, same launch
         padded = [(_pad64(w.shape[0]), _pad64(w.shape[1])) for w, _ in self.items]
         numel = [co * ci * 9 for co, ci in padded]
-        # fp32 64 -> 64 weights also get their Winograd F(2x2,3x3) transform right behind the direct packing (both orders);
+        # fp32 64 -> 64 weights, and the 64 -> 64 r^2 weights of a conv with a fused PixelShuffle(r), also get their Winograd
+        # F(2x2,3x3) transform right behind the direct packing (both orders, one block per pair of 64-channel chunks);
         # conv_c64 sees it in the slice length and lets the library use the Winograd kernel where it pays
-        wino = [PRECISION == "fp32" and r == 1 and p == (64, 64) == tuple(w.shape[:2]) for (w, r), p in zip(self.items, padded)]
-        extra = [WINOGRAD_FLOATS if k else 0 for k in wino]
+        wino = [PRECISION == "fp32" and p == (64 * r * r, 64) == tuple(w.shape[:2]) for (w, r), p in zip(self.items, padded)]
+        pairs = [(co // 64) * (ci // 64) for co, ci in padded]
+        extra = [pairs[k] * WINOGRAD_FLOATS if wino[k] else 0 for k in range(len(wino))]
         total = planes * sum(numel) + sum(extra)
         dt = torch.float32 if PRECISION == "fp32" else torch.bfloat16
         self.fwd = torch.empty(total, device=device, dtype=dt)
@@ -210,7 +212,7 @@ class _PackPlan:
                        padded[k][1], r | (_PACK_WINOGRAD if wino[k] else 0), blocks, real[0], real[1])
             self.slices.append((self.fwd[off:off + n], self.dgrad[off:off + n]))
             off += n
-            blocks += (numel[k] + 255) // 256 + (16 if wino[k] else 0)  # + one thread per (ci, co) for the transform
+            blocks += (numel[k] + 255) // 256 + (16 * pairs[k] if wino[k] else 0)  # + one thread per (ci, co) for the transform
         self.blocks = blocks
         self.jobs = torch.from_numpy(jobs.view(np.uint8)).to(device)
 
@@ -359,7 +361,7 @@ def conv_c64(x, xview, packed, bias, bias_nq, y, yview, B, H, W, cin, cout, res=
     # the packing decides: a weight packed under one mode runs under it (three bf16 planes = the bf16x3 split)
     if packed.dtype != torch.bfloat16:
         import ctypes
-        if select == 0 and cin == 64 and cout == 64 and packed.numel() == 64 * 64 * 9 + WINOGRAD_FLOATS:
+        if select == 0 and packed.numel() == cin * cout * 9 + (cin // 64) * (cout // 64) * WINOGRAD_FLOATS:
             select = SELECT_WINOGRAD
         rc = L.sisr_conv3x3_c64(hip.ptr(x), xview, _wptr(packed), hip.ptr(bias), bias_nq[0], bias_nq[1], hip.ptr(y), yview,
                                 hip.ptr(res), hip.ptr(mask), hip.ptr(in_scale), hip.ptr(in_shift), hip.ptr(out_scale),

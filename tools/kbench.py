@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the hot kernels through the C ABI (HIP-event timing, one process).
 
-    python tools/kbench.py [--batch 8] [--iters 20] [--only conv,wgrad,...] [--winograd]
+    python tools/kbench.py [--batch 8] [--iters 20] [--only conv,wgrad,conv_up128,dgrad_up256,...] [--winograd]
 Prints one JSON line per kernel: mean launch time and achieved TFLOP/s (or GB/s) on 128x128x64 maps.
 Used for interleaved A/B of kernel variants and as the target of rocprofv3 --pmc passes.
 """
@@ -143,6 +143,29 @@ def main():
     run("wgrad_affine", lambda: ops.wgrad_c64(x, v, dy, v, dw, db, B, H, W, 64, 64, dy_scale=sc, dy_shift=sh), flop,
         "TFLOP/s")
     run("pack", lambda: ops.pack_weight(w, "fwd"), 2 * 36864 * 4, "GB/s")
+    # the x4 upsampler's two fused-shuffle stages: 64 -> 256 stored through view_shuffle and the 256 -> 64 input gradient read
+    # through it, at B x 128^2 and B x 256^2 (--winograd: the chunked Winograd form above 8 x 128^2 pixels)
+    if a.precision == "fp32" and (not only or only & {"conv_up128", "dgrad_up128", "conv_up256", "dgrad_up256"}):
+        wu = (torch.randn(256, 64, 3, 3, generator=g) * 0.05).to(dev)
+        bu = torch.randn(256, generator=g).to(dev)
+        if a.winograd:
+            plan = ops._PackPlan([(wu, 2)], wu.device)
+            plan.run()
+            ops.invalidate_packs()
+            puf, pud = plan.slices[0]
+        else:
+            puf, pud = ops.pack_pair(wu, 2)
+        for hw in (128, 256):
+            if only and not only & {f"conv_up{hw}", f"dgrad_up{hw}"}:
+                continue
+            xs = torch.randn(B, 64, hw, hw, generator=g).to(dev).contiguous(memory_format=cl)
+            ys = torch.randn(B, 64, 2 * hw, 2 * hw, generator=g).to(dev).contiguous(memory_format=cl)
+            dxs = torch.empty_like(xs)
+            vp, vs = hip.view_plain(hw, hw, 64), hip.view_shuffle(hw, hw, 2)
+            fl = 2.0 * B * hw * hw * 64 * 256 * 9
+            run(f"dgrad_up{hw}", lambda: ops.conv_c64(ys, vs, pud, None, (1, 64), dxs, vp, B, hw, hw, 256, 64), fl, "TFLOP/s")
+            run(f"conv_up{hw}", lambda: ops.conv_c64(xs, vp, puf, bu, (4, 1), ys, vs, B, hw, hw, 64, 256), fl, "TFLOP/s")
+            del xs, ys, dxs
     L = hip.lib()
     parts = L.sisr_gate_dg_parts(H * W)
     dgp = torch.empty(B, parts, 64, device=dev)
