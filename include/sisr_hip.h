@@ -331,6 +331,11 @@ int sisr_nl_attn_bwd(const float* theta, const float* phi, const float* g, const
  * ref: SISR/models/__init__.py:268 nn.L1Loss, :299-308 optim.Adam, :481-489 standard_update */
 size_t sisr_l1_loss_workspace_bytes(void);
 int sisr_l1_loss(const float* a, const float* b, long n, float* loss, float* grad, float* workspace, void* stream);
+/* The same loss and gradient with the sums kept in double and divided by n: the value is the mean rounded to fp32 once
+ * (sisr_l1_loss multiplies an fp32 sum by a rounded 1 / n).  workspace: 16-byte aligned (SISR_ERR_ALIGN otherwise). */
+size_t sisr_l1_loss_mean_workspace_bytes(void);
+int sisr_l1_loss_mean(const float* a, const float* b, long n, float* loss, float* grad, double* workspace,
+                      void* stream);
 /* torch.optim.Adam's update over one flat range (parameters, gradients, exp_avg, exp_avg_sq laid out alike):
  * one_minus_beta*, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t) computed by the host in double;
  * gradients are read as g * grad_scale.  p, g, m and v must be 16-byte aligned (SISR_ERR_ALIGN, -2, otherwise: the
@@ -639,6 +644,26 @@ int sisr_mse_loss(const float* a, const float* b, long n, float* loss, float* gr
  * any launch: null pointers, n, c, h or w <= 0 (-1); more than 2^31 - 1 tiles of 64 x 64 (-4). */
 int sisr_dihedral_fan(const float* x, int n, int c, int h, int w, float* upright, float* turned, void* stream);
 int sisr_dihedral_merge(const float* upright, const float* turned, int n, int c, int H, int W, float* out, void* stream);
+
+/* ---- perceptual (VGG19 feature) loss: everything but the convolutions (csrc/perceptual.hip) ---------------------------
+ * ref: sr_tools/loss_functions.py:6-22 PerceptualMechanism, SISR/models/feature_extractors/VGGNets.py:118-131
+ * VGGFeatureExtractor ((img - mean) / std, then torchvision's vgg19.features[:35]: 3x3 convs + ReLU, four MaxPool2d(2, 2)).
+ * The convs run on sisr_conv3x3_c64; these are the streams around them.  Maps are channels-last fp32 with a 64-multiple of
+ * channels, images planar (B,3,H,W) fp32; mean3 / std3: three floats on the device.
+ * sisr_vgg_prep_fwd: out[b,h,w,c] = (img[b,c,h,w] - mean3[c]) / std3[c] for c < 3 -- an IEEE subtraction, then a correctly
+ *   rounded division, bit for bit torch's fp32 expression -- and 0 for 3 <= c < cp.
+ * sisr_vgg_prep_bwd: dimg[b,c,h,w] = gmap[b,h,w,c] / std3[c], c < 3 (channels >= 3 of gmap are not read).
+ * sisr_maxpool2_fwd: out (B, H/2, W/2, C) = MaxPool2d(2, 2)(y), floor mode: an odd last row / column is dropped.
+ * sisr_maxpool2_relu_bwd: the input gradient of maxpool2(y) for a post-ReLU map y with that ReLU's derivative applied:
+ *   dy[p] = dout[window(p)] if p holds the first maximum of its window, in the scan order (0,0), (0,1), (1,0), (1,1), and
+ *   y[p] > 0; else 0.  Pixels outside every window get 0.  A gather: no atomics, a repeat call is bit-identical.
+ * One launch each.  Refused before any launch: null pointers, B, H, W or the channel count <= 0 (-1); a channel count that
+ * is not a multiple of 64, H < 2 or W < 2 for the pool (-4); a map that is not 16-byte aligned (-2). */
+int sisr_vgg_prep_fwd(const float* img, const float* mean3, const float* std3, float* out, int B, int H, int W, int cp,
+                      void* stream);
+int sisr_vgg_prep_bwd(const float* gmap, const float* std3, float* dimg, int B, int H, int W, int cp, void* stream);
+int sisr_maxpool2_fwd(const float* y, float* out, int B, int H, int W, int C, void* stream);
+int sisr_maxpool2_relu_bwd(const float* y, const float* dout, float* dy, int B, int H, int W, int C, void* stream);
 
 #ifdef __cplusplus
 }

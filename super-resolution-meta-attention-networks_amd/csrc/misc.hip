@@ -6,16 +6,20 @@
 //          m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;
 //          p -= lr / (1-b1^t) * m / (sqrt(v) / sqrt(1-b2^t) + eps)
 // Both are single-pass HBM-bound streams; the loss reduction is two-stage and ordered.
+// sisr_l1_loss keeps the sums in fp32 and multiplies by a rounded 1 / N; sisr_l1_loss_mean keeps them in double and divides by
+// N, so the value is the mean rounded to fp32 once (what a criterion that is compared with float64 to a fraction of an fp32
+// unit needs: the rounded reciprocal alone costs up to 1.5 units).  The gradients of the two are the same.
 #include "sisr_common.h"
 #include <string.h>
 
 #define L1_BLOCKS 512
 
+template <typename Acc>
 __global__ __launch_bounds__(256) void l1_partial_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                          float* __restrict__ grad, float inv_n, long n,
-                                                         float* __restrict__ part) {
-  __shared__ float red[256];
-  float s = 0.f;
+                                                         Acc* __restrict__ part) {
+  __shared__ Acc red[256];
+  Acc s = 0;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const float d = a[i] - b[i];
     s += fabsf(d);
@@ -30,10 +34,12 @@ __global__ __launch_bounds__(256) void l1_partial_kernel(const float* __restrict
   if (threadIdx.x == 0) part[blockIdx.x] = red[0];
 }
 
-__global__ __launch_bounds__(256) void l1_final_kernel(const float* __restrict__ part, int nparts, float inv_n,
+// Acc = float: loss = sum * inv_n;  Acc = double: loss = (float)(sum / n)
+template <typename Acc>
+__global__ __launch_bounds__(256) void l1_final_kernel(const Acc* __restrict__ part, int nparts, float inv_n, long n,
                                                        float* __restrict__ loss) {
-  __shared__ float red[256];
-  float s = 0.f;
+  __shared__ Acc red[256];
+  Acc s = 0;
   for (int i = threadIdx.x; i < nparts; i += 256) s += part[i];
   red[threadIdx.x] = s;
   __syncthreads();
@@ -41,23 +47,40 @@ __global__ __launch_bounds__(256) void l1_final_kernel(const float* __restrict__
     if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
     __syncthreads();
   }
-  if (threadIdx.x == 0) *loss = red[0] * inv_n;
+  if (threadIdx.x == 0) {
+    if (sizeof(Acc) == sizeof(float)) *loss = (float)red[0] * inv_n;
+    else *loss = (float)(red[0] / (Acc)n);
+  }
+}
+
+template <typename Acc>
+static int l1_loss_launch(const float* a, const float* b, long n, float* loss, float* grad, Acc* part, void* stream) {
+  if (!a || !b || !loss || !part || n <= 0) return SISR_ERR_ARG;
+  long blocks = (n + 255) / 256;
+  if (blocks > L1_BLOCKS) blocks = L1_BLOCKS;
+  const float inv_n = 1.0f / (float)n;
+  hipLaunchKernelGGL(l1_partial_kernel<Acc>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, grad, inv_n, n,
+                     part);
+  int rc = sisr_check_launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL(l1_final_kernel<Acc>, dim3(1), dim3(256), 0, (hipStream_t)stream, (const Acc*)part, (int)blocks, inv_n, n,
+                     loss);
+  return sisr_check_launch();
 }
 
 extern "C" size_t sisr_l1_loss_workspace_bytes() { return L1_BLOCKS * sizeof(float); }
 
 extern "C" int sisr_l1_loss(const float* a, const float* b, long n, float* loss, float* grad, float* workspace,
                             void* stream) {
-  if (!a || !b || !loss || !workspace || n <= 0) return SISR_ERR_ARG;
-  long blocks = (n + 255) / 256;
-  if (blocks > L1_BLOCKS) blocks = L1_BLOCKS;
-  const float inv_n = 1.0f / (float)n;
-  hipLaunchKernelGGL(l1_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, grad, inv_n, n,
-                     workspace);
-  int rc = sisr_check_launch();
-  if (rc) return rc;
-  hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, workspace, (int)blocks, inv_n, loss);
-  return sisr_check_launch();
+  return l1_loss_launch<float>(a, b, n, loss, grad, workspace, stream);
+}
+
+extern "C" size_t sisr_l1_loss_mean_workspace_bytes() { return L1_BLOCKS * sizeof(double); }
+
+extern "C" int sisr_l1_loss_mean(const float* a, const float* b, long n, float* loss, float* grad, double* workspace,
+                                 void* stream) {
+  if (!sisr_aligned16(workspace)) return SISR_ERR_ALIGN;
+  return l1_loss_launch<double>(a, b, n, loss, grad, workspace, stream);
 }
 
 // torch.optim.Adam (no amsgrad, no weight decay) over one flat fp32 range, in torch's operation order:

@@ -61,6 +61,8 @@ class BaseModel(nn.Module):
         # <= 4 tiles per GPU the ~3700 launches of an RCAN step cost more host time than GPU time)
         self.use_graph = os.environ.get("SISR_GRAPH", "0") == "1"
         self._graphs = {}
+        # file of VGG19 weights for training_setup(perceptual=...); a model parameter, so it can sit in a config's internal_params
+        self.perceptual_weights = kwargs.get('perceptual_weights')
 
     # -- optimiser / scheduler (ref :292-335)
     def define_optimizer(self, lr=1e-4, optimizer_params=None):
@@ -105,8 +107,27 @@ class BaseModel(nn.Module):
             if scheduler is not None:
                 self.define_scheduler(scheduler=scheduler, scheduler_params=scheduler_params)
         if perceptual is not None and self.eval_mode is False:
-            raise NotImplementedError('perceptual (VGG) loss is outside the HIP hot path; every sample config '
-                                      'of the reference uses perceptual=None')
+            self.criterion = self._perceptual_criterion(perceptual)
+
+    def _perceptual_criterion(self, lambda_per):
+        """ref: models/__init__.py:341-342 PerceptualMechanism(lambda_per=perceptual, device=device), with the extractor's weights
+        read from a local file (perceptual.load_vgg19_weights) instead of fetched.  The extractor hangs off the criterion, not
+        off self.net: the optimiser, the gradient reducer, the step-level weight packing and checkpoints never see it."""
+        from . import perceptual
+        name = type(self).__name__
+        if 'rgb' not in (self.colorspace or ''):
+            raise NotImplementedError("perceptual loss: %s works in the %r colorspace, the VGG19 feature extractor reads "
+                                      "three-channel RGB images" % (name, self.colorspace))
+        ops._fp32_only("perceptual loss (%s)" % name)
+        path = self.perceptual_weights or os.environ.get("SISR_VGG19_WEIGHTS")
+        if not path:
+            raise RuntimeError("perceptual loss (%s, perceptual=%r) needs a file of VGG19 weights, which is never fetched: pass "
+                               "perceptual_weights=<path> to the handler (a model parameter) or set SISR_VGG19_WEIGHTS; the "
+                               "file is torchvision's vgg19 state dict, or one with the reference's vgg19_54.* keys"
+                               % (name, lambda_per))
+        criterion = perceptual.PerceptualMechanism(lambda_per=lambda_per)
+        perceptual.load_vgg19_weights(criterion.vgg_extractor, path)
+        return criterion.to(self.device)
 
     def set_multi_gpu(self, device_ids=None, bucket_mb=None):
         """One process per GPU: gradients are averaged over the torch.distributed (RCCL) world.  bucket_mb: size of the

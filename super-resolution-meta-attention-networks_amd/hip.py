@@ -53,6 +53,8 @@ _SIGS = {
     "sisr_sum_partials": (c_int, [P, c_int, c_int, c_int, c_float, P, P]),
     "sisr_l1_loss_workspace_bytes": (c_size_t, []),
     "sisr_l1_loss": (c_int, [P, P, c_long, P, P, P, P]),
+    "sisr_l1_loss_mean_workspace_bytes": (c_size_t, []),
+    "sisr_l1_loss_mean": (c_int, [P, P, c_long, P, P, P, P]),
     "sisr_crop_augment": (c_int, [P, P, P, c_int, c_int, c_int, P]),
     "sisr_adam_flat": (c_int, [P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_float, c_float, c_float, P]),
     "sisr_host_flags_alloc": (P, [c_int]),
@@ -205,6 +207,13 @@ _SIGS.update({  # geometric self-ensemble: the eight flips / transposes of a bat
     "sisr_dihedral_merge": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P]),
 })
 
+
+_SIGS.update({  # perceptual (VGG19 feature) loss: input normalisation and the 2 x 2 max-pool, both ways (csrc/perceptual.hip)
+    "sisr_vgg_prep_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    "sisr_vgg_prep_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
+    "sisr_maxpool2_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
+    "sisr_maxpool2_relu_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
+})
 
 GM_MAXL = 4
 

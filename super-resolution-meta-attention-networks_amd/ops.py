@@ -23,6 +23,8 @@ Operators
   pixel_shuffle  nn.PixelShuffle on channels-last maps wider than 64 channels (64-wide: fused into the conv's store)
   conv_y2f / conv_f2y / conv_kxk / mse_loss         SRCNN, VDSR: K x K convs, the Y-channel ends, nn.MSELoss
                  (ref: basic/architectures.py:6-77, basic/handlers.py:14)
+  frozen_features / FrozenChain    the perceptual loss's VGG19 feature extractor: frozen, once-packed convs, max-pools,
+                 input-gradient-only backward (ref: feature_extractors/VGGNets.py:118-131, sr_tools/loss_functions.py:6-22)
 """
 import os
 
@@ -1688,6 +1690,135 @@ def nchw_to_nhwc_pad(x, cp=None):
     return y
 
 
+# ----------------------------------------------------------------------------- frozen feature extractor (csrc/perceptual.hip)
+class FrozenChain:
+    """The device-side form of a frozen stack of 3x3 convs with 2x2 max-pools between its blocks (VGG19's features[:35] for
+    the perceptual loss, perceptual.VGGFeatureExtractor): forward and input-gradient packings of every weight, zero-padded to
+    64-channel multiples, built ONCE from the weights as they are now and owned by whoever holds this object -- they are not
+    entries of the step-level packing, so invalidate_packs() (which follows every optimiser step of the trainable network)
+    leaves them alone.  blocks: [[(weight, bias), ...], ...], a pool after every block but the last; ReLU after every conv but
+    the very last.  mean / std: the three input-normalisation constants each (None: the image goes in as it is)."""
+
+    def __init__(self, blocks, mean=None, std=None):
+        _fp32_only("the frozen feature extractor")
+        first = blocks[0][0][0]
+        dev = first.device
+        if first.shape[1] != 3:
+            raise NotImplementedError(f"the feature extractor reads RGB images; its first conv takes {first.shape[1]} channels")
+        self.device = dev
+        self.mean = torch.as_tensor([0.0] * 3 if mean is None else mean, dtype=torch.float32).reshape(3).to(dev).contiguous()
+        self.std = torch.as_tensor([1.0] * 3 if std is None else std, dtype=torch.float32).reshape(3).to(dev).contiguous()
+        self.blocks = []
+        cin_p = 64
+        with torch.no_grad():
+            for convs in blocks:
+                layers = []
+                for w, b in convs:
+                    if w.requires_grad or (b is not None and b.requires_grad):
+                        raise RuntimeError("FrozenChain takes frozen weights (requires_grad == False); trainable stacks go "
+                                           "through conv_chain")
+                    co, ci = w.shape[0], w.shape[1]
+                    if tuple(w.shape[2:]) != (3, 3) or ci > cin_p:
+                        raise RuntimeError(f"frozen chain: a {tuple(w.shape)} weight does not follow a {cin_p}-channel map")
+                    cop = _pad64(co)
+                    wp = _pad_oihw(w.detach(), cop, cin_p)
+                    bp = _pad_oihw(b.detach().reshape(co, 1), cop, 1).reshape(cop) if b is not None else None
+                    pf, pd = pack_pair(wp)
+                    layers.append((pf, pd, bp, cin_p, cop))
+                    cin_p = cop
+                self.blocks.append(layers)
+        self.channels = blocks[-1][-1][0].shape[0]
+
+
+def _maxpool2(y, B, H, W, C):
+    out = _empty_cl(B, C, H // 2, W // 2, y.device)
+    hip.check(hip.lib().sisr_maxpool2_fwd(hip.ptr(y), hip.ptr(out), B, H, W, C, hip.stream()), "sisr_maxpool2_fwd")
+    return out
+
+
+class _FrozenFeatures(Function):
+    """phi(img) for a FrozenChain as ONE autograd node: normalise + lay out channels-last (sisr_vgg_prep_fwd), the blocks'
+    convs with their ReLU epilogues, sisr_maxpool2_fwd between blocks.  No weight gradients exist, so the backward is the
+    chain of input-gradient convs alone -- inside a block with the ReLU-mask epilogue, across a pool through
+    sisr_maxpool2_relu_bwd (pool routing and the ReLU in front of it in one pass over the saved map), sisr_vgg_prep_bwd at
+    the end -- and all it keeps from the forward pass are the post-ReLU conv outputs.  Without a gradient to return (the
+    target's features, evaluation) nothing is kept at all."""
+
+    @staticmethod
+    def forward(ctx, img, chain):
+        B, C, H, W = img.shape
+        if C != 3:
+            raise RuntimeError(f"the feature extractor reads (B, 3, H, W) RGB images, got {tuple(img.shape)}")
+        dev = img.device
+        if dev != chain.device:
+            raise RuntimeError(f"feature extractor packed on {chain.device}, image on {dev}")
+        L = hip.lib()
+        keep = ctx.needs_input_grad[0]
+        cur = _empty_cl(B, 64, H, W, dev)
+        hip.check(L.sisr_vgg_prep_fwd(hip.ptr_c(img), hip.ptr(chain.mean), hip.ptr(chain.std), hip.ptr(cur), B, H, W,
+                                      64, hip.stream()), "sisr_vgg_prep_fwd")
+        saved, geo = [], []
+        nb = len(chain.blocks)
+        for bi, layers in enumerate(chain.blocks):
+            for li, (pf, _, bp, cin_p, cop) in enumerate(layers):
+                last = bi == nb - 1 and li == len(layers) - 1
+                y = _empty_cl(B, cop, H, W, dev)
+                conv_c64(cur, hip.view_plain(H, W, cin_p), pf, bp, (1, 64), y, hip.view_plain(H, W, cop), B, H, W, cin_p, cop,
+                         relu=0 if last else 1)
+                if keep and not last:
+                    saved.append(y)
+                cur = y
+            geo.append((H, W))
+            if bi < nb - 1:
+                cur = _maxpool2(cur, B, H, W, layers[-1][4])
+                H, W = H // 2, W // 2
+        if keep:
+            ctx.save_for_backward(*saved)
+            ctx.chain, ctx.geo, ctx.B = chain, geo, B
+        return cur
+
+    @staticmethod
+    def backward(ctx, dy):
+        global IN_BACKWARD
+        IN_BACKWARD = True
+        try:
+            chain, geo, B = ctx.chain, ctx.geo, ctx.B
+            saved = list(ctx.saved_tensors)  # post-ReLU outputs of every conv but the last, in forward order
+            dev = dy.device
+            L = hip.lib()
+            g = _cl(dy)
+            k = len(saved)  # index of the current conv's output among `saved` (the last conv's is not there)
+            for bi in range(len(chain.blocks) - 1, -1, -1):
+                H, W = geo[bi]
+                layers = chain.blocks[bi]
+                for li in range(len(layers) - 1, -1, -1):
+                    _, pd, _, cin_p, cop = layers[li]
+                    k -= 1  # saved[k]: the map this conv read, where that is a conv output of the same block
+                    gin = _empty_cl(B, cin_p, H, W, dev)
+                    conv_c64(g, hip.view_plain(H, W, cop), pd, None, (1, 64), gin, hip.view_plain(H, W, cin_p), B, H, W, cop,
+                             cin_p, mask=saved[k] if li > 0 else None)
+                    g = gin
+                if bi > 0:  # g: gradient of the pooled map -> gradient of the previous block's last conv, before its ReLU
+                    Hp, Wp = geo[bi - 1]
+                    y = saved[k]
+                    gy = torch.empty_like(y)
+                    hip.check(L.sisr_maxpool2_relu_bwd(hip.ptr(y), hip.ptr(g), hip.ptr(gy), B, Hp, Wp, y.shape[1], hip.stream()),
+                              "sisr_maxpool2_relu_bwd")
+                    g = gy
+            H, W = geo[0]
+            dimg = torch.empty((B, 3, H, W), device=dev, dtype=torch.float32)
+            hip.check(L.sisr_vgg_prep_bwd(hip.ptr(g), hip.ptr(chain.std), hip.ptr(dimg), B, H, W, 64, hip.stream()),
+                      "sisr_vgg_prep_bwd")
+            return dimg, None
+        finally:
+            IN_BACKWARD = False
+
+
+def frozen_features(img, chain):
+    """(B, 3, H, W) RGB image -> channels-last feature map of `chain` (a FrozenChain); differentiable in the image only."""
+    return _FrozenFeatures.apply(img, chain)
+
+
 # ----------------------------------------------------------------------------- SPARNet pieces (csrc/sparnet.hip)
 def _padded_packs(weight, cop, cip, need_dgrad):
     """(forward packing, input-gradient packing | None) of `weight` zero-padded to (cop, cip, 3, 3): the step-level packing
@@ -3240,27 +3371,31 @@ def scale_add(a, r, gamma):
 # ----------------------------------------------------------------------------- L1 loss
 class _L1Loss(Function):
     @staticmethod
-    def forward(ctx, a, b):
+    def forward(ctx, a, b, rounded_once=False):
         a, b = a.contiguous(), b.contiguous()
         if a.shape != b.shape:
             raise RuntimeError(f"l1_loss shape mismatch {tuple(a.shape)} vs {tuple(b.shape)}")
         L = hip.lib()
         loss = torch.empty((), device=a.device, dtype=torch.float32)
         grad = torch.empty_like(a) if ctx.needs_input_grad[0] else None
-        ws = hip.workspace(a.device, L.sisr_l1_loss_workspace_bytes())
-        hip.check(L.sisr_l1_loss(hip.ptr(a), hip.ptr(b), a.numel(), hip.ptr(loss), hip.ptr(grad), hip.ptr(ws),
-                                 hip.stream()), "sisr_l1_loss")
+        fn, nbytes = ((L.sisr_l1_loss_mean, L.sisr_l1_loss_mean_workspace_bytes()) if rounded_once else
+                      (L.sisr_l1_loss, L.sisr_l1_loss_workspace_bytes()))
+        ws = hip.workspace(a.device, nbytes)
+        hip.check(fn(hip.ptr(a), hip.ptr(b), a.numel(), hip.ptr(loss), hip.ptr(grad), hip.ptr(ws), hip.stream()),
+                  "sisr_l1_loss")
         ctx.save_for_backward(grad)
         return loss
 
     @staticmethod
     def backward(ctx, go):
         (grad,) = ctx.saved_tensors
-        return grad * go, None
+        return grad * go, None, None
 
 
-def l1_loss(a, b):
-    return _L1Loss.apply(a, b)
+def l1_loss(a, b, rounded_once=False):
+    """mean |a - b|.  rounded_once: the sums are kept in double and divided by n, so the value is the mean rounded to fp32 once;
+    otherwise an fp32 sum times a rounded 1 / n (up to 1.5 fp32 units further off).  The gradient is the same either way."""
+    return _L1Loss.apply(a, b, rounded_once)
 
 
 # ----------------------------------------------------------------------------- SRCNN / VDSR pieces (csrc/basic.hip)

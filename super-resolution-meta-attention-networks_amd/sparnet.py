@@ -33,7 +33,7 @@ from torch import nn
 
 from . import architectures as A
 from . import ops
-from .handlers import BaseModel, QModel, L1Loss
+from .handlers import BaseModel, QModel
 
 
 class NormLayer(nn.Module):
@@ -328,7 +328,9 @@ class SPARNetHandler(BaseModel):
         self.activate_device()
         self.training_setup(lr, scheduler, scheduler_params, perceptual, device)
         self.model_name = 'sparnet'
-        self.criterion = L1Loss()
+        # The reference sets criterion = nn.L1Loss() here again (SPARNet/handlers.py:17), which discards the criterion that
+        # training_setup(perceptual=...) has just built.  Intentional difference: it is kept (BaseModel starts with L1Loss, so
+        # perceptual=None trains on L1 as before).
         self.scale = scale
 
 
@@ -344,5 +346,4 @@ class QSPARNetHandler(QModel):
         self.activate_device()
         self.training_setup(lr, scheduler, scheduler_params, perceptual, device)
         self.model_name = 'qsparnet'
-        self.criterion = L1Loss()
-        self.scale = scale
+        self.scale = scale  # the criterion stays training_setup's, as above
