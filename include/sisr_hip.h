@@ -596,6 +596,23 @@ size_t sisr_ssim_workspace_bytes(int n, int h, int w);
 int sisr_ssim(const float* a, const float* b, int n, int channels, int h, int w, double data_range, double* out,
               void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- structural (SSIM) training loss (csrc/ssim_loss.hip) -------------------------------------------------------------
+ * The mean SSIM of two batches and its gradient with respect to the first (no counterpart in the reference; the loss
+ * pixel term + alpha (1 - mean SSIM) of structural.StructuralMechanism).  sr, y: `planes` contiguous fp32 planes [planes][h][w]
+ * (a (B, C, H, W) batch is B * C planes), each compared as given: no clipping, no Y conversion.  Per plane the quantity of
+ * sisr_ssim: Gaussian window (11 taps, sigma 1.5), population covariance, C1 = (0.01 R)^2, C2 = (0.03 R)^2, on the
+ * (h - 10) x (w - 10) windows inside the image, all in float64.  value: one float on the device, the mean of S over all
+ * windows of all planes -- double sums in a fixed order, divided by the count, rounded to fp32 once.  grad (optional):
+ * [planes][h][w] fp32, d value / d sr; y takes none.  Two launches, three with grad; no atomics: a repeat call is
+ * bit-identical.  No allocation and no host synchronisation: capturable.  workspace: the tile sums and, with grad, three
+ * float64 coefficient maps on the window grid (24 bytes per window).  Refused before any launch: null sr / y / value /
+ * workspace, planes <= 0, h or w < 11, data_range not finite or <= 0, workspace_bytes <
+ * sisr_ssim_loss_workspace_bytes(planes, h, w, grad != NULL) (-1); a workspace that is not 16-byte aligned or a float
+ * pointer that is not 4-byte aligned (-2); more than 2^31 - 1 tiles (-4). */
+size_t sisr_ssim_loss_workspace_bytes(int planes, int h, int w, int want_grad);
+int sisr_ssim_loss(const float* sr, const float* y, int planes, int h, int w, double data_range, float* value,
+                   float* grad /* nullable */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- SRCNN / VDSR building blocks (csrc/basic.hip) ------------------------------------------------------------------
  * ref: SISR/models/basic/architectures.py (SRCNN, VDSR: K x K convs, padding K/2), basic/handlers.py (nn.MSELoss).
  * K odd, 1..9.  Maps between layers: channels-last, cp = 32 or 64 channels (real channels first, the rest zero); the image

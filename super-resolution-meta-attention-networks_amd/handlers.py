@@ -63,6 +63,12 @@ class BaseModel(nn.Module):
         self._graphs = {}
         # file of VGG19 weights for training_setup(perceptual=...); a model parameter, so it can sit in a config's internal_params
         self.perceptual_weights = kwargs.get('perceptual_weights')
+        # weight of the structural term alpha * (1 - SSIM(sr, y)) added to the criterion by training_setup (None / 0: no such
+        # term), and the data range of its constants; model parameters as well (no counterpart in the reference)
+        self.ssim_loss = kwargs.get('ssim_loss')
+        self.ssim_data_range = kwargs.get('ssim_data_range', 1.0)
+        if self.ssim_loss is not None and not self.ssim_loss >= 0:
+            raise ValueError("ssim_loss: the weight of the structural term must be >= 0; got %r" % (self.ssim_loss,))
 
     # -- optimiser / scheduler (ref :292-335)
     def define_optimizer(self, lr=1e-4, optimizer_params=None):
@@ -108,6 +114,10 @@ class BaseModel(nn.Module):
                 self.define_scheduler(scheduler=scheduler, scheduler_params=scheduler_params)
         if perceptual is not None and self.eval_mode is False:
             self.criterion = self._perceptual_criterion(perceptual)
+        if self.ssim_loss is not None and self.ssim_loss != 0 and self.eval_mode is False:
+            # every handler sets its criterion before it calls training_setup: whichever it is becomes the pixel term
+            from . import structural
+            self.criterion = structural.StructuralMechanism(self.criterion, self.ssim_loss, self.ssim_data_range)
 
     def _perceptual_criterion(self, lambda_per):
         """ref: models/__init__.py:341-342 PerceptualMechanism(lambda_per=perceptual, device=device), with the extractor's weights

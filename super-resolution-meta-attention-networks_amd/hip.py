@@ -215,6 +215,11 @@ _SIGS.update({  # perceptual (VGG19 feature) loss: input normalisation and the 2
     "sisr_maxpool2_relu_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
 })
 
+_SIGS.update({  # structural (SSIM) loss: mean SSIM and its gradient, float64 window statistics (csrc/ssim_loss.hip)
+    "sisr_ssim_loss_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "sisr_ssim_loss": (c_int, [P, P, c_int, c_int, c_int, c_double, P, P, P, c_size_t, P]),
+})
+
 GM_MAXL = 4
 
 

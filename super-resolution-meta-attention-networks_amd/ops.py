@@ -3398,6 +3398,49 @@ def l1_loss(a, b, rounded_once=False):
     return _L1Loss.apply(a, b, rounded_once)
 
 
+# ----------------------------------------------------------------------------- mean SSIM (csrc/ssim_loss.hip)
+SSIM_WINDOW = 11  # the Gaussian window's side: the smallest image side the loss term takes
+
+
+class _SsimMean(Function):
+    @staticmethod
+    def forward(ctx, sr, y, data_range, want_grad):
+        sr, y = sr.contiguous(), y.contiguous()
+        B, C, H, W = sr.shape
+        L = hip.lib()
+        value = torch.empty((), device=sr.device, dtype=torch.float32)
+        grad = torch.empty_like(sr) if want_grad and ctx.needs_input_grad[0] else None
+        nbytes = L.sisr_ssim_loss_workspace_bytes(B * C, H, W, int(grad is not None))
+        ws = hip.workspace(sr.device, nbytes)
+        hip.check(L.sisr_ssim_loss(hip.ptr(sr), hip.ptr(y), B * C, H, W, float(data_range), hip.ptr(value), hip.ptr(grad),
+                                   hip.ptr(ws), nbytes, hip.stream()), "sisr_ssim_loss")
+        ctx.save_for_backward(grad)
+        return value
+
+    @staticmethod
+    def backward(ctx, go):
+        (grad,) = ctx.saved_tensors
+        return grad * go, None, None, None
+
+
+def ssim_mean(sr, y, data_range=1.0):
+    """Mean SSIM over all (H - 10) x (W - 10) windows of all B * C planes of two (B, C, H, W) fp32 batches: Gaussian window
+    (11 taps, sigma 1.5), population covariance, every plane as given (no clipping, no Y conversion), float64 statistics, the
+    value rounded to fp32 once.  The gradient goes to `sr` only and is computed with the value."""
+    if sr.dim() != 4 or sr.shape != y.shape:
+        raise RuntimeError(f"ssim_mean takes two (B, C, H, W) batches of one shape; got {tuple(sr.shape)} and {tuple(y.shape)}")
+    if min(sr.shape[2:]) < SSIM_WINDOW:
+        raise ValueError(f"ssim_mean: the {SSIM_WINDOW} x {SSIM_WINDOW} window exceeds the image extent {tuple(sr.shape[2:])}; "
+                         f"both sides must be at least {SSIM_WINDOW}")
+    if sr.numel() == 0:
+        raise RuntimeError(f"ssim_mean: empty batch {tuple(sr.shape)}")
+    hip.ptr(sr), hip.ptr(y)  # raises on CPU or non-fp32 tensors: there is no CPU path
+    if y.requires_grad:
+        raise RuntimeError("ssim_mean: the target takes no gradient; detach it")
+    # needs_input_grad is set under no_grad as well (run_eval(request_loss=True)): the gradient launch and its maps are skipped there
+    return _SsimMean.apply(sr, y, data_range, torch.is_grad_enabled())
+
+
 # ----------------------------------------------------------------------------- SRCNN / VDSR pieces (csrc/basic.hip)
 # K x K convolutions (odd K <= 9, padding K // 2).  Maps between layers are channels-last with 32 or 64 channels (real channels
 # first, the rest zero); the image ends are contiguous (B, 1, H, W).  Every operator with a ReLU applies its own mask to the
