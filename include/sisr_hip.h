@@ -682,6 +682,19 @@ int sisr_vgg_prep_bwd(const float* gmap, const float* std3, float* dimg, int B, 
 int sisr_maxpool2_fwd(const float* y, float* out, int B, int H, int W, int C, void* stream);
 int sisr_maxpool2_relu_bwd(const float* y, const float* dout, float* dy, int B, int H, int W, int C, void* stream);
 
+/* ---- JPEG degradation (csrc/jpeg.hip) -----------------------------------------------------------------------------------
+ * ref: Code/data_converter.py jpeg_compress: `image.save(buf, "JPEG", subsampling=0, quality=q)` then `PIL.Image.open(buf)`.
+ * The decoded pixels of that round trip, byte for byte, without the file: libjpeg's integer arithmetic per 8 x 8 block
+ * (jccolor, jfdctint, jcdctmgr, jidctint, jdcolor; the lossless entropy coder is left out).  in: planar [C][H][W] uint8 on
+ * the device, as sisr_pil_resample writes it; out: [C][H][W] uint8 (to_float = 0) or fp32 = byte / 255 (to_float = 1, the
+ * rounding of sisr_pil_resample's to_float).  C = 3: RGB through YCbCr 4:4:4; C = 1: a grey plane on the luminance table
+ * (PIL mode L).  The image is padded to whole blocks by edge replication; nothing outside [C][H][W] is written.  The two
+ * quantisation tables (Annex K scaled by the quality as jcparam.c scales them) are built inside the call and reach the
+ * kernel by value.  One launch, no workspace, no atomics, no state: capturable, a repeat call is bit-identical.  Refused
+ * before any launch (-1): null pointers, C other than 1 or 3, H or W < 1, quality outside 1..100, to_float other than 0 or 1;
+ * more than 2^31 - 1 blocks (-4). */
+int sisr_jpeg_roundtrip(const unsigned char* in, void* out, int C, int H, int W, int quality, int to_float, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -365,7 +365,7 @@ class SuperResImages(Dataset):
             table, self.metadata_keys = read_degradation_metadata(degradation_metadata_file, names)
             self.metadata = [table[n] for n in names]
         if self.online_degradations:
-            kernel_keys = ['blur_kernel'] * self.degrader.para_in
+            kernel_keys = self.degrader.metadata_keys()  # + 'noise', 'jpeg_quality' with the jpeg stage
             if len(self.metadata_keys) == 0:
                 self.metadata_keys = kernel_keys  # ref :293-295
             else:

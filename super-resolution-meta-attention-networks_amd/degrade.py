@@ -15,6 +15,11 @@ uint8 input.  There is no CPU path: the tensors must live on a HIP device.
 
 The same resampler run the other way (`pil_bicubic_upsample`, csrc/interp.hip) is the evaluator's bicubic pre-up-sampling
 of an LR batch for the interpolated-input models (ref: Code/SISR/evaluation/standard_eval.py:146-164).
+
+JPEG compression (`jpeg_roundtrip`, csrc/jpeg.hip; ref: Code/data_converter.py jpeg_compress, `save(buf, "JPEG",
+subsampling=0, quality=q)` + `open`) is the optional last stage on the LR bytes: libjpeg's integer arithmetic per 8 x 8
+block, bit-identical to PIL's decoded image.  `jpeg_roundtrip_host` states the same arithmetic in numpy for images that
+are on the host anyway (tools/make_jpeg_set.py without a GPU) and is what the CPU tests hold against PIL.
 """
 import math
 
@@ -223,6 +228,125 @@ def pil_bicubic_upsample(lr, scale, rgb=True, ycbcr=False):
     return (out_rgb, out_ycc) if rgb and ycbcr else (out_rgb if rgb else out_ycc)
 
 
+# ----------------------------------------------------------------------------- JPEG round trip (libjpeg's integer arithmetic)
+_JPEG_LUMA = np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+                       14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+                       49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99]).reshape(8, 8)
+_JPEG_CHROMA = np.full((8, 8), 99)
+_JPEG_CHROMA[:4, :4] = [[17, 18, 24, 47], [18, 21, 26, 66], [24, 26, 56, 99], [47, 66, 99, 99]]
+
+
+def _check_quality(quality):
+    if isinstance(quality, bool) or int(quality) != quality or not 1 <= quality <= 100:
+        raise ValueError(f"JPEG quality must be an integer in 1..100; got {quality!r}")
+    return int(quality)
+
+
+def jpeg_tables(quality):
+    """jcparam.c jpeg_set_quality: the Annex-K luminance and chrominance tables scaled for `quality` (1..100), each an
+    (8, 8) int array in natural (row-major) order."""
+    q = _check_quality(quality)
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    return tuple(np.clip((base * s + 50) // 100, 1, 255) for base in (_JPEG_LUMA, _JPEG_CHROMA))
+
+
+def _descale(x, n):
+    return (x + (1 << (n - 1))) >> n
+
+
+def _jpeg_odd_part(t4, t5, t6, t7):
+    """The odd half shared by jfdctint.c and jidctint.c: -> (from t4, from t5, from t6, from t7) before the descale."""
+    z1, z2, z3, z4 = t4 + t7, t5 + t6, t4 + t6, t5 + t7
+    z5 = (z3 + z4) * 9633
+    t4, t5, t6, t7 = t4 * 2446, t5 * 16819, t6 * 25172, t7 * 12299
+    z1, z2, z3, z4 = z1 * -7373, z2 * -20995, -z3 * 16069 + z5, -z4 * 3196 + z5
+    return t4 + z1 + z3, t5 + z2 + z4, t6 + z2 + z3, t7 + z1 + z4
+
+
+def _jpeg_fdct_pass(d, second):
+    """One pass of jfdctint.c over the LAST axis (length 8) of an integer array."""
+    d = [d[..., i] for i in range(8)]
+    t0, t7, t1, t6 = d[0] + d[7], d[0] - d[7], d[1] + d[6], d[1] - d[6]
+    t2, t5, t3, t4 = d[2] + d[5], d[2] - d[5], d[3] + d[4], d[3] - d[4]
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    n = 15 if second else 11
+    o = [None] * 8
+    o[0] = _descale(t10 + t11, 2) if second else (t10 + t11) << 2
+    o[4] = _descale(t10 - t11, 2) if second else (t10 - t11) << 2
+    z1 = (t12 + t13) * 4433
+    o[2] = _descale(z1 + t13 * 6270, n)
+    o[6] = _descale(z1 - t12 * 15137, n)
+    o[7], o[5], o[3], o[1] = (_descale(v, n) for v in _jpeg_odd_part(t4, t5, t6, t7))
+    return np.stack(o, axis=-1)
+
+
+def _jpeg_idct_pass(c, second):
+    """One pass of jidctint.c over the LAST axis (length 8) of an integer array."""
+    c = [c[..., i] for i in range(8)]
+    z1 = (c[2] + c[6]) * 4433
+    t2, t3 = z1 - c[6] * 15137, z1 + c[2] * 6270
+    t0, t1 = (c[0] + c[4]) << 13, (c[0] - c[4]) << 13
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    t0, t1, t2, t3 = _jpeg_odd_part(c[7], c[5], c[3], c[1])
+    n = 18 if second else 11
+    return np.stack([_descale(v, n) for v in (t10 + t3, t11 + t2, t12 + t1, t13 + t0, t13 - t0, t12 - t1, t11 - t2, t10 - t3)],
+                    axis=-1)
+
+
+def _jpeg_plane(plane, table):
+    """One component (H, W), samples 0..255 in an integer dtype -> the decoded component, same shape and dtype."""
+    H, W = plane.shape
+    x = np.pad(plane, ((0, -H % 8), (0, -W % 8)), mode="edge") - 128
+    x = x.reshape(x.shape[0] // 8, 8, x.shape[1] // 8, 8).transpose(0, 2, 1, 3)  # (by, bx, row, column)
+    x = _jpeg_fdct_pass(x, False)                                           # along the rows
+    x = _jpeg_fdct_pass(x.swapaxes(-1, -2), True).swapaxes(-1, -2)          # along the columns
+    d = table.astype(x.dtype) * 8
+    x = np.sign(x) * ((np.abs(x) + d // 2) // d) * table.astype(x.dtype)    # jcdctmgr quantise, jdcoefct dequantise
+    x = _jpeg_idct_pass(x.swapaxes(-1, -2), False).swapaxes(-1, -2)         # along the columns
+    x = _jpeg_idct_pass(x, True)                                            # along the rows
+    x = np.clip(x + 128, 0, 255)
+    return x.transpose(0, 2, 1, 3).reshape(H + -H % 8, W + -W % 8)[:H, :W]
+
+
+def jpeg_roundtrip_host(u8, quality, acc=np.int64):
+    """The image `PIL.Image.open` returns after `save(buf, "JPEG", subsampling=0, quality=quality)`, from libjpeg's
+    arithmetic in numpy: (C, H, W) uint8 array, C = 3 (RGB) or 1 (PIL mode L) -> (C, H, W) uint8.  `acc`: the integer type
+    everything is computed in (the device kernel uses 32 bits; np.int32 here shows that they suffice)."""
+    u8 = np.asarray(u8)
+    if u8.dtype != np.uint8 or u8.ndim != 3 or u8.shape[0] not in (1, 3) or u8.shape[1] < 1 or u8.shape[2] < 1:
+        raise ValueError(f"jpeg_roundtrip_host takes a (1 or 3, H, W) uint8 image; got {u8.dtype} {u8.shape}")
+    luma, chroma = jpeg_tables(quality)
+    x = u8.astype(acc)
+    if x.shape[0] == 1:
+        return _jpeg_plane(x[0], luma)[None].astype(np.uint8)
+    r, g, b = x
+    y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16                                   # jccolor.c
+    cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16
+    cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16
+    y, cb, cr = _jpeg_plane(y, luma), _jpeg_plane(cb, chroma) - 128, _jpeg_plane(cr, chroma) - 128
+    out = (y + ((91881 * cr + 32768) >> 16), y + ((-22554 * cb + 32768 - 46802 * cr) >> 16),  # jdcolor.c
+           y + ((116130 * cb + 32768) >> 16))
+    return np.clip(np.stack(out), 0, 255).astype(np.uint8)
+
+
+def jpeg_roundtrip(u8, quality, to_float=True):
+    """The same round trip on the device, one launch: planar uint8 (C, H, W), C = 3 or 1, as
+    `pil_bicubic_downsample(..., to_float=False)` returns it -> (C, H, W) fp32 / 255 (ToTensor) or uint8."""
+    if not u8.is_cuda:
+        raise RuntimeError("degrade.jpeg_roundtrip: the image must be on a HIP device (no CPU path; jpeg_roundtrip_host is "
+                           "the numpy form)")
+    if u8.dtype != torch.uint8 or u8.dim() != 3:
+        raise ValueError(f"jpeg_roundtrip takes a (C, H, W) uint8 image; got {u8.dtype} {tuple(u8.shape)}")
+    quality = _check_quality(quality)
+    C, H, W = u8.shape
+    u8 = u8.contiguous()
+    with torch.cuda.device(u8.device):
+        out = torch.empty((C, H, W), device=u8.device, dtype=torch.float32 if to_float else torch.uint8)
+        hip.check(hip.lib().sisr_jpeg_roundtrip(u8.data_ptr(), out.data_ptr(), C, H, W, quality, int(bool(to_float)),
+                                                hip.stream()), "sisr_jpeg_roundtrip")
+    return out
+
+
 def center_crop_box(height, width, scale):
     """image_manipulation.downsample's crop: (top, left, r_height, r_width), rounding as center_crop does."""
     rh, rw = (height // scale) * scale, (width // scale) * scale
@@ -234,15 +358,39 @@ class OnlineDegrader:
     SuperResImages.__getitem__ applies it (data_handler.py:446-456); returns device tensors.  With `noise` (ref
     gaussian_utils.py:371-424; the reference's own default for SRMDPreprocessing, off in the dataset's default set-up):
     a noise level per image (random_batch_noise: uniform * noise_high, zero with probability rate_cln), Gaussian noise of
-    that level on the BLURRED full-size image, clamped to [0, 1], and 10 * level appended to the kernel code."""
+    that level on the BLURRED full-size image, clamped to [0, 1], and 10 * level appended to the kernel code.
+    With `jpeg` (not a reference option; its offline counterpart is data_converter.py's jpeg_compress): the LR bytes go
+    through a JPEG round trip at a quality drawn per image from `jpeg_quality` = q or [lo, hi] (inclusive) -- the last draw
+    of the call, one np.random.randint -- and (q - a) / (b - a) is appended to the code, [a, b] = `jpeg_norm` (default: the
+    quality range; [0, 100] for a single quality): the min-max normalisation the reference applies to an integer CSV column."""
 
     def __init__(self, scale=4, pca=None, kernel=21, sig_min=0.2, sig_max=4.0, rate_iso=1.0, scaling=3, noise=False,
-                 random=True, sig=2.6, para_input=10, rate_cln=0.2, noise_high=0.08, **unused):
+                 random=True, sig=2.6, para_input=10, rate_cln=0.2, noise_high=0.08, jpeg=False, jpeg_quality=(30, 95),
+                 jpeg_norm=None, **unused):
+        self.jpeg = bool(jpeg)
+        if self.jpeg:
+            lo, hi = (jpeg_quality, jpeg_quality) if np.isscalar(jpeg_quality) else jpeg_quality
+            self.jpeg_lo, self.jpeg_hi = _check_quality(lo), _check_quality(hi)
+            if self.jpeg_lo > self.jpeg_hi:
+                raise ValueError(f"jpeg_quality = [lo, hi] needs lo <= hi; got {jpeg_quality!r}")
+            if jpeg_norm is None:
+                jpeg_norm = (self.jpeg_lo, self.jpeg_hi) if self.jpeg_lo < self.jpeg_hi else (0, 100)
+            self.jpeg_norm = (float(jpeg_norm[0]), float(jpeg_norm[1]))
+            if not self.jpeg_norm[0] < self.jpeg_norm[1]:
+                raise ValueError(f"jpeg_norm = [a, b] needs a < b; got {jpeg_norm!r}")
         self.noise, self.rate_cln, self.noise_high = bool(noise), rate_cln, noise_high
         self.scale, self.l, self.random, self.sig = int(scale), int(kernel), bool(random), 2.6 if sig is None else sig
         self.sig_min, self.sig_max, self.rate_iso, self.scaling = sig_min, sig_max, rate_iso, scaling
         self.pca = pca if pca is not None else pca_matrix()
         self.para_in = para_input
+
+    def metadata_keys(self):
+        """The keys of the code's entries.  Without `jpeg`: the reference's list, 'blur_kernel' per kernel-code entry (the
+        noise level, when on, has none: data_handler.py:293-297).  With it every value has a key."""
+        keys = ['blur_kernel'] * self.para_in
+        if self.jpeg:
+            keys += (['noise'] if self.noise else []) + ['jpeg_quality']
+        return keys
 
     def draw_kernel(self):
         if self.random:
@@ -267,4 +415,10 @@ class OnlineDegrader:
         top, left, rh, rw = center_crop_box(hr.shape[1], hr.shape[2], self.scale)
         if (rh, rw) != (hr.shape[1], hr.shape[2]):
             u8 = u8[:, top:top + rh, left:left + rw].contiguous()
-        return pil_bicubic_downsample(u8, self.scale), code, kernel, (top, left, rh, rw)
+        if not self.jpeg:
+            return pil_bicubic_downsample(u8, self.scale), code, kernel, (top, left, rh, rw)
+        q = int(np.random.randint(self.jpeg_lo, self.jpeg_hi + 1))
+        a, b = self.jpeg_norm
+        code = torch.cat([code, torch.tensor([(q - a) / (b - a)], dtype=torch.float32)])
+        lr = jpeg_roundtrip(pil_bicubic_downsample(u8, self.scale, to_float=False), q)
+        return lr, code, kernel, (top, left, rh, rw)

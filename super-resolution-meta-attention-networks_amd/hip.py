@@ -220,6 +220,10 @@ _SIGS.update({  # structural (SSIM) loss: mean SSIM and its gradient, float64 wi
     "sisr_ssim_loss": (c_int, [P, P, c_int, c_int, c_int, c_double, P, P, P, c_size_t, P]),
 })
 
+_SIGS.update({  # JPEG degradation: encode -> decode of a planar uint8 image as libjpeg computes it (csrc/jpeg.hip)
+    "sisr_jpeg_roundtrip": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
+})
+
 GM_MAXL = 4
 
 
