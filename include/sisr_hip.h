@@ -343,6 +343,36 @@ int sisr_l1_loss_mean(const float* a, const float* b, long n, float* loss, float
 int sisr_adam_flat(float* p, const float* g, float* m, float* v, long n, float beta2, float one_minus_beta1,
                    float one_minus_beta2, float eps, float step_size, float bc2_sqrt, float grad_scale, void* stream);
 
+/* ---- the step's optional parts: gradient-norm clipping, decoupled weight decay, weight EMA (csrc/update.hip) ----
+ * Global L2 norm of the gradient over several flat fp32 ranges, two stages, no atomics.  Every product g * g (exact in
+ * double) and every sum is in double.  sisr_sumsq_partial cuts a range of n floats over sisr_sumsq_workspace_bytes(n) / 8
+ * workgroups (at most 1024; a grid-stride loop above 1 048 576 floats) and writes that many double partial sums at `part`;
+ * the caller places the partials of its ranges one behind the other.  g must be 16-byte aligned (the body loads float4, a
+ * tail of n % 4 floats one by one), part 8-byte aligned.  sisr_clip_coef is one workgroup: it adds the nparts partials in
+ * a fixed order and writes  *norm64 = sqrt(sum),  *norm32 = (float)*norm64,
+ * *coef = (float)min(1, max_norm / (*norm64 + 1e-6))  -- torch.nn.utils.clip_grad_norm_(error_if_nonfinite=False): the
+ * coefficient is computed in double and rounded once; a NaN norm gives a NaN coefficient.  The cut of a range and the order
+ * of every sum depend on the range lengths alone: two calls on the same data give the same bits.  One launch per range
+ * plus one, no host synchronisation.  A null pointer, n <= 0, nparts <= 0 or max_norm not > 0: SISR_ERR_ARG. */
+size_t sisr_sumsq_workspace_bytes(long n);
+int sisr_sumsq_partial(const float* g, long n, double* part, void* stream);
+int sisr_clip_coef(const double* part, long nparts, double max_norm, double* norm64, float* norm32, float* coef,
+                   void* stream);
+
+/* sisr_adam_flat with three additions, in this order per element (no fused multiply-adds):
+ *   gg = g * grad_scale, and if grad_scale_dev != NULL  gg = gg * *grad_scale_dev  (a device word the kernel reads, e.g.
+ *        sisr_clip_coef's coefficient; the stored gradient is not modified);
+ *   p = p * decay_factor  (decoupled / AdamW weight decay: the host passes 1 - lr * weight_decay, computed in double);
+ *   exp_avg, exp_avg_sq and p as sisr_adam_flat updates them, on gg;
+ *   if ema != NULL  ema = ema + (p_new - ema) * one_minus_decay  (a fifth array laid out like the others).
+ * With grad_scale_dev == NULL, decay_factor == 1 and ema == NULL the results are bitwise sisr_adam_flat's.  Alignment
+ * and refusals as there (ema 16-byte aligned, grad_scale_dev 4-byte aligned).
+ * sisr_ema_flat performs the ema line alone over a range (parameters the step skips); p is only read. */
+int sisr_update_flat(float* p, const float* g, float* m, float* v, float* ema, long n, float beta2, float one_minus_beta1,
+                     float one_minus_beta2, float eps, float step_size, float bc2_sqrt, float grad_scale,
+                     const float* grad_scale_dev, float decay_factor, float one_minus_decay, void* stream);
+int sisr_ema_flat(const float* p, float* ema, long n, float one_minus_decay, void* stream);
+
 /* ---- progress words for hipGraph replays (data-parallel reducer; ref: SISR/models/__init__.py:344-347 DataParallel) ----
  * sisr_host_flags_alloc: n zeroed 32-bit words of pinned, host-coherent, device-visible memory (nullptr on failure; the
  * one allocation the library makes on the caller's behalf, returned to sisr_host_flags_free).  sisr_signal_host enqueues

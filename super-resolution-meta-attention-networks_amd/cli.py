@@ -104,6 +104,15 @@ class TrainingHandler:
         return losses
 
     def eval(self, epoch_idx):
+        """validation on the averaged weights when the model keeps an average (ema_decay): the best epoch is then chosen on
+        what 'network_ema' of its checkpoint holds"""
+        handler = self.model.model
+        if getattr(handler, 'has_ema', None) is not None and handler.has_ema():
+            with handler.averaged_weights():
+                return self._eval(epoch_idx)
+        return self._eval(epoch_idx)
+
+    def _eval(self, epoch_idx):
         losses = defaultdict(list)
         wanted = list(dict.fromkeys(self.metrics or ()))  # columns follow the order the metrics are listed in
         for batch in self.val_data:
@@ -235,7 +244,9 @@ def eval_sisr(config=None, **kw):
     (on the device when the models run there), or read from `lr_dir_interp`.  `lr_baseline = true` adds 'LR' rows: the
     up-sampled image itself against the HR image (the reference always writes them).  `self_ensemble = true` evaluates
     every model with the geometric self-ensemble (run_eval(self_ensemble=True), the papers' "+" rows): its rows and its image
-    folder carry the name '<experiment>+'; the LR rows are unaffected."""
+    folder carry the name '<experiment>+'; the LR rows are unaffected.  `use_ema = true` loads every listed model from the
+    averaged weights of its checkpoint ('network_ema', stored by a run with ema_decay; a checkpoint without them is an
+    error): its rows and image folder carry '<experiment>@ema' (before the '+', if both are set)."""
     import pandas as pd
     cfg = dict(_load_toml(config)) if config is not None else {}
     cfg.update({k: v for k, v in kw.items() if v is not None})
@@ -243,7 +254,8 @@ def eval_sisr(config=None, **kw):
     os.makedirs(out_dir, exist_ok=True)
     scale = cfg.get('scale', 4)
     models = [ModelInterface(cfg['model_loc'], name, gpu='single' if cfg.get('gpu') else 'off',
-                             sp_gpu=cfg.get('sp_gpu', 0), mode='eval', load_epoch=ep if ep in ('best', 'last') else int(ep))
+                             sp_gpu=cfg.get('sp_gpu', 0), mode='eval', load_epoch=ep if ep in ('best', 'last') else int(ep),
+                             ema=bool(cfg.get('use_ema')))
               for name, ep in cfg['model_and_epoch']]
     for m in models:
         # A network fed the up-sampled image maps it to one of the same size whatever `scale` it was configured with (it
@@ -264,7 +276,8 @@ def eval_sisr(config=None, **kw):
     timing = cfg.get('time_models', True)
     baseline = bool(cfg.get('lr_baseline'))
     plus = {'self_ensemble': True} if cfg.get('self_ensemble') else {}
-    label = (lambda m: m.experiment + '+') if plus else (lambda m: m.experiment)
+    suffix = ('@ema' if cfg.get('use_ema') else '') + ('+' if plus else '')
+    label = lambda m: m.experiment + suffix  # noqa: E731
     y_models = [m for m in models if 'rgb' not in m.configuration['colorspace']]
     need_interp = baseline or bool(y_models) or any(m.configuration['input'] != 'unmodified' for m in models)
     need_ycbcr = baseline or bool(y_models)

@@ -8,9 +8,10 @@ Mirrors (names, arguments, return values, error behaviour):
   QRCAN/QEDSR/QHAN handlers   ref: Code/SISR/models/attention_manipulators/handlers.py:7-76,156-171
 so TrainingHandler / EvalHub style callers (train_batch, net_run_and_process, save, ...) work unchanged
 and checkpoints ({'network','optimizer','model_name','model_epoch'[,'scheduler_G']}) interchange with the
-reference.  The only intentional difference: gpu='multi' means one process per GPU + RCCL gradient
+reference; a handler that keeps an average of the weights (ema_decay) adds 'network_ema'.  The only intentional difference: gpu='multi' means one process per GPU + RCCL gradient
 all-reduce (parallel.py) instead of single-process nn.DataParallel (ref :344-347).
 """
+import contextlib
 import glob
 import math
 import os
@@ -69,18 +70,83 @@ class BaseModel(nn.Module):
         self.ssim_data_range = kwargs.get('ssim_data_range', 1.0)
         if self.ssim_loss is not None and not self.ssim_loss >= 0:
             raise ValueError("ssim_loss: the weight of the structural term must be >= 0; got %r" % (self.ssim_loss,))
+        # the optional parts of the update step, all carried out by optim.FlatAdam in its one pass over the arenas (no
+        # counterpart in the reference; model parameters, so a config's internal_params can hold them):
+        #   weight_decay  decoupled (AdamW) weight decay;   ema_decay  an exponential moving average of the weights,
+        #   validated on / saved as 'network_ema';   fused_clip  grad_clip on the device instead of clip_grad_norm_
+        self.weight_decay = kwargs.get('weight_decay')
+        self.ema_decay = kwargs.get('ema_decay')
+        self.fused_clip = bool(kwargs.get('fused_clip'))
+        self._averaged = False  # inside averaged_weights()
+        if self.weight_decay is not None and not (self.weight_decay >= 0 and math.isfinite(self.weight_decay)):
+            raise ValueError("weight_decay must be a finite number >= 0; got %r" % (self.weight_decay,))
+        if self.ema_decay is not None and not 0 <= self.ema_decay < 1:
+            raise ValueError("ema_decay must be in [0, 1); got %r" % (self.ema_decay,))
+        if self.fused_clip and self.grad_clip is None:
+            raise ValueError("fused_clip=True moves gradient clipping into the optimiser's pass, but no grad_clip is in effect")
 
     # -- optimiser / scheduler (ref :292-335)
     def define_optimizer(self, lr=1e-4, optimizer_params=None):
         params = [p for p in self.net.parameters() if p.requires_grad]
         betas = (optimizer_params['beta_1'], optimizer_params['beta_2']) if optimizer_params is not None else (0.9, 0.999)
+        options = {}
+        if self.weight_decay:
+            options['weight_decay'] = self.weight_decay
+        if self.ema_decay is not None:
+            options['ema_decay'] = self.ema_decay
+        if self.fused_clip:
+            options['max_norm'] = self.grad_clip
         if params and all(p.is_cuda for p in params) and os.environ.get("SISR_FLAT_ADAM", "1") != "0":
             from .optim import FlatAdam  # one-launch Adam over a flat arena, torch.optim.Adam's schema (optim.py)
             # the meta-attention layers a network runs as ONE launch deliver their gradients at the very end of backward
             # (architectures.meta_gates); layers applied block by block (QSPARNet, the metadata-mixing styles) do not
-            self.optimizer = FlatAdam(params, lr=lr, betas=betas, late=A.late_parameters(self.net))
+            self.optimizer = FlatAdam(params, lr=lr, betas=betas, late=A.late_parameters(self.net), **options)
+        elif options:
+            why = ("SISR_FLAT_ADAM=0 selects torch.optim.Adam" if params and all(p.is_cuda for p in params)
+                   else "the parameters are not on a HIP device")
+            asked = ' / '.join('fused_clip' if k == 'max_norm' else k for k in options)
+            raise RuntimeError("%s: %s is carried out by optim.FlatAdam's pass over its arenas, and this handler's optimiser is "
+                               "not one (%s)" % (type(self).__name__, asked, why))
         else:  # CPU handlers exist for construction / checkpoint plumbing only and are never stepped
             self.optimizer = optim.Adam(params, lr=lr, betas=betas)
+
+    def has_ema(self):
+        return getattr(self.optimizer, 'flat_e', None) is not None
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Inside the block the network holds the averaged weights (validation, export); on exit the trained ones are back,
+        bit for bit.  The CONTENTS of the parameter and average arenas are exchanged, not the pointers, so captured graphs,
+        ops.GRAD_SINK and every view stay valid.  Not nestable."""
+        if not self.has_ema():
+            raise RuntimeError("%s keeps no average of the weights (ema_decay is not set)" % type(self).__name__)
+        if self._averaged:
+            raise RuntimeError("averaged_weights() is already active: it cannot be nested")
+        opt = self.optimizer
+
+        def exchange():
+            with torch.no_grad():
+                keep = opt.flat_p.clone()
+                opt.flat_p.copy_(opt.flat_e)
+                opt.flat_e.copy_(keep)
+            ops.invalidate_packs()
+        self._averaged = True
+        exchange()
+        try:
+            yield self
+        finally:
+            exchange()
+            self._averaged = False
+
+    def _averaged_state_dict(self):
+        """net.state_dict() with every trained parameter replaced by its average (buffers and frozen parameters as they are)"""
+        sd = self.net.state_dict()
+        names = {id(p): k for k, p in self.net.named_parameters()}
+        ema = self.optimizer.ema_state()
+        out = OrderedDict(sd)
+        for k, p in enumerate(self.optimizer.param_groups[0]['params']):
+            out[names[id(p)]] = ema[k]
+        return out
 
     def define_scheduler(self, scheduler, scheduler_params):
         if scheduler == 'cosine_annealing_warm_restarts':
@@ -166,7 +232,11 @@ class BaseModel(nn.Module):
 
     # -- checkpoints (ref :349-464)
     def save_model(self, model_save_name, model_idx, extract_state_only=False):
+        if self._averaged:
+            raise RuntimeError("save_model inside averaged_weights(): the network holds the averaged weights")
         self.state['network'] = self.net.state_dict()
+        if self.has_ema():  # the averaged network, loadable as it is (load_model(ema=True)); absent without an average
+            self.state['network_ema'] = OrderedDict((k, v.detach().clone()) for k, v in self._averaged_state_dict().items())
         self.state['optimizer'] = self.optimizer.state_dict()
         self.state['model_name'] = self.model_name
         self.state['model_epoch'] = self.curr_epoch
@@ -188,7 +258,9 @@ class BaseModel(nn.Module):
                 out[k] = v
         return out
 
-    def load_model(self, model_save_name, model_idx, legacy=False, load_override=None, preloaded_state=None):
+    def load_model(self, model_save_name, model_idx, legacy=False, load_override=None, preloaded_state=None, ema=False):
+        """ema: load the checkpoint's averaged weights ('network_ema') as the network.  In training mode a handler that keeps
+        an average restores it from the checkpoint, or starts it from the loaded weights if the checkpoint has none."""
         loc = self.device if self.device == torch.device('cpu') else "cuda:%d" % self.device
         folder = self.model_save_dir if load_override is None else load_override
         load_file = os.path.join(folder, "{}_{}".format(model_save_name, str(model_idx)))
@@ -197,10 +269,19 @@ class BaseModel(nn.Module):
             state = torch.load(f=load_file, map_location=loc, weights_only=True)
         else:
             state = preloaded_state
-        net_state = self.legacy_switch(state['network']) if legacy else state['network']
+        if ema and 'network_ema' not in state:
+            raise RuntimeError("%s holds no averaged weights ('network_ema'): it was saved by a run without ema_decay"
+                               % load_file)
+        net_state = state['network_ema'] if ema else state['network']
+        net_state = self.legacy_switch(net_state) if legacy else net_state
         self.net.load_state_dict(state_dict=net_state)
         if not self.eval_mode:
-            self.optimizer.load_state_dict(state['optimizer'])
+            self.optimizer.load_state_dict(state['optimizer'])  # (restarts the average from the loaded weights)
+            if self.has_ema() and 'network_ema' in state:
+                avg = self.legacy_switch(state['network_ema']) if legacy else state['network_ema']
+                names = {id(p): k for k, p in self.net.named_parameters()}
+                self.optimizer.load_ema({k: avg[names[id(p)]]
+                                         for k, p in enumerate(self.optimizer.param_groups[0]['params'])})
             if self.learning_rate_scheduler is not None:
                 self.learning_rate_scheduler.load_state_dict(state['scheduler_G'])
         self.set_epoch(state['model_epoch'])
@@ -322,7 +403,7 @@ class BaseModel(nn.Module):
                 red.hooks_enabled = True
         if red is not None:
             red.reduce(prescaled=True)
-        if self.grad_clip is not None:
+        if self.grad_clip is not None and not self.fused_clip:  # fused: the optimiser's own pass clips (max_norm)
             nn.utils.clip_grad_norm_(self.net.parameters(), self.grad_clip)
         self.optimizer.step()
         if self.learning_rate_scheduler is not None:
@@ -344,7 +425,7 @@ class BaseModel(nn.Module):
     def _finish_update(self):
         if self.reducer is not None:
             self.reducer.reduce(prescaled=True)
-        if self.grad_clip is not None:
+        if self.grad_clip is not None and not self.fused_clip:  # fused: the optimiser's own pass clips (max_norm)
             nn.utils.clip_grad_norm_(self.net.parameters(), self.grad_clip)
         self.optimizer.step()
         if self.learning_rate_scheduler is not None:
@@ -601,10 +682,11 @@ class ModelInterface:
     """ref: Code/SISR/models/__init__.py:33-254"""
 
     def __init__(self, model_loc, experiment, gpu='off', sp_gpu=0, mode='eval', new_params=None, load_epoch=None,
-                 scale=None, save_subdir=None, new_branch=False):
+                 scale=None, save_subdir=None, new_branch=False, ema=False):
         """Same contract as the reference's constructor: experiment folder layout (<model_loc>/<experiment>/{result_outputs,
         saved_models}[/<save_subdir>]), parameters from `new_params` (new model) or the folder's config.toml (load_epoch given,
-        a number or 'best' / 'last'), the same refusals with the same messages."""
+        a number or 'best' / 'last'), the same refusals with the same messages.  ema: load the checkpoint's averaged weights
+        (a run with ema_decay stores them) as the network."""
         self.experiment, self.mode = experiment, mode
         resuming = load_epoch is not None
         self._lay_out(model_loc, experiment, save_subdir, create=mode == 'train')
@@ -623,7 +705,8 @@ class ModelInterface:
         self.model_epoch = self._epoch_number(load_epoch) if resuming else 0
         if resuming:
             self.model.load_model(model_save_name='train_model', model_idx=self.model_epoch, legacy=self.model.legacy_load,
-                                  load_override=os.path.dirname(self.saved_models) if new_branch else None)
+                                  load_override=os.path.dirname(self.saved_models) if new_branch else None,
+                                  **({'ema': True} if ema else {}))
         else:
             self.model.pre_training_model_load()
         self.full_name = '%s_%d' % (experiment, self.model_epoch)

@@ -224,6 +224,15 @@ _SIGS.update({  # JPEG degradation: encode -> decode of a planar uint8 image as 
     "sisr_jpeg_roundtrip": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
 })
 
+_SIGS.update({  # the optimiser step's optional parts: gradient norm / clip coefficient, AdamW decay, weight EMA (csrc/update.hip)
+    "sisr_sumsq_workspace_bytes": (c_size_t, [c_long]),
+    "sisr_sumsq_partial": (c_int, [P, c_long, P, P]),
+    "sisr_clip_coef": (c_int, [P, c_long, c_double, P, P, P, P]),
+    "sisr_update_flat": (c_int, [P, P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_float, c_float, c_float, P,
+                                 c_float, c_float, P]),
+    "sisr_ema_flat": (c_int, [P, P, c_long, c_float, P]),
+})
+
 GM_MAXL = 4
 
 
