@@ -643,6 +643,27 @@ size_t sisr_ssim_loss_workspace_bytes(int planes, int h, int w, int want_grad);
 int sisr_ssim_loss(const float* sr, const float* y, int planes, int h, int w, double data_range, float* value,
                    float* grad /* nullable */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- frequency-domain (FFT L1) training loss (csrc/freq_loss.hip) ------------------------------------------------------
+ * The mean absolute real and imaginary part of the orthonormal 2-D DFT of sr - y over the half spectrum, and its gradient
+ * with respect to sr (no counterpart in the reference; the loss base + beta * value of frequency.FrequencyMechanism).
+ * sr, y: `planes` contiguous fp32 planes [planes][h][w]; wh = w / 2 + 1; F = rfft2(sr - y, norm = 'ortho') per plane;
+ * value = (sum |Re F| + sum |Im F|) / (2 planes h wh): one float on the device, float64 sums of per-workgroup partials in
+ * a fixed order, rounded to fp32 once.  grad (optional): [planes][h][w] fp32, d value / d sr with sign(0) = 0; y takes none.
+ * The transform runs as matrix products on the fp32 MFMA against four tables that the caller keeps per (h, w):
+ *   sisr_freq_loss_tables writes Ch, Sh ([h][h]) and Cw, Sw ([wh][w]) in that order, sisr_freq_loss_table_bytes(h, w)
+ *   bytes in all: C[k][j] = cos(2 pi r / N), S[k][j] = sin(2 pi r / N), r = k j mod N, evaluated in float64 and rounded
+ *   once; exactly 0 / +-1 at quarter turns, which makes the imaginary parts at the self-conjugate bins exact zeros.
+ * Three launches, five with grad; no atomics: a repeat call is bit-identical.  No allocation and no host synchronisation:
+ * capturable.  workspace: the partials, two fp32 [planes][h][wh] maps and, with grad, one sign byte per bin.
+ * Refused before any launch: null sr / y / tables / value / workspace, planes < 1, h or w outside [2, 4096],
+ * workspace_bytes < sisr_freq_loss_workspace_bytes(planes, h, w, grad != NULL) (-1; the size queries return 0 for such
+ * extents); a workspace that is not 16-byte aligned or a float pointer that is not 4-byte aligned (-2); planes > 65535 (-4). */
+size_t sisr_freq_loss_table_bytes(int h, int w);
+int sisr_freq_loss_tables(int h, int w, float* tables, void* stream);
+size_t sisr_freq_loss_workspace_bytes(int planes, int h, int w, int want_grad);
+int sisr_freq_loss(const float* sr, const float* y, int planes, int h, int w, const float* tables, float* value,
+                   float* grad /* nullable */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- SRCNN / VDSR building blocks (csrc/basic.hip) ------------------------------------------------------------------
  * ref: SISR/models/basic/architectures.py (SRCNN, VDSR: K x K convs, padding K/2), basic/handlers.py (nn.MSELoss).
  * K odd, 1..9.  Maps between layers: channels-last, cp = 32 or 64 channels (real channels first, the rest zero); the image

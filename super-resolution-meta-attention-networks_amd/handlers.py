@@ -70,6 +70,12 @@ class BaseModel(nn.Module):
         self.ssim_data_range = kwargs.get('ssim_data_range', 1.0)
         if self.ssim_loss is not None and not self.ssim_loss >= 0:
             raise ValueError("ssim_loss: the weight of the structural term must be >= 0; got %r" % (self.ssim_loss,))
+        # weight of the frequency-domain term beta * mean |rfft2(sr - y, norm='ortho')| added after the structural one (None / 0: no
+        # such term); a model parameter as well (no counterpart in the reference)
+        self.freq_loss = kwargs.get('freq_loss')
+        if self.freq_loss is not None and not (self.freq_loss >= 0 and math.isfinite(self.freq_loss)):
+            raise ValueError("freq_loss: the weight of the frequency-domain term must be a finite number >= 0; got %r"
+                             % (self.freq_loss,))
         # the optional parts of the update step, all carried out by optim.FlatAdam in its one pass over the arenas (no
         # counterpart in the reference; model parameters, so a config's internal_params can hold them):
         #   weight_decay  decoupled (AdamW) weight decay;   ema_decay  an exponential moving average of the weights,
@@ -184,6 +190,10 @@ class BaseModel(nn.Module):
             # every handler sets its criterion before it calls training_setup: whichever it is becomes the pixel term
             from . import structural
             self.criterion = structural.StructuralMechanism(self.criterion, self.ssim_loss, self.ssim_data_range)
+        if self.freq_loss is not None and self.freq_loss != 0 and self.eval_mode is False:
+            # outermost: pixel or perceptual base -> StructuralMechanism -> FrequencyMechanism
+            from . import frequency
+            self.criterion = frequency.FrequencyMechanism(self.criterion, self.freq_loss)
 
     def _perceptual_criterion(self, lambda_per):
         """ref: models/__init__.py:341-342 PerceptualMechanism(lambda_per=perceptual, device=device), with the extractor's weights

@@ -233,6 +233,13 @@ _SIGS.update({  # the optimiser step's optional parts: gradient norm / clip coef
     "sisr_ema_flat": (c_int, [P, P, c_long, c_float, P]),
 })
 
+_SIGS.update({  # frequency-domain (FFT L1) loss: DFT tables, value and gradient on the fp32 MFMA (csrc/freq_loss.hip)
+    "sisr_freq_loss_table_bytes": (c_size_t, [c_int, c_int]),
+    "sisr_freq_loss_tables": (c_int, [c_int, c_int, P, P]),
+    "sisr_freq_loss_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "sisr_freq_loss": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
+})
+
 GM_MAXL = 4
 
 

@@ -26,6 +26,7 @@ Operators
   frozen_features / FrozenChain    the perceptual loss's VGG19 feature extractor: frozen, once-packed convs, max-pools,
                  input-gradient-only backward (ref: feature_extractors/VGGNets.py:118-131, sr_tools/loss_functions.py:6-22)
 """
+import collections
 import os
 
 import torch
@@ -3439,6 +3440,83 @@ def ssim_mean(sr, y, data_range=1.0):
         raise RuntimeError("ssim_mean: the target takes no gradient; detach it")
     # needs_input_grad is set under no_grad as well (run_eval(request_loss=True)): the gradient launch and its maps are skipped there
     return _SsimMean.apply(sr, y, data_range, torch.is_grad_enabled())
+
+
+# ----------------------------------------------------------------------------- spectral L1 (csrc/freq_loss.hip)
+SPECTRAL_MIN_SIDE, SPECTRAL_MAX_SIDE = 2, 4096
+SPECTRAL_TABLE_SLOTS = 8  # (H, W) pairs kept per device: training uses one, validation images vary in size
+_spectral_tables = {}     # device index -> OrderedDict((H, W) -> the four DFT tables in one fp32 tensor), least recent first
+_spectral_held = {}       # device index -> {(H, W): tables a captured graph reads}: never evicted
+
+
+def spectral_tables(device, H, W):
+    """Ch, Sh (H x H), Cw, Sw ((W // 2 + 1) x W) of sisr_freq_loss, in that order in one flat fp32 tensor on `device`; built by
+    the table kernel on a miss and kept in a per-device LRU cache (tables that a captured graph reads are kept for good).  A miss needs an allocation, so it cannot happen while the
+    stream is capturing: run the operator once eagerly at that shape first (handlers._graphed_step's warm-up pass does)."""
+    cache = _spectral_tables.setdefault(device.index, collections.OrderedDict())
+    held = _spectral_held.setdefault(device.index, {})
+    capturing = torch.cuda.is_current_stream_capturing()
+    t = held.get((H, W))
+    if t is not None:
+        return t
+    t = cache.get((H, W))
+    if t is not None:
+        if capturing:  # a captured graph keeps the address: this entry leaves the LRU list for good
+            held[(H, W)] = cache.pop((H, W))
+        else:
+            cache.move_to_end((H, W))
+        return t
+    if capturing:
+        raise RuntimeError(f"spectral_l1: the DFT tables of a {H} x {W} image are not cached and cannot be built while the "
+                           f"stream is capturing; call it once eagerly at this shape before the capture")
+    L = hip.lib()
+    t = torch.empty(L.sisr_freq_loss_table_bytes(H, W) // 4, device=device, dtype=torch.float32)
+    hip.check(L.sisr_freq_loss_tables(H, W, hip.ptr(t), hip.stream()), "sisr_freq_loss_tables")
+    cache[(H, W)] = t
+    while len(cache) > SPECTRAL_TABLE_SLOTS:
+        cache.popitem(last=False)
+    return t
+
+
+class _SpectralL1(Function):
+    @staticmethod
+    def forward(ctx, sr, y, want_grad):
+        sr, y = sr.contiguous(), y.contiguous()
+        B, C, H, W = sr.shape
+        L = hip.lib()
+        tables = spectral_tables(sr.device, H, W)
+        value = torch.empty((), device=sr.device, dtype=torch.float32)
+        grad = torch.empty_like(sr) if want_grad and ctx.needs_input_grad[0] else None
+        nbytes = L.sisr_freq_loss_workspace_bytes(B * C, H, W, int(grad is not None))
+        ws = hip.workspace(sr.device, nbytes)
+        hip.check(L.sisr_freq_loss(hip.ptr(sr), hip.ptr(y), B * C, H, W, hip.ptr(tables), hip.ptr(value), hip.ptr(grad),
+                                   hip.ptr(ws), nbytes, hip.stream()), "sisr_freq_loss")
+        ctx.save_for_backward(grad)
+        return value
+
+    @staticmethod
+    def backward(ctx, go):
+        (grad,) = ctx.saved_tensors
+        return grad * go, None, None
+
+
+def spectral_l1(sr, y):
+    """Mean of |Re F| and |Im F| over F = rfft2(sr - y, norm='ortho') of two (B, C, H, W) fp32 batches: the mean of
+    view_as_real(F).abs(), the structurally zero imaginary parts counted.  The transform runs as matrix products on the fp32
+    MFMA, the sums in float64 in a fixed order, the value rounded to fp32 once.  The gradient goes to `sr` only, takes
+    sign(0) = 0 and is computed with the value."""
+    if sr.dim() != 4 or sr.shape != y.shape:
+        raise RuntimeError(f"spectral_l1 takes two (B, C, H, W) batches of one shape; got {tuple(sr.shape)} and {tuple(y.shape)}")
+    if sr.numel() == 0:
+        raise ValueError(f"spectral_l1: empty batch {tuple(sr.shape)}")
+    if min(sr.shape[2:]) < SPECTRAL_MIN_SIDE or max(sr.shape[2:]) > SPECTRAL_MAX_SIDE:
+        raise ValueError(f"spectral_l1: image extent {tuple(sr.shape[2:])} is outside the supported sides "
+                         f"[{SPECTRAL_MIN_SIDE}, {SPECTRAL_MAX_SIDE}]")
+    hip.ptr(sr), hip.ptr(y)  # raises on CPU or non-fp32 tensors: there is no CPU path
+    if y.requires_grad:
+        raise RuntimeError("spectral_l1: the target takes no gradient; detach it")
+    # needs_input_grad is set under no_grad as well (run_eval(request_loss=True)): the gradient launches and the sign map are skipped there
+    return _SpectralL1.apply(sr, y, torch.is_grad_enabled())
 
 
 # ----------------------------------------------------------------------------- SRCNN / VDSR pieces (csrc/basic.hip)
