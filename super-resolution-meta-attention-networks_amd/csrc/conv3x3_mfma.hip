@@ -2476,17 +2476,6 @@ __global__ void pack_conv3x3_both_kernel(const float* __restrict__ w, float* __r
   }
 }
 
-static View view_from(const int64_t* v) {
-  View r;
-  r.sB = v[0];
-  r.sH = v[1];
-  r.sW = v[2];
-  r.chi = v[3];
-  r.clo = v[4];
-  r.cdiv = (int)v[5];
-  return r;
-}
-
 extern "C" int sisr_pack_conv3x3(const float* w, float* packed, int cout, int cin, int64_t so, int64_t si,
                                  int flip_taps, int out_perm_n, int out_perm_q, int in_perm_n, int in_perm_q,
                                  void* stream) {
@@ -2664,13 +2653,28 @@ extern "C" int sisr_pack_conv3x3_many(const void* jobs_device, int n_jobs, int t
   return sisr_check_launch();
 }
 
+// select codes of sisr_conv3x3_c64 (include/sisr_hip.h; 1, 3 and 5 are refused)
+enum ConvSelect {
+  SEL_DEFAULT = 0,           // = SEL_LEAN
+  SEL_GENERAL = 2,           // general kernel only
+  SEL_LEAN = 4,              // issue-lean kernel: per-tile below the persistent threshold, persistent from it up
+  SEL_PER_TILE = 6,          // ... with the per-tile form forced
+  SEL_PERSISTENT = 7,        // ... with the persistent form forced
+  SEL_SPARSE_FIRST = 8,      // 8 / 9 / 10: structurally sparse weights, KSEL 1 / 2 / 3 of conv3x3_c64_v4_kernel
+  SEL_SPARSE_LAST = 10,
+  SEL_WINOGRAD = 11,         // the Winograd weights follow the direct packing: as SEL_DEFAULT, Winograd where it pays
+  SEL_WINOGRAD_FORCED = 12,  // ... as SEL_PERSISTENT, Winograd forced
+  SEL_DIAG_ABL3 = 13,        // -DSISR_DIAG only: ablations 3 / 6 of the general kernel
+  SEL_DIAG_ABL6 = 16,
+};
+
 // Kernel selection (per call; the library keeps no state).  Launches are sized in 4 x 32 tiles (nblk): the persistent and
 // Winograd kernels walk those, and the per-tile kernel (conv3x3_c64_v4_kernel) splits each into two V4_TH-row tiles.
 // The persistent form (conv3x3_c64_p4_kernel) is used from two tiles per workgroup on (select 7 forces it, 6 the
 // per-tile kernel; SISR_CONV_PERSISTENT=0 switches it off per call, for A/B measurements)
 static inline bool sisr_use_persistent(int variant, long nblk) {
-  if (variant == 7) return true;
-  if (variant != 4) return false;
+  if (variant == SEL_PERSISTENT) return true;
+  if (variant != SEL_LEAN) return false;
   const char* e = getenv("SISR_CONV_PERSISTENT");
   if (e && e[0] == '0') return false;
   return nblk >= 1024;
@@ -2681,9 +2685,9 @@ static inline bool sisr_use_persistent(int variant, long nblk) {
 // launched, and both forms must run one kernel.  SISR_CONV_WINOGRAD=0 switches it off per call.  The same rule selects the
 // chunked instantiation for the plain form of the fused-shuffle upsampler convs and of their input gradients.
 #define SISR_WINO_MIN_PIXELS (8L * 128 * 128)
-static inline bool sisr_use_winograd(bool avail, bool force, long pixels) {
-  if (!avail) return false;
-  if (force) return true;
+static inline bool sisr_use_winograd(int select, long pixels) {  // select: as the caller passed it
+  if (select == SEL_WINOGRAD_FORCED) return true;
+  if (select != SEL_WINOGRAD) return false;
   const char* e = getenv("SISR_CONV_WINOGRAD");
   if (e && e[0] == '0') return false;
   return pixels > SISR_WINO_MIN_PIXELS;
@@ -2716,28 +2720,146 @@ static unsigned* g_diag_conv_stamp = nullptr;  // diagnostic library only (the p
 extern "C" void sisr_diag_conv_stamp(void* buf) { g_diag_conv_stamp = static_cast<unsigned*>(buf); }
 #endif
 
+// ---- What the five conv entries share.  Each entry puts checks of its own between the shared ones, and the order decides
+// which code comes back when two violations coincide; so the shared part comes as three steps, called in this order.
+// The arguments the entries have in common, in the order of the C API (an entry without one of them passes null or 0):
+struct ConvArgs {
+  const float* x;
+  const int64_t* xview;
+  const void* w;
+  const float* bias;
+  int bias_n, bias_q;
+  float* y;
+  const int64_t* yview;
+  const float *res, *mask, *in_scale, *in_shift, *out_scale;
+  float alpha;
+  float* gap;
+  const float* gate_add;
+  float* gate_out;
+  const float* dot;
+  int B, H, W, cin, cout;
+};
+// 1. what every entry refuses first (SISR_ERR_ARG)
+static bool conv_args_missing(const ConvArgs& a) {
+  return !a.x || !a.w || !a.y || !a.xview || !a.yview || a.B <= 0 || a.H <= 0 || a.W <= 0;
+}
+// 2. the ConvParams builder: 16-byte alignment of x, w, in_scale, in_shift and of what `also` names, the view decode, the
+// stride mask of x's view (3: fp32 elements, 7: 2-byte elements; 16-byte pixel rows either way), and the plain fields
+enum { ALIGN_Y = 1, ALIGN_MAPS = 2 };  // also: y; res, mask, dot and the gates
+static int conv_params(ConvParams& p, const ConvArgs& a, int stride_mask, int also) {
+  if (!sisr_aligned16(a.x) || !sisr_aligned16(a.w) || !sisr_aligned16(a.in_scale) || !sisr_aligned16(a.in_shift) ||
+      ((also & ALIGN_Y) && !sisr_aligned16(a.y)) ||
+      ((also & ALIGN_MAPS) && (!sisr_aligned16(a.res) || !sisr_aligned16(a.mask) || !sisr_aligned16(a.dot) ||
+                               !sisr_aligned16(a.gate_add) || !sisr_aligned16(a.gate_out))))
+    return SISR_ERR_ALIGN;
+  memset(&p, 0, sizeof(p));
+  p.x = a.x;
+  p.xv = view_from(a.xview);
+  p.y = a.y;
+  p.yv = view_from(a.yview);
+  if ((p.xv.sB | p.xv.sH | p.xv.sW | p.xv.chi | p.xv.clo) & stride_mask) return SISR_ERR_ALIGN;
+  p.res = a.res;
+  p.mask = a.mask;
+  p.w = static_cast<const float*>(a.w);
+  p.bias = a.bias;
+  p.in_scale = a.in_scale;
+  p.in_shift = a.in_shift;
+  p.out_scale = a.out_scale;
+  p.gap = a.gap;
+  p.gate_add = a.gate_add;
+  p.gate_out = a.gate_out;
+  p.dot = a.dot;
+  p.alpha = a.alpha;
+  p.bias_n = a.bias_n;
+  p.bias_q = a.bias_q;
+  p.B = a.B;
+  p.H = a.H;
+  p.W = a.W;
+  p.cin_chunks = a.cin / 64;
+  p.cout_chunks = a.cout / 64;
+  return SISR_OK;
+}
+// 3. the launch size in 4 x 32 tiles of p.H x p.W
+static int conv_tiles(ConvParams& p, long& nblk) {
+  p.tiles_w = (p.W + TW - 1) / TW;
+  p.tiles_h = (p.H + TH - 1) / TH;
+  nblk = (long)p.tiles_w * p.tiles_h * p.B;
+  return nblk > 0x7fffffffL ? SISR_ERR_ARG : SISR_OK;
+}
+
+// The fused gated-residual chain (GATE prologue or DOT epilogue, each [+ residual]): what a call with gate_add, gate_out
+// or dot must satisfy.  The fp32, bf16 and x3 entries build it for 64 -> 64 without mask, shift or output scale; the
+// bf16-storage entry (storage16) asks this of every call, allows the affine / mask forms beside a DOT, and checks the
+// gates' alignment with its other maps.
+static bool conv_chain_ok(const ConvArgs& a, bool storage16) {
+  const bool gate = a.gate_add != nullptr;
+  if (gate != (a.gate_out != nullptr) || (gate && !a.in_scale) || (gate && a.dot) || (a.dot && !a.gap)) return false;
+  if (memcmp(a.xview, a.yview, 6 * sizeof(int64_t)) != 0) return false;  // skip / dot share one layout with x and y
+  if (storage16) return !(gate && (a.in_shift || a.mask));
+  return !((!gate && a.in_scale) || a.in_shift || a.mask || a.out_scale || a.cin != 64 || a.cout != 64 ||
+           !sisr_aligned16(a.gate_add) || !sisr_aligned16(a.gate_out));
+}
+
+// Form ladders: the runtime form -> the kernels' template flags.  Each calls f(AFFINE, MASK, RES, GATE, DOT) with
+// std::integral_constant arguments; a kernel family passes a generic lambda that names its kernel, grid, LDS size and
+// extra arguments once.  Only the combinations listed here are instantiated.
+using Yes = std::integral_constant<bool, true>;
+using No = std::integral_constant<bool, false>;
+// the chain forms: GATE or DOT, with or without the residual
+template <class F>
+static void conv_chain_forms(bool gate, bool rs, F&& f) {
+  if (gate) { if (rs) f(No{}, No{}, Yes{}, Yes{}, No{}); else f(No{}, No{}, No{}, Yes{}, No{}); }
+  else      { if (rs) f(No{}, No{}, Yes{}, No{}, Yes{}); else f(No{}, No{}, No{}, No{}, Yes{}); }
+}
+// the four plain forms of the fp32 lean kernels: affine with its mask, mask, residual, none
+template <class F>
+static void conv_plain_forms(bool aff, bool msk, bool rs, F&& f) {
+  if (aff) f(Yes{}, Yes{}, No{}, No{}, No{});
+  else if (msk) f(No{}, Yes{}, No{}, No{}, No{});
+  else if (rs) f(No{}, No{}, Yes{}, No{}, No{});
+  else f(No{}, No{}, No{}, No{}, No{});
+}
+// every form of the bf16, bf16 persistent and x3 kernels: the chain forms, else affine x mask x residual
+template <class F>
+static void conv_all_forms(const ConvArgs& a, F&& f) {
+  if (a.gate_add || a.dot) return conv_chain_forms(a.gate_add != nullptr, a.res != nullptr, f);
+  switch ((a.in_scale ? 4 : 0) | (a.mask ? 2 : 0) | (a.res ? 1 : 0)) {
+    case 0: f(No{}, No{}, No{}, No{}, No{}); break;
+    case 1: f(No{}, No{}, Yes{}, No{}, No{}); break;
+    case 2: f(No{}, Yes{}, No{}, No{}, No{}); break;
+    case 3: f(No{}, Yes{}, Yes{}, No{}, No{}); break;
+    case 4: f(Yes{}, No{}, No{}, No{}, No{}); break;
+    case 5: f(Yes{}, No{}, Yes{}, No{}, No{}); break;
+    case 6: f(Yes{}, Yes{}, No{}, No{}, No{}); break;
+    case 7: f(Yes{}, Yes{}, Yes{}, No{}, No{}); break;
+  }
+}
+
 extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const float* wpacked, const float* bias,
                                 int bias_n, int bias_q, float* y, const int64_t* yview, const float* res,
                                 const float* mask, const float* in_scale, const float* in_shift,
                                 const float* out_scale, float alpha, int relu, float* gap_partial,
                                 const float* gate_add, float* gate_out, const float* dot, int B, int H, int W, int cin,
                                 int cout, const void* ca_tail, int select, void* stream) {
-  if (!x || !wpacked || !y || !xview || !yview || B <= 0 || H <= 0 || W <= 0) return SISR_ERR_ARG;
+  const ConvArgs a = {x, xview, wpacked, bias, bias_n, bias_q, y, yview, res, mask, in_scale, in_shift, out_scale, alpha,
+                      gap_partial, gate_add, gate_out, dot, B, H, W, cin, cout};
+  if (conv_args_missing(a)) return SISR_ERR_ARG;
   // 11 / 12: the Winograd weights follow the direct packing (64 -> 64, or the shapes of a conv with a fused PixelShuffle(r)
   // and of its input gradient, 64 -> 64 r^2 and 64 r^2 -> 64: the chunked plain form); otherwise as 0 / 7
-  const bool wino_avail = select == 11 || select == 12, wino_force = select == 12;
+  const int asked = select;
+  const bool wino_avail = select == SEL_WINOGRAD || select == SEL_WINOGRAD_FORCED;
   if (wino_avail) {
     const int wide = cin > cout ? cin : cout;
     int r = 1;
     while (64 * r * r < wide) ++r;
     if ((cin != 64 && cout != 64) || wide != 64 * r * r) return SISR_ERR_ARG;
-    select = wino_force ? 7 : 0;
+    select = select == SEL_WINOGRAD_FORCED ? SEL_PERSISTENT : SEL_DEFAULT;
   }
   const bool wino_chunked = wino_avail && (cin != 64 || cout != 64);
   const sisr_ca_tail_host* head = static_cast<const sisr_ca_tail_host*>(ca_tail);
   if (head) {  // gate head: computed by this launch's workgroups from the previous launch's partial sums
     if (!head->head || cin != 64 || cout != 64 || !head->head_part || head->head_parts <= 0 || head->hidden < 1 ||
-        head->hidden > 16 || select != 0)
+        head->hidden > 16 || select != SEL_DEFAULT)
       return SISR_ERR_UNSUPPORTED;
     if (head->backward ? (!mask || !in_scale || in_shift != head->shift || !head->w1 || !head->w2 || !head->hid || !head->ca ||
                           !head->shift || !head->workspace || (head->mul && !head->dmul) || gate_add || dot)
@@ -2750,49 +2872,25 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
   // measurements, bit-identical results); 2 = general kernel only.  Diagnostic builds (-DSISR_DIAG) add 13 / 16.
   // 8 / 9 / 10 = structurally sparse weights (SFTMD's merged convs; KSEL 1 / 2 / 3 of conv3x3_c64_v4_kernel): the caller
   // asserts that the skipped blocks of the packed weight are zero
-  const int ksel = (select >= 8 && select <= 10) ? select - 7 : 0;
-  const int variant = (select == 0 || ksel) ? 4 : select;
+  const int ksel = (select >= SEL_SPARSE_FIRST && select <= SEL_SPARSE_LAST) ? select - SEL_SPARSE_FIRST + 1 : 0;
+  const int variant = (select == SEL_DEFAULT || ksel) ? SEL_LEAN : select;
+  const bool lean = variant == SEL_LEAN || variant == SEL_PER_TILE || variant == SEL_PERSISTENT;
 #ifdef SISR_DIAG
-  if (variant != 4 && variant != 6 && variant != 7 && variant != 2 && variant != 13 && variant != 16) return SISR_ERR_ARG;
+  if (!lean && variant != SEL_GENERAL && variant != SEL_DIAG_ABL3 && variant != SEL_DIAG_ABL6) return SISR_ERR_ARG;
 #else
-  if (variant != 4 && variant != 6 && variant != 7 && variant != 2) return SISR_ERR_ARG;
+  if (!lean && variant != SEL_GENERAL) return SISR_ERR_ARG;
 #endif
   if (ksel) {
     const bool shape_ok = ksel == 1 ? (cin == 64 && cout == 128) : (cin == 128 && cout == 64);
     if (!shape_ok || ca_tail || gate_add || gate_out || dot || in_scale || in_shift || out_scale || res) return SISR_ERR_UNSUPPORTED;
   }
   if ((cin & 63) || (cout & 63) || cin <= 0 || cout <= 0) return SISR_ERR_UNSUPPORTED;
-  if (!sisr_aligned16(x) || !sisr_aligned16(wpacked) || !sisr_aligned16(in_scale) || !sisr_aligned16(in_shift))
-    return SISR_ERR_ALIGN;
   ConvParams p;
-  memset(&p, 0, sizeof(p));
+  int rc = conv_params(p, a, 3, 0);
+  if (rc) return rc;
 #ifdef SISR_DIAG
   p.stamp = g_diag_conv_stamp;
 #endif
-  p.x = x;
-  p.xv = view_from(xview);
-  p.y = y;
-  p.yv = view_from(yview);
-  if ((p.xv.sB | p.xv.sH | p.xv.sW | p.xv.chi | p.xv.clo) & 3) return SISR_ERR_ALIGN;  // 16-B pixel rows
-  p.res = res;
-  p.mask = mask;
-  p.w = wpacked;
-  p.bias = bias;
-  p.in_scale = in_scale;
-  p.in_shift = in_shift;
-  p.out_scale = out_scale;
-  p.gap = gap_partial;
-  p.gate_add = gate_add;
-  p.gate_out = gate_out;
-  p.dot = dot;
-  p.alpha = alpha;
-  p.bias_n = bias_n;
-  p.bias_q = bias_q;
-  p.B = B;
-  p.H = H;
-  p.W = W;
-  p.cin_chunks = cin / 64;
-  p.cout_chunks = cout / 64;
   // relu: 0 none, 1 ReLU, 2 LeakyReLU(0.2); + 4: `mask` carries LeakyReLU's derivative (slope 0.2 where the map is <= 0)
   if (relu < 0 || relu > 6 || (relu & 3) == 3 || ((relu & 4) && !mask)) return SISR_ERR_ARG;
   p.relu = relu & 3;
@@ -2815,60 +2913,44 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
       p.bwd_gate.inv_hw = head->inv_hw; p.bwd_gate.R = head->hidden;
     }
   }
-  p.tiles_w = (W + TW - 1) / TW;
-  p.tiles_h = (H + TH - 1) / TH;
-  const long nblk = (long)p.tiles_w * p.tiles_h * B;
-  if (nblk > 0x7fffffffL) return SISR_ERR_ARG;
-  const dim3 grid((unsigned)nblk, p.cout_chunks);
-  if (gate_add || gate_out || dot) {
-    // fused gated-residual chain (64 -> 64 only): GATE prologue [+ residual], or DOT epilogue [+ residual]
-    const bool gate = gate_add != nullptr;
-    if (gate != (gate_out != nullptr) || (gate && !in_scale) || (gate && dot) || (dot && !gap_partial) ||
-        (!gate && in_scale) || in_shift || mask || out_scale || cin != 64 || cout != 64 ||
-        !sisr_aligned16(gate_add) || !sisr_aligned16(gate_out))
-      return SISR_ERR_UNSUPPORTED;
-    if (memcmp(xview, yview, 6 * sizeof(int64_t)) != 0) return SISR_ERR_UNSUPPORTED;  // skip / dot share one layout
-    hipStream_t st = (hipStream_t)stream;
-    const bool rs = res != nullptr;
+  long nblk;
+  if ((rc = conv_tiles(p, nblk))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const bool aff = in_scale != nullptr, msk = mask != nullptr, rs = res != nullptr, gate = gate_add != nullptr;
+  // The three kernel families of the lean forms.  The Winograd and persistent kernels walk the 4 x 32 tiles, two
+  // workgroups per CU; the Winograd weights of a 64 -> 64 conv follow its direct packing.
+  const dim3 gp((unsigned)(nblk < 512 ? nblk : 512));
+  const size_t lbp = HALO_H * HALO_W * 64 * sizeof(float);
+  auto w4 = [&](auto AF, auto MK, auto RS, auto GT, auto DT) {
+    hipLaunchKernelGGL((conv3x3_c64_w4_kernel<AF(), MK(), RS(), GT(), DT()>), gp, dim3(256), lbp, st, p, (int)nblk,
+                       wpacked + 64 * 64 * 9);
+  };
+  auto p4 = [&](auto AF, auto MK, auto RS, auto GT, auto DT) {
+    hipLaunchKernelGGL((conv3x3_c64_p4_kernel<AF(), MK(), RS(), GT(), DT()>), gp, dim3(256), lbp, st, p, (int)nblk);
+  };
+  auto v4 = [&](auto AF, auto MK, auto RS, auto GT, auto DT) {
+    const dim3 g = sisr_v4_grid(p);
+    hipLaunchKernelGGL((conv3x3_c64_v4_kernel<AF(), MK(), RS(), GT(), DT()>), g, dim3(256), V4_HALO_BYTES, st, p);
+  };
+  if (gate_add || gate_out || dot) {  // 64 -> 64 only
+    if (!conv_chain_ok(a, false)) return SISR_ERR_UNSUPPORTED;
     if (!head && sisr_use_persistent(variant, nblk)) {
-      const dim3 gp((unsigned)(nblk < 512 ? nblk : 512));
-      const size_t lbp = HALO_H * HALO_W * 64 * sizeof(float);
-      if (sisr_use_winograd(wino_avail, wino_force, (long)B * H * W)) {
-        const float* wu = wpacked + 64 * 64 * 9;
-#define W4X(RS, GT, DT)                                                                                       \
-  do {                                                                                                        \
-    hipLaunchKernelGGL((conv3x3_c64_w4_kernel<false, false, RS, GT, DT>), gp, dim3(256), lbp, st, p, (int)nblk, wu); \
-  } while (0)
-        if (gate) { if (rs) W4X(true, true, false); else W4X(false, true, false); }
-        else      { if (rs) W4X(true, false, true); else W4X(false, false, true); }
-#undef W4X
-        return sisr_check_launch();
-      }
-#define P4X(RS, GT, DT) hipLaunchKernelGGL((conv3x3_c64_p4_kernel<false, false, RS, GT, DT>), gp, dim3(256), lbp, st, p, (int)nblk)
-      if (gate) { if (rs) P4X(true, true, false); else P4X(false, true, false); }
-      else      { if (rs) P4X(true, false, true); else P4X(false, false, true); }
-#undef P4X
+      if (sisr_use_winograd(asked, (long)B * H * W)) conv_chain_forms(gate, rs, w4);
+      else conv_chain_forms(gate, rs, p4);
       return sisr_check_launch();
     }
     if (head && (!gate || head->backward)) return SISR_ERR_ARG;
-    const dim3 g = sisr_v4_grid(p);
-    const size_t lb = V4_HALO_BYTES;
-#define V4X(RS, GT, DT) hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, RS, GT, DT>), g, dim3(256), lb, st, p)
-#define V4H(RS) hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, RS, true, false, false, 0, 1>), g, dim3(256), lb + SISR_HEAD_LDS, st, p)
-    if (gate && head) {
-      if (rs) V4H(true); else V4H(false);
-    } else if (gate) {
-      if (rs) V4X(true, true, false); else V4X(false, true, false);
+    if (head) {
+      const dim3 g = sisr_v4_grid(p);
+      const size_t lb = V4_HALO_BYTES + SISR_HEAD_LDS;
+      if (rs) hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, true, true, false, false, 0, 1>), g, dim3(256), lb, st, p);
+      else hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, false, true, false, false, 0, 1>), g, dim3(256), lb, st, p);
     } else {
-      if (rs) V4X(true, false, true); else V4X(false, false, true);
+      conv_chain_forms(gate, rs, v4);
     }
-#undef V4X
-#undef V4H
     return sisr_check_launch();
   }
-  if (variant == 4 || variant == 6 || variant == 7) {
-    const bool aff = in_scale != nullptr, msk = mask != nullptr, rs = res != nullptr;
-    hipStream_t st = (hipStream_t)stream;
+  if (lean) {
     if (ksel) {
       // 1: plain (bias only); 2: LeakyReLU epilogue; 3: LeakyReLU' mask -- the forms SFTMD needs
       const bool form_ok = ksel == 1 ? (!msk && p.relu == 0) : (ksel == 2 ? (!msk && p.relu == 2) : (msk && p.mask_leaky && p.relu == 0 && !p.bias));
@@ -2886,70 +2968,44 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
       return sisr_check_launch();
     }
     if (wino_chunked && !aff && !in_shift && !msk && !rs && !leaky && !head && !out_scale && !gap_partial &&
-        sisr_use_persistent(variant, nblk) && sisr_use_winograd(true, wino_force, (long)B * H * W)) {
+        sisr_use_persistent(variant, nblk) && sisr_use_winograd(asked, (long)B * H * W)) {
       // chunked Winograd form (plain epilogue, x and y through their own views); every other form at these shapes runs direct
-      const dim3 gp((unsigned)(nblk < 512 ? nblk : 512));
-      const size_t lbp = HALO_H * HALO_W * 64 * sizeof(float);
       const float* wu = wpacked + (long)cin * cout * 9;
       hipLaunchKernelGGL((conv3x3_c64_w4_kernel<false, false, false, false, false, true>), gp, dim3(256), lbp, st, p, (int)nblk, wu);
       return sisr_check_launch();
     }
-    if (!(in_shift && !in_scale) && !(aff && !msk) && !(msk && rs) && !leaky && !head && cin == 64 && cout == 64 &&
-        memcmp(xview, yview, 6 * sizeof(int64_t)) == 0 && p.xv.clo == 64 && p.xv.chi == 0 && sisr_use_persistent(variant, nblk)) {
+    const bool lean_form = !(in_shift && !in_scale) && !(aff && !msk) && !(msk && rs);
+    if (lean_form && !leaky && !head && cin == 64 && cout == 64 && memcmp(xview, yview, 6 * sizeof(int64_t)) == 0 &&
+        p.xv.clo == 64 && p.xv.chi == 0 && sisr_use_persistent(variant, nblk)) {
       // persistent form (plain 64 -> 64 maps): see conv3x3_c64_p4_kernel
-      const dim3 gp((unsigned)(nblk < 512 ? nblk : 512));
-      const size_t lbp = HALO_H * HALO_W * 64 * sizeof(float);
-      if (sisr_use_winograd(wino_avail, wino_force, (long)B * H * W)) {
-        const float* wu = wpacked + 64 * 64 * 9;
-#define W4K(AF, MK, RS)                                                                                       \
-  do {                                                                                                        \
-    hipLaunchKernelGGL((conv3x3_c64_w4_kernel<AF, MK, RS, false, false>), gp, dim3(256), lbp, st, p, (int)nblk, wu); \
-  } while (0)
-        if (aff) W4K(true, true, false);
-        else if (msk) W4K(false, true, false);
-        else if (rs) W4K(false, false, true);
-        else W4K(false, false, false);
-#undef W4K
-        return sisr_check_launch();
+      if (sisr_use_winograd(asked, (long)B * H * W)) conv_plain_forms(aff, msk, rs, w4);
+      else conv_plain_forms(aff, msk, rs, p4);
+      return sisr_check_launch();
+    }
+    if (lean_form) {
+      if (leaky || (aff && head)) {
+        const dim3 g = sisr_v4_grid(p);
+        const size_t lb = V4_HALO_BYTES;
+        if (leaky && msk) hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, true, false, false, false, true>), g, dim3(256), lb, st, p);
+        else if (leaky) hipLaunchKernelGGL((conv3x3_c64_v4_kernel<false, false, false, false, false, true>), g, dim3(256), lb, st, p);
+        else hipLaunchKernelGGL((conv3x3_c64_v4_kernel<true, true, false, false, false, false, 0, 2>), g, dim3(256), lb + SISR_HEAD_LDS, st, p);
+      } else {
+        conv_plain_forms(aff, msk, rs, v4);
       }
-#define P4K(AF, MK, RS) hipLaunchKernelGGL((conv3x3_c64_p4_kernel<AF, MK, RS, false, false>), gp, dim3(256), lbp, st, p, (int)nblk)
-      if (aff) P4K(true, true, false);
-      else if (msk) P4K(false, true, false);
-      else if (rs) P4K(false, false, true);
-      else P4K(false, false, false);
-#undef P4K
       return sisr_check_launch();
     }
-    if (!(in_shift && !in_scale) && !(aff && !msk) && !(msk && rs)) {
-      const dim3 g = sisr_v4_grid(p);
-      const size_t lb = V4_HALO_BYTES;
-#define V4P(...) hipLaunchKernelGGL((conv3x3_c64_v4_kernel<__VA_ARGS__>), g, dim3(256), lb, st, p)
-      if (leaky && msk) V4P(false, true, false, false, false, true);
-      else if (leaky) V4P(false, false, false, false, false, true);
-      else if (aff && head)
-        hipLaunchKernelGGL((conv3x3_c64_v4_kernel<true, true, false, false, false, false, 0, 2>), g, dim3(256), lb + SISR_HEAD_LDS, st, p);
-      else if (aff) V4P(true, true, false);
-      else if (msk) V4P(false, true, false);
-      else if (rs) V4P(false, false, true);
-      else V4P(false, false, false);
-#undef V4P
-      return sisr_check_launch();
-    }
-    if (head) return SISR_ERR_UNSUPPORTED;  // the general kernel has no heads
-    const size_t lb = HALO_H * HALO_W * 64 * sizeof(float);
-    hipLaunchKernelGGL(conv3x3_c64_kernel<0>, grid, dim3(256), lb, st, p);
-    return sisr_check_launch();
   }
-  if (head) return SISR_ERR_UNSUPPORTED;
+  if (head) return SISR_ERR_UNSUPPORTED;  // the general kernel has no heads
+  const dim3 grid((unsigned)nblk, p.cout_chunks);
   const size_t lb = HALO_H * HALO_W * 64 * sizeof(float);
 #ifdef SISR_DIAG
-  if (variant == 13)
-    hipLaunchKernelGGL(conv3x3_c64_kernel<3>, grid, dim3(256), lb, (hipStream_t)stream, p);
-  else if (variant == 16)
-    hipLaunchKernelGGL(conv3x3_c64_kernel<6>, grid, dim3(256), lb, (hipStream_t)stream, p);
+  if (variant == SEL_DIAG_ABL3)
+    hipLaunchKernelGGL(conv3x3_c64_kernel<3>, grid, dim3(256), lb, st, p);
+  else if (variant == SEL_DIAG_ABL6)
+    hipLaunchKernelGGL(conv3x3_c64_kernel<6>, grid, dim3(256), lb, st, p);
   else
 #endif
-    hipLaunchKernelGGL(conv3x3_c64_kernel<0>, grid, dim3(256), lb, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(conv3x3_c64_kernel<0>, grid, dim3(256), lb, st, p);
   return sisr_check_launch();
 }
 
@@ -2963,7 +3019,9 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
 extern "C" int sisr_conv3x3_c64_geo(const float* x, const int64_t* xview, const float* wpacked, const float* bias, float* y,
                                     const int64_t* yview, float* gap_partial, int B, int H, int W, int cin, int cout, int mode,
                                     int up, int kreal, void* stream) {
-  if (!x || !wpacked || !y || !xview || !yview || B <= 0 || H <= 0 || W <= 0) return SISR_ERR_ARG;
+  const ConvArgs a = {x, xview, wpacked, bias, 1, 64, y, yview, nullptr, nullptr, nullptr, nullptr, nullptr, 1.f,
+                      gap_partial, nullptr, nullptr, nullptr, B, H, W, cin, cout};
+  if (conv_args_missing(a)) return SISR_ERR_ARG;
   if ((cin & 63) || (cout & 63) || cin <= 0 || cout <= 0) return SISR_ERR_UNSUPPORTED;
   if (mode < 1 || mode > 4) return SISR_ERR_ARG;
   if (up < 0 || up > 1 || (mode != 1 && up) || kreal < 0) return SISR_ERR_UNSUPPORTED;
@@ -2971,26 +3029,9 @@ extern "C" int sisr_conv3x3_c64_geo(const float* x, const int64_t* xview, const 
   if (sub) mode = 2;
   if (mode != 2 && (H < 2 || W < 2 || ((H | W) & ((1 << up) - 1)))) return SISR_ERR_ARG;  // ReflectionPad2d(1) needs 2 pixels
   if (mode == 2 && (H < 3 || W < 3)) return SISR_ERR_ARG;
-  if (!sisr_aligned16(x) || !sisr_aligned16(wpacked) || !sisr_aligned16(y)) return SISR_ERR_ALIGN;
   ConvParams p;
-  memset(&p, 0, sizeof(p));
-#ifdef SISR_DIAG
-  p.stamp = nullptr;
-#endif
-  p.x = x;
-  p.xv = view_from(xview);
-  p.y = y;
-  p.yv = view_from(yview);
-  if ((p.xv.sB | p.xv.sH | p.xv.sW | p.xv.chi | p.xv.clo) & 3) return SISR_ERR_ALIGN;
-  p.w = wpacked;
-  p.bias = bias;
-  p.gap = gap_partial;
-  p.alpha = 1.f;
-  p.bias_n = 1;
-  p.bias_q = 64;
-  p.B = B;
-  p.cin_chunks = cin / 64;
-  p.cout_chunks = cout / 64;
+  int rc = conv_params(p, a, 3, ALIGN_Y);
+  if (rc) return rc;
   p.geo_reflect = mode != 2;
   p.geo_up = sub ? 1 : up;
   p.geo_sub = sub;
@@ -2998,15 +3039,11 @@ extern "C" int sisr_conv3x3_c64_geo(const float* x, const int64_t* xview, const 
   p.geo_h = mode == 2 ? H - 2 : H;
   p.geo_w = mode == 2 ? W - 2 : W;
   if (mode == 3) {  // H, W are the INPUT's; the output has every second pixel of the stride-1 result
-    H = (H + 1) / 2;
-    W = (W + 1) / 2;
+    p.H = (H + 1) / 2;
+    p.W = (W + 1) / 2;
   }
-  p.H = H;
-  p.W = W;
-  p.tiles_w = (W + TW - 1) / TW;
-  p.tiles_h = (H + TH - 1) / TH;
-  const long nblk = (long)p.tiles_w * p.tiles_h * B;
-  if (nblk > 0x7fffffffL) return SISR_ERR_ARG;
+  long nblk;
+  if ((rc = conv_tiles(p, nblk))) return rc;
   const int ksel = (cin == 64 && kreal > 0 && kreal <= 8) ? 5 : ((cin == 64 && kreal > 0 && kreal <= 32) ? 4 : 0);
   const dim3 g = sisr_v4_grid(p);
   hipStream_t st = (hipStream_t)stream;
@@ -3042,113 +3079,54 @@ extern "C" int sisr_pack_conv3x3_bf16_both(const float* w, void* packed_fwd, voi
   return sisr_check_launch();
 }
 
+// The bf16 and x3 entries have one contract: their own checks around the shared steps, in their order.  Before
+// conv_params the chain contract, the channel counts and the affine form; after it the ReLU code, the tile count and
+// the partial-sum forms.
+static int conv_params_lowp(ConvParams& p, long& nblk, const ConvArgs& a, int relu) {
+  if ((a.gate_add || a.gate_out || a.dot) && !conv_chain_ok(a, false)) return SISR_ERR_UNSUPPORTED;
+  if ((a.cin & 63) || (a.cout & 63) || a.cin <= 0 || a.cout <= 0) return SISR_ERR_UNSUPPORTED;
+  if (a.in_shift && !a.in_scale) return SISR_ERR_UNSUPPORTED;
+  int rc = conv_params(p, a, 3, 0);
+  if (rc) return rc;
+  if (relu != 0 && relu != 1) return SISR_ERR_UNSUPPORTED;  // LeakyReLU codes: fp32 kernels only
+  p.relu = relu;
+  if ((rc = conv_tiles(p, nblk))) return rc;
+  if (a.gap && !a.dot && (a.mask || a.res)) return SISR_ERR_UNSUPPORTED;
+  return SISR_OK;
+}
+
 extern "C" int sisr_conv3x3_c64_bf16(const float* x, const int64_t* xview, const void* wpacked_bf16, const float* bias,
                                      int bias_n, int bias_q, float* y, const int64_t* yview, const float* res,
                                      const float* mask, const float* in_scale, const float* in_shift,
                                      const float* out_scale, float alpha, int relu, float* gap_partial,
                                      const float* gate_add, float* gate_out, const float* dot, int B, int H, int W,
                                      int cin, int cout, int select, void* stream) {
-  if (!x || !wpacked_bf16 || !y || !xview || !yview || B <= 0 || H <= 0 || W <= 0) return SISR_ERR_ARG;
+  const ConvArgs a = {x, xview, wpacked_bf16, bias, bias_n, bias_q, y, yview, res, mask, in_scale, in_shift, out_scale, alpha,
+                      gap_partial, gate_add, gate_out, dot, B, H, W, cin, cout};
+  if (conv_args_missing(a)) return SISR_ERR_ARG;
   if (select != 0 && select != 1) return SISR_ERR_ARG;
   const bool persist = select != 1;  // per call: 0 = persistent tile loop where it applies, 1 = per-tile kernel
-  const bool gate = gate_add != nullptr;
-  if (gate_add || gate_out || dot) {  // fused gated-residual chain, same contract as the fp32 entry
-    if (gate != (gate_out != nullptr) || (gate && !in_scale) || (gate && dot) || (dot && !gap_partial) ||
-        (!gate && in_scale) || in_shift || mask || out_scale || cin != 64 || cout != 64 || !sisr_aligned16(gate_add) ||
-        !sisr_aligned16(gate_out) || memcmp(xview, yview, 6 * sizeof(int64_t)) != 0)
-      return SISR_ERR_UNSUPPORTED;
-  }
-  if ((cin & 63) || (cout & 63) || cin <= 0 || cout <= 0) return SISR_ERR_UNSUPPORTED;
-  if (in_shift && !in_scale) return SISR_ERR_UNSUPPORTED;
-  if (!sisr_aligned16(x) || !sisr_aligned16(wpacked_bf16) || !sisr_aligned16(in_scale) || !sisr_aligned16(in_shift))
-    return SISR_ERR_ALIGN;
   ConvParams p;
-  memset(&p, 0, sizeof(p));
-  p.x = x;
-  p.xv = view_from(xview);
-  p.y = y;
-  p.yv = view_from(yview);
-  if ((p.xv.sB | p.xv.sH | p.xv.sW | p.xv.chi | p.xv.clo) & 3) return SISR_ERR_ALIGN;
-  p.res = res;
-  p.mask = mask;
-  p.w = reinterpret_cast<const float*>(wpacked_bf16);
-  p.bias = bias;
-  p.in_scale = in_scale;
-  p.in_shift = in_shift;
-  p.out_scale = out_scale;
-  p.gap = gap_partial;
-  p.gate_add = gate_add;
-  p.gate_out = gate_out;
-  p.dot = dot;
-  p.alpha = alpha;
-  p.bias_n = bias_n;
-  p.bias_q = bias_q;
-  p.B = B;
-  p.H = H;
-  p.W = W;
-  p.cin_chunks = cin / 64;
-  p.cout_chunks = cout / 64;
-  if (relu != 0 && relu != 1) return SISR_ERR_UNSUPPORTED;  // LeakyReLU codes: fp32 kernels only
-  p.relu = relu;
-  p.tiles_w = (W + TW - 1) / TW;
-  p.tiles_h = (H + TH - 1) / TH;
-  const long nblk = (long)p.tiles_w * p.tiles_h * B;
-  if (nblk > 0x7fffffffL) return SISR_ERR_ARG;
-  const dim3 grid((unsigned)nblk, p.cout_chunks);
-  if (gap_partial && !dot && (mask || res)) return SISR_ERR_UNSUPPORTED;
-  const size_t lb_halo = HALO_H * HALO_W * BH_PIX, lb_out = TH * TW * BE_LD * sizeof(float);
-  const size_t lb = lb_halo > lb_out ? lb_halo : lb_out;
+  long nblk;
+  const int rc = conv_params_lowp(p, nblk, a, relu);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (persist && cin == 64 && cout == 64 && nblk >= 1024) {
     // 64 -> 64 with enough tiles to give every persistent workgroup at least two: the double-buffered tile loop
-    const int G = 512;  // two workgroups per CU
+    const dim3 pg(512);  // two workgroups per CU
     const size_t plb = 2 * (size_t)PB_BUF;
-    const dim3 pg(G);
-    const int total = (int)nblk;
-#define PBX(AF, MK, RS, GT, DT)                                                                              \
-  do {                                                                                                       \
-    SISR_ALLOW_LDS((conv3x3_c64_bf16_persist_kernel<AF, MK, RS, GT, DT>), plb);                              \
-    hipLaunchKernelGGL((conv3x3_c64_bf16_persist_kernel<AF, MK, RS, GT, DT>), pg, dim3(256), plb, st, p, total); \
-  } while (0)
-    if (gate) { if (res) PBX(false, false, true, true, false); else PBX(false, false, false, true, false); }
-    else if (dot) { if (res) PBX(false, false, true, false, true); else PBX(false, false, false, false, true); }
-    else {
-      const int sel = (in_scale ? 4 : 0) | (mask ? 2 : 0) | (res ? 1 : 0);
-      switch (sel) {
-        case 0: PBX(false, false, false, false, false); break;
-        case 1: PBX(false, false, true, false, false); break;
-        case 2: PBX(false, true, false, false, false); break;
-        case 3: PBX(false, true, true, false, false); break;
-        case 4: PBX(true, false, false, false, false); break;
-        case 5: PBX(true, false, true, false, false); break;
-        case 6: PBX(true, true, false, false, false); break;
-        case 7: PBX(true, true, true, false, false); break;
-      }
-    }
-#undef PBX
+    conv_all_forms(a, [&](auto AF, auto MK, auto RS, auto GT, auto DT) {
+      SISR_ALLOW_LDS((conv3x3_c64_bf16_persist_kernel<AF(), MK(), RS(), GT(), DT()>), plb);
+      hipLaunchKernelGGL((conv3x3_c64_bf16_persist_kernel<AF(), MK(), RS(), GT(), DT()>), pg, dim3(256), plb, st, p, (int)nblk);
+    });
     return sisr_check_launch();
   }
-  if (gate || dot) {
-#define BFX(RS, GT, DT) hipLaunchKernelGGL((conv3x3_c64_bf16_kernel<false, false, RS, GT, DT>), grid, dim3(256), lb, st, p)
-    if (gate) { if (res) BFX(true, true, false); else BFX(false, true, false); }
-    else      { if (res) BFX(true, false, true); else BFX(false, false, true); }
-#undef BFX
-    return sisr_check_launch();
-  }
-  const int sel = (in_scale ? 4 : 0) | (mask ? 2 : 0) | (res ? 1 : 0);
-  switch (sel) {
-#define BF_CASE(i, a, m, r) \
-  case i: hipLaunchKernelGGL((conv3x3_c64_bf16_kernel<a, m, r>), grid, dim3(256), lb, st, p); break;
-    BF_CASE(0, false, false, false)
-    BF_CASE(1, false, false, true)
-    BF_CASE(2, false, true, false)
-    BF_CASE(3, false, true, true)
-    BF_CASE(4, true, false, false)
-    BF_CASE(5, true, false, true)
-    BF_CASE(6, true, true, false)
-    BF_CASE(7, true, true, true)
-#undef BF_CASE
-  }
+  const dim3 grid((unsigned)nblk, p.cout_chunks);
+  const size_t lb_halo = HALO_H * HALO_W * BH_PIX, lb_out = TH * TW * BE_LD * sizeof(float);
+  const size_t lb = lb_halo > lb_out ? lb_halo : lb_out;
+  conv_all_forms(a, [&](auto AF, auto MK, auto RS, auto GT, auto DT) {
+    hipLaunchKernelGGL((conv3x3_c64_bf16_kernel<AF(), MK(), RS(), GT(), DT()>), grid, dim3(256), lb, st, p);
+  });
   return sisr_check_launch();
 }
 
@@ -3164,7 +3142,6 @@ extern "C" int sisr_conv3x3_c64_bf16s(const float* x, const int64_t* xview, cons
                                       const float* mask, const float* in_scale, const float* in_shift, float alpha, int relu,
                                       float* gap_partial, const float* gate_add, float* gate_out, const float* dot, int B,
                                       int H, int W, int storage, void* stream) {
-  if (!x || !wpacked_bf16 || !y || !xview || !yview || B <= 0 || H <= 0 || W <= 0 || storage < 0 || storage > 15) return SISR_ERR_ARG;
 #ifdef SISR_DIAG
   const float* stamp_buf = nullptr;  // tools/bf16s_timeline.py: the plain bf16 -> bf16 form with in-kernel cycle sums
   if (getenv("SISR_BF16S_STAMP") && storage == 3 && dot && !gap_partial && !gate_add && !mask && !res && !in_scale) {
@@ -3172,46 +3149,20 @@ extern "C" int sisr_conv3x3_c64_bf16s(const float* x, const int64_t* xview, cons
     dot = nullptr;
   }
 #endif
+  const ConvArgs a = {x, xview, wpacked_bf16, bias, bias_n, bias_q, y, yview, res, mask, in_scale, in_shift, nullptr, alpha,
+                      gap_partial, gate_add, gate_out, dot, B, H, W, 64, 64};
+  if (conv_args_missing(a) || storage < 0 || storage > 15) return SISR_ERR_ARG;
   const bool gate = gate_add != nullptr;
-  if (gate != (gate_out != nullptr) || (gate && !in_scale) || (gate && dot) || (dot && !gap_partial) ||
-      (gate && (in_shift || mask)) || memcmp(xview, yview, 6 * sizeof(int64_t)) != 0)
-    return SISR_ERR_UNSUPPORTED;
+  if (!conv_chain_ok(a, true)) return SISR_ERR_UNSUPPORTED;
   if (in_shift && !in_scale) return SISR_ERR_UNSUPPORTED;
   if (gap_partial && !dot && (mask || res)) return SISR_ERR_UNSUPPORTED;
   if (relu != 0 && relu != 1) return SISR_ERR_UNSUPPORTED;
-  if (!sisr_aligned16(x) || !sisr_aligned16(y) || !sisr_aligned16(wpacked_bf16) || !sisr_aligned16(in_scale) ||
-      !sisr_aligned16(in_shift) || !sisr_aligned16(gate_add) || !sisr_aligned16(gate_out) || !sisr_aligned16(res) ||
-      !sisr_aligned16(mask) || !sisr_aligned16(dot))
-    return SISR_ERR_ALIGN;
   ConvParams p;
-  memset(&p, 0, sizeof(p));
-  p.x = x;
-  p.xv = view_from(xview);
-  p.y = y;
-  p.yv = view_from(yview);
-  if ((p.xv.sB | p.xv.sH | p.xv.sW | p.xv.chi | p.xv.clo) & 7) return SISR_ERR_ALIGN;  // 16-B pieces of 2-byte elements
-  p.res = res;
-  p.mask = mask;
-  p.w = reinterpret_cast<const float*>(wpacked_bf16);
-  p.bias = bias;
-  p.in_scale = in_scale;
-  p.in_shift = in_shift;
-  p.gap = gap_partial;
-  p.gate_add = gate_add;
-  p.gate_out = gate_out;
-  p.dot = dot;
-  p.alpha = alpha;
-  p.bias_n = bias_n;
-  p.bias_q = bias_q;
-  p.B = B;
-  p.H = H;
-  p.W = W;
-  p.cin_chunks = p.cout_chunks = 1;
+  int rc = conv_params(p, a, 7, ALIGN_Y | ALIGN_MAPS);
+  if (rc) return rc;
   p.relu = relu;
-  p.tiles_w = (W + TW - 1) / TW;
-  p.tiles_h = (H + TH - 1) / TH;
-  const long nblk = (long)p.tiles_w * p.tiles_h * B;
-  if (nblk > 0x7fffffffL) return SISR_ERR_ARG;
+  long nblk;
+  if ((rc = conv_tiles(p, nblk))) return rc;
   const int G = (int)(nblk < 512 ? nblk : 512);  // two workgroups per CU; fewer tiles than that: one tile each
   const size_t plb = 2 * (size_t)PB_BUF;
   const dim3 pg(G);
@@ -3260,85 +3211,30 @@ extern "C" int sisr_conv3x3_c64_x3(const float* x, const int64_t* xview, const v
                                      const float* out_scale, float alpha, int relu, float* gap_partial,
                                      const float* gate_add, float* gate_out, const float* dot, int B, int H, int W,
                                      int cin, int cout, int select, void* stream) {
-  if (!x || !wpacked_bf16 || !y || !xview || !yview || B <= 0 || H <= 0 || W <= 0) return SISR_ERR_ARG;
+  const ConvArgs a = {x, xview, wpacked_bf16, bias, bias_n, bias_q, y, yview, res, mask, in_scale, in_shift, out_scale, alpha,
+                      gap_partial, gate_add, gate_out, dot, B, H, W, cin, cout};
+  if (conv_args_missing(a)) return SISR_ERR_ARG;
   if (select != 0) return SISR_ERR_ARG;  // one kernel family; the argument keeps the three conv entries call-compatible
-  const bool gate = gate_add != nullptr;
-  if (gate_add || gate_out || dot) {  // fused gated-residual chain, same contract as the fp32 entry
-    if (gate != (gate_out != nullptr) || (gate && !in_scale) || (gate && dot) || (dot && !gap_partial) ||
-        (!gate && in_scale) || in_shift || mask || out_scale || cin != 64 || cout != 64 || !sisr_aligned16(gate_add) ||
-        !sisr_aligned16(gate_out) || memcmp(xview, yview, 6 * sizeof(int64_t)) != 0)
-      return SISR_ERR_UNSUPPORTED;
-  }
-  if ((cin & 63) || (cout & 63) || cin <= 0 || cout <= 0) return SISR_ERR_UNSUPPORTED;
-  if (in_shift && !in_scale) return SISR_ERR_UNSUPPORTED;
-  if (!sisr_aligned16(x) || !sisr_aligned16(wpacked_bf16) || !sisr_aligned16(in_scale) || !sisr_aligned16(in_shift))
-    return SISR_ERR_ALIGN;
   ConvParams p;
-  memset(&p, 0, sizeof(p));
-  p.x = x;
-  p.xv = view_from(xview);
-  p.y = y;
-  p.yv = view_from(yview);
-  if ((p.xv.sB | p.xv.sH | p.xv.sW | p.xv.chi | p.xv.clo) & 3) return SISR_ERR_ALIGN;
-  p.res = res;
-  p.mask = mask;
-  p.w = reinterpret_cast<const float*>(wpacked_bf16);
-  p.bias = bias;
-  p.in_scale = in_scale;
-  p.in_shift = in_shift;
-  p.out_scale = out_scale;
-  p.gap = gap_partial;
-  p.gate_add = gate_add;
-  p.gate_out = gate_out;
-  p.dot = dot;
-  p.alpha = alpha;
-  p.bias_n = bias_n;
-  p.bias_q = bias_q;
-  p.B = B;
-  p.H = H;
-  p.W = W;
-  p.cin_chunks = cin / 64;
-  p.cout_chunks = cout / 64;
-  if (relu != 0 && relu != 1) return SISR_ERR_UNSUPPORTED;  // LeakyReLU codes: fp32 kernels only
-  p.relu = relu;
-  p.tiles_w = (W + TW - 1) / TW;
-  p.tiles_h = (H + TH - 1) / TH;
-  const long nblk = (long)p.tiles_w * p.tiles_h * B;
-  if (nblk > 0x7fffffffL) return SISR_ERR_ARG;
+  long nblk;
+  const int rc = conv_params_lowp(p, nblk, a, relu);
+  if (rc) return rc;
   const dim3 grid((unsigned)nblk, p.cout_chunks);
-  if (gap_partial && !dot && (mask || res)) return SISR_ERR_UNSUPPORTED;
   const size_t lb_halo = 3 * (size_t)X3_PLANE, lb_out = TH * TW * BE_LD * sizeof(float);
   const size_t lb = lb_halo > lb_out ? lb_halo : lb_out;
   hipStream_t st = (hipStream_t)stream;
   const long wplane = (long)cin * cout * 9 * 2;  // bytes between the hi / mid / lo planes of the packed weights
-#define X3L(AF, MK, RS, GT, DT)                                                                        \
-  do {                                                                                                 \
-    SISR_ALLOW_LDS((conv3x3_c64_x3_kernel<AF, MK, RS, GT, DT>), lb);                                   \
-    hipLaunchKernelGGL((conv3x3_c64_x3_kernel<AF, MK, RS, GT, DT>), grid, dim3(256), lb, st, p, wplane); \
-  } while (0)
 #ifdef SISR_DIAG
-  if (getenv("SISR_X3_STAMP") && dot && !gate && !in_scale && !mask && !res) {  // tools/x3_phases.py
+  if (getenv("SISR_X3_STAMP") && dot && !gate_add && !in_scale && !mask && !res) {  // tools/x3_phases.py
     SISR_ALLOW_LDS((conv3x3_c64_x3_kernel<false, false, false, false, false, true>), lb);
     hipLaunchKernelGGL((conv3x3_c64_x3_kernel<false, false, false, false, false, true>), grid, dim3(256), lb, st, p, wplane);
     return sisr_check_launch();
   }
 #endif
-  if (gate) { if (res) X3L(false, false, true, true, false); else X3L(false, false, false, true, false); }
-  else if (dot) { if (res) X3L(false, false, true, false, true); else X3L(false, false, false, false, true); }
-  else {
-    const int sel = (in_scale ? 4 : 0) | (mask ? 2 : 0) | (res ? 1 : 0);
-    switch (sel) {
-      case 0: X3L(false, false, false, false, false); break;
-      case 1: X3L(false, false, true, false, false); break;
-      case 2: X3L(false, true, false, false, false); break;
-      case 3: X3L(false, true, true, false, false); break;
-      case 4: X3L(true, false, false, false, false); break;
-      case 5: X3L(true, false, true, false, false); break;
-      case 6: X3L(true, true, false, false, false); break;
-      case 7: X3L(true, true, true, false, false); break;
-    }
-  }
-#undef X3L
+  conv_all_forms(a, [&](auto AF, auto MK, auto RS, auto GT, auto DT) {
+    SISR_ALLOW_LDS((conv3x3_c64_x3_kernel<AF(), MK(), RS(), GT(), DT()>), lb);
+    hipLaunchKernelGGL((conv3x3_c64_x3_kernel<AF(), MK(), RS(), GT(), DT()>), grid, dim3(256), lb, st, p, wplane);
+  });
   return sisr_check_launch();
 }
 

@@ -16,17 +16,6 @@
 #include "sisr_common.h"
 #include "conv_rgb_out.h"
 
-static View view_from(const int64_t* v) {
-  View r;
-  r.sB = v[0];
-  r.sH = v[1];
-  r.sW = v[2];
-  r.chi = v[3];
-  r.clo = v[4];
-  r.cdiv = (int)v[5];
-  return r;
-}
-
 // ------------------------------------------------------------------ 3 -> 64k
 struct Cin3Params {
   const float* x;  // [B][3][H][W]

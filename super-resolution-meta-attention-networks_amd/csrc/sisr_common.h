@@ -19,6 +19,8 @@ struct View {
   int cdiv;
   __host__ __device__ long chunk(int q) const { return (long)(q / cdiv) * chi + (long)(q % cdiv) * clo; }
 };
+// The six int64 of a view argument of the C API (include/sisr_hip.h), in the order of the fields above.
+static inline View view_from(const int64_t* v) { return View{v[0], v[1], v[2], v[3], v[4], (int)v[5]}; }
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // Zero a float4 with a lane mask by bitwise AND: exact zeros even if the (clamped-address) load

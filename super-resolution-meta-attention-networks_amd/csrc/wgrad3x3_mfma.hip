@@ -1497,17 +1497,6 @@ struct ReduceBatch {
 };
 __global__ __launch_bounds__(64 * RG) void wgrad_reduce_batch_kernel(ReduceBatch bt) { wgrad_reduce_body(bt.job[blockIdx.y]); }
 
-static View view_from(const int64_t* v) {
-  View r;
-  r.sB = v[0];
-  r.sH = v[1];
-  r.sW = v[2];
-  r.chi = v[3];
-  r.clo = v[4];
-  r.cdiv = (int)v[5];
-  return r;
-}
-
 static int wgrad_split(int B, int H, int W, int units) {
   const long tiles = (long)B * ((H + WT_H - 1) / WT_H) * ((W + WT_W - 1) / WT_W);
   long S = 512 / units;  // two workgroups per CU resident across the whole grid
@@ -1538,6 +1527,71 @@ extern "C" size_t sisr_wgrad3x3_c64_workspace_bytes(int B, int H, int W, int cin
   size_t slabs = (size_t)(S * units > 512 ? S * units : 512);
   if ((size_t)Sf * units > slabs) slabs = (size_t)Sf * units;
   return (slabs * SLAB + (size_t)512 * cout) * sizeof(float);
+}
+
+// What the single-launch weight gradients share.  wgrad_params: the argument checks (in this order: it decides the code
+// when two violations coincide), the view decode and the geometry fields; stride_mask 3 = fp32 maps, 7 = 2-byte elements
+// (16-byte pieces either way); tile_h is the family's tile height.
+static int wgrad_params(WgradParams& p, const float* x, const int64_t* xview, const float* dy, const int64_t* dyview,
+                        const float* dy_scale, const float* dy_shift, const float* dw, float* workspace, size_t workspace_bytes,
+                        size_t workspace_need, int B, int H, int W, int cin, int cout, int stride_mask, int tile_h) {
+  if (!x || !dy || !dw || !xview || !dyview || !workspace || B <= 0 || H <= 0 || W <= 0) return SISR_ERR_ARG;
+  if ((cin & 63) || (cout & 63) || cin <= 0 || cout <= 0) return SISR_ERR_UNSUPPORTED;
+  if (workspace_bytes < workspace_need) return SISR_ERR_ARG;
+  if (!sisr_aligned16(x) || !sisr_aligned16(dy) || !sisr_aligned16(workspace) || !sisr_aligned16(dy_scale) ||
+      !sisr_aligned16(dy_shift))
+    return SISR_ERR_ALIGN;
+  p = {};
+  p.x = x;
+  p.xv = view_from(xview);
+  p.dy = dy;
+  p.yv = view_from(dyview);
+  if ((p.xv.sB | p.xv.sH | p.xv.sW | p.xv.chi | p.xv.clo | p.yv.sB | p.yv.sH | p.yv.sW | p.yv.chi | p.yv.clo) & stride_mask)
+    return SISR_ERR_ALIGN;
+  p.dy_scale = dy_scale;
+  p.dy_shift = dy_shift;
+  p.B = B;
+  p.H = H;
+  p.W = W;
+  p.cin_chunks = cin / 64;
+  p.cout_chunks = cout / 64;
+  p.tiles_w = (W + WT_W - 1) / WT_W;
+  p.tiles_h = (H + tile_h - 1) / tile_h;
+  return SISR_OK;
+}
+// The reduction that sums a gradient launch's slabs into dw / dbias: `r` arrives zeroed, or with the optional mapped /
+// unit_map / o_lim / i_lim of the forms that have them.  wgrad_reduce checks the gradient kernel's launch and runs it.
+static void wgrad_reduce_fill(ReduceParams& r, const WgradParams& p, int units, float alpha, float* dw, int64_t so, int64_t si,
+                              int flip_taps, int out_perm_n, int out_perm_q, int in_perm_n, int in_perm_q, float* dbias,
+                              int bias_n, int bias_q) {
+  r.slabs = p.slabs;
+  r.bias_slabs = p.bias_slabs;
+  r.dw = dw;
+  r.db = dbias;
+  r.so = so;
+  r.si = si;
+  r.alpha = alpha;
+  r.S = p.S;
+  r.units = units;
+  r.cin_chunks = p.cin_chunks;
+  r.cout_chunks = p.cout_chunks;
+  r.flip = flip_taps;
+  r.on = out_perm_n;
+  r.oq = out_perm_q;
+  r.in_ = in_perm_n;
+  r.iq = in_perm_q;
+  r.bias_n = bias_n;
+  r.bias_q = bias_q;
+}
+static int wgrad_reduce(ReduceParams& r, const WgradParams& p, int units, float alpha, float* dw, int64_t so, int64_t si,
+                        int flip_taps, int out_perm_n, int out_perm_q, int in_perm_n, int in_perm_q, float* dbias, int bias_n,
+                        int bias_q, void* stream) {
+  const int rc = sisr_check_launch();
+  if (rc) return rc;
+  wgrad_reduce_fill(r, p, units, alpha, dw, so, si, flip_taps, out_perm_n, out_perm_q, in_perm_n, in_perm_q, dbias, bias_n, bias_q);
+  const long total = (long)units * SLAB + (dbias ? 64 * p.cout_chunks : 0);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(64, RG), 0, (hipStream_t)stream, r);
+  return sisr_check_launch();
 }
 
 static int wgrad_fp32_launch(const float* x, const int64_t* xview, const float* dy, const int64_t* dyview,
@@ -1580,28 +1634,10 @@ static int wgrad_fp32_launch(const float* x, const int64_t* xview, const float* 
                              int in_perm_q, float* dbias, int bias_n, int bias_q, float* workspace,
                              size_t workspace_bytes, int B, int H, int W, int cin, int cout,
                              unsigned long long active_units, int geo, int geo_up, int o_lim, int i_lim, void* stream) {
-  if (!x || !dy || !dw || !xview || !dyview || !workspace || B <= 0 || H <= 0 || W <= 0) return SISR_ERR_ARG;
-  if ((cin & 63) || (cout & 63) || cin <= 0 || cout <= 0) return SISR_ERR_UNSUPPORTED;
-  if (workspace_bytes < sisr_wgrad3x3_c64_workspace_bytes(B, H, W, cin, cout)) return SISR_ERR_ARG;
-  if (!sisr_aligned16(x) || !sisr_aligned16(dy) || !sisr_aligned16(workspace) || !sisr_aligned16(dy_scale) ||
-      !sisr_aligned16(dy_shift))
-    return SISR_ERR_ALIGN;
-  WgradParams p = {};
-  p.x = x;
-  p.xv = view_from(xview);
-  p.dy = dy;
-  p.yv = view_from(dyview);
-  if ((p.xv.sB | p.xv.sH | p.xv.sW | p.xv.chi | p.xv.clo | p.yv.sB | p.yv.sH | p.yv.sW | p.yv.chi | p.yv.clo) & 3)
-    return SISR_ERR_ALIGN;
-  p.dy_scale = dy_scale;
-  p.dy_shift = dy_shift;
-  p.B = B;
-  p.H = H;
-  p.W = W;
-  p.cin_chunks = cin / 64;
-  p.cout_chunks = cout / 64;
-  p.tiles_w = (W + WT_W - 1) / WT_W;
-  p.tiles_h = (H + WT_H - 1) / WT_H;
+  WgradParams p;
+  const int rc = wgrad_params(p, x, xview, dy, dyview, dy_scale, dy_shift, dw, workspace, workspace_bytes,
+                              sisr_wgrad3x3_c64_workspace_bytes(B, H, W, cin, cout), B, H, W, cin, cout, 3, WT_H);
+  if (rc) return rc;
   p.geo_reflect = geo;
   p.geo_up = geo_up & 1;
   p.geo_ysub = (geo_up >> 1) & 1;
@@ -1669,31 +1705,10 @@ static int wgrad_fp32_launch(const float* x, const int64_t* xview, const float* 
       hipLaunchKernelGGL(wgrad3x3_c64_kernel, dim3(p.S, units), dim3(256), lds_bytes, (hipStream_t)stream, p);
     }
   }
-  int rc = sisr_check_launch();
-  if (rc) return rc;
-  r.slabs = p.slabs;
-  r.bias_slabs = p.bias_slabs;
-  r.dw = dw;
-  r.db = dbias;
-  r.so = so;
-  r.si = si;
-  r.alpha = alpha;
-  r.S = p.S;
-  r.units = units;
-  r.cin_chunks = p.cin_chunks;
-  r.cout_chunks = p.cout_chunks;
-  r.flip = flip_taps;
-  r.on = out_perm_n;
-  r.oq = out_perm_q;
-  r.in_ = in_perm_n;
-  r.iq = in_perm_q;
-  r.bias_n = bias_n;
-  r.bias_q = bias_q;
   r.o_lim = o_lim;
   r.i_lim = i_lim;
-  const long total = (long)units * SLAB + (dbias ? cout : 0);
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(64, RG), 0, (hipStream_t)stream, r);
-  return sisr_check_launch();
+  return wgrad_reduce(r, p, units, alpha, dw, so, si, flip_taps, out_perm_n, out_perm_q, in_perm_n, in_perm_q, dbias, bias_n,
+                      bias_q, stream);
 }
 
 // ---- batched launch of sisr_wgrad3x3_c64_geo jobs of different geometries (<= 8 per launch, any number per call)
@@ -1807,24 +1822,7 @@ extern "C" int sisr_wgrad3x3_c64_geo_batch(const void* jobs_host, int njobs, flo
       p.bias_slabs = j.dbias ? ws : nullptr;
       ws += (size_t)p.S * j.cout + 64;
       ws = reinterpret_cast<float*>(((uintptr_t)ws + 15) & ~(uintptr_t)15);
-      r.slabs = p.slabs;
-      r.bias_slabs = p.bias_slabs;
-      r.dw = j.dw;
-      r.db = j.dbias;
-      r.so = (long)j.ci_real * 9;
-      r.si = 9;
-      r.alpha = 1.f;
-      r.S = p.S;
-      r.units = units;
-      r.cin_chunks = p.cin_chunks;
-      r.cout_chunks = p.cout_chunks;
-      r.flip = 0;
-      r.on = 1;
-      r.oq = 64;
-      r.in_ = 1;
-      r.iq = 64;
-      r.bias_n = 1;
-      r.bias_q = 64;
+      wgrad_reduce_fill(r, p, units, 1.f, j.dw, (long)j.ci_real * 9, 9, 0, 1, 64, 1, 64, j.dbias, 1, 64);
       r.o_lim = j.co_real;
       r.i_lim = j.ci_real;
       if (p.S > smax) smax = p.S;
@@ -1903,25 +1901,7 @@ extern "C" int sisr_wgrad3x3_c64_batch(const void* jobs_host, int njobs, const i
     p.slabs = workspace + (size_t)k * per_job;
     p.bias_slabs = j.dbias ? p.slabs + (size_t)S * 4 * SLAB : nullptr;
     p.mapped = 0;
-    ReduceParams& r = rb.job[k];
-    r.slabs = p.slabs;
-    r.bias_slabs = p.bias_slabs;
-    r.dw = j.dw;
-    r.db = j.dbias;
-    r.so = 64 * 9;
-    r.si = 9;
-    r.alpha = 1.f;
-    r.S = S;
-    r.units = 4;
-    r.cin_chunks = r.cout_chunks = 1;
-    r.flip = 0;
-    r.on = 1;
-    r.oq = 64;
-    r.in_ = 1;
-    r.iq = 64;
-    r.bias_n = 1;
-    r.bias_q = 64;
-    r.mapped = 0;
+    wgrad_reduce_fill(rb.job[k], p, 4, 1.f, j.dw, 64 * 9, 9, 0, 1, 64, 1, 64, j.dbias, 1, 64);
   }
   const size_t lds_bytes = (size_t)(FW_X + FW_Y) * sizeof(float);
   SISR_ALLOW_LDS(wgrad3x3_c64_full_batch_kernel, lds_bytes);
@@ -1953,29 +1933,10 @@ static int wgrad3x3_c64_bf16_launch(const float* x, const int64_t* xview, const 
                                     int64_t si, int flip_taps, int out_perm_n, int out_perm_q, int in_perm_n,
                                     int in_perm_q, float* dbias, int bias_n, int bias_q, float* workspace,
                                     size_t workspace_bytes, int B, int H, int W, int cin, int cout, int storage, void* stream) {
-  if (!x || !dy || !dw || !xview || !dyview || !workspace || B <= 0 || H <= 0 || W <= 0) return SISR_ERR_ARG;
-  if (storage != 0 && storage != 1 && storage != 3) return SISR_ERR_UNSUPPORTED;
-  if ((cin & 63) || (cout & 63) || cin <= 0 || cout <= 0) return SISR_ERR_UNSUPPORTED;
-  if (workspace_bytes < sisr_wgrad3x3_c64_bf16_workspace_bytes(B, H, W, cin, cout)) return SISR_ERR_ARG;
-  if (!sisr_aligned16(x) || !sisr_aligned16(dy) || !sisr_aligned16(workspace) || !sisr_aligned16(dy_scale) ||
-      !sisr_aligned16(dy_shift))
-    return SISR_ERR_ALIGN;
-  WgradParams p = {};
-  p.x = x;
-  p.xv = view_from(xview);
-  p.dy = dy;
-  p.yv = view_from(dyview);
-  if ((p.xv.sB | p.xv.sH | p.xv.sW | p.xv.chi | p.xv.clo | p.yv.sB | p.yv.sH | p.yv.sW | p.yv.chi | p.yv.clo) & (storage ? 7 : 3))
-    return SISR_ERR_ALIGN;  // 16-B pieces: four fp32 or eight bf16 elements
-  p.dy_scale = dy_scale;
-  p.dy_shift = dy_shift;
-  p.B = B;
-  p.H = H;
-  p.W = W;
-  p.cin_chunks = cin / 64;
-  p.cout_chunks = cout / 64;
-  p.tiles_w = (W + WT_W - 1) / WT_W;
-  p.tiles_h = (H + WT_H - 1) / WT_H;
+  WgradParams p;  // storage (0, 1 or 3: the entries below): 16-byte pieces are four fp32 or eight bf16 elements
+  const int rc = wgrad_params(p, x, xview, dy, dyview, dy_scale, dy_shift, dw, workspace, workspace_bytes,
+                              sisr_wgrad3x3_c64_bf16_workspace_bytes(B, H, W, cin, cout), B, H, W, cin, cout, storage ? 7 : 3, WT_H);
+  if (rc) return rc;
   const int pairs = p.cin_chunks * p.cout_chunks;
   const int units = pairs * 4;
   p.S = wgrad_bf16_split(B, H, W, pairs);
@@ -2001,31 +1962,9 @@ static int wgrad3x3_c64_bf16_launch(const float* x, const int64_t* xview, const 
       hipLaunchKernelGGL(wgrad3x3_c64_bf16_xy16_kernel, dim3(p.S, pairs), dim3(256), lds_bytes, (hipStream_t)stream, p);
     }
   }
-  int rc = sisr_check_launch();
-  if (rc) return rc;
   ReduceParams r = {};
-  r.mapped = 0;
-  r.slabs = p.slabs;
-  r.bias_slabs = p.bias_slabs;
-  r.dw = dw;
-  r.db = dbias;
-  r.so = so;
-  r.si = si;
-  r.alpha = alpha;
-  r.S = p.S;
-  r.units = units;
-  r.cin_chunks = p.cin_chunks;
-  r.cout_chunks = p.cout_chunks;
-  r.flip = flip_taps;
-  r.on = out_perm_n;
-  r.oq = out_perm_q;
-  r.in_ = in_perm_n;
-  r.iq = in_perm_q;
-  r.bias_n = bias_n;
-  r.bias_q = bias_q;
-  const long total = (long)units * SLAB + (dbias ? cout : 0);
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(64, RG), 0, (hipStream_t)stream, r);
-  return sisr_check_launch();
+  return wgrad_reduce(r, p, units, alpha, dw, so, si, flip_taps, out_perm_n, out_perm_q, in_perm_n, in_perm_q, dbias, bias_n,
+                      bias_q, stream);
 }
 
 extern "C" int sisr_wgrad3x3_c64_bf16(const float* x, const int64_t* xview, const float* dy, const int64_t* dyview,
@@ -2072,28 +2011,10 @@ extern "C" int sisr_wgrad3x3_c64_x3(const float* x, const int64_t* xview, const 
                                     int64_t si, int flip_taps, int out_perm_n, int out_perm_q, int in_perm_n,
                                     int in_perm_q, float* dbias, int bias_n, int bias_q, float* workspace,
                                     size_t workspace_bytes, int B, int H, int W, int cin, int cout, void* stream) {
-  if (!x || !dy || !dw || !xview || !dyview || !workspace || B <= 0 || H <= 0 || W <= 0) return SISR_ERR_ARG;
-  if ((cin & 63) || (cout & 63) || cin <= 0 || cout <= 0) return SISR_ERR_UNSUPPORTED;
-  if (workspace_bytes < sisr_wgrad3x3_c64_x3_workspace_bytes(B, H, W, cin, cout)) return SISR_ERR_ARG;
-  if (!sisr_aligned16(x) || !sisr_aligned16(dy) || !sisr_aligned16(workspace) || !sisr_aligned16(dy_scale) ||
-      !sisr_aligned16(dy_shift))
-    return SISR_ERR_ALIGN;
-  WgradParams p = {};
-  p.x = x;
-  p.xv = view_from(xview);
-  p.dy = dy;
-  p.yv = view_from(dyview);
-  if ((p.xv.sB | p.xv.sH | p.xv.sW | p.xv.chi | p.xv.clo | p.yv.sB | p.yv.sH | p.yv.sW | p.yv.chi | p.yv.clo) & 3)
-    return SISR_ERR_ALIGN;
-  p.dy_scale = dy_scale;
-  p.dy_shift = dy_shift;
-  p.B = B;
-  p.H = H;
-  p.W = W;
-  p.cin_chunks = cin / 64;
-  p.cout_chunks = cout / 64;
-  p.tiles_w = (W + WT_W - 1) / WT_W;
-  p.tiles_h = (H + XW_TH - 1) / XW_TH;
+  WgradParams p;
+  const int rc = wgrad_params(p, x, xview, dy, dyview, dy_scale, dy_shift, dw, workspace, workspace_bytes,
+                              sisr_wgrad3x3_c64_x3_workspace_bytes(B, H, W, cin, cout), B, H, W, cin, cout, 3, XW_TH);
+  if (rc) return rc;
   const int pairs = p.cin_chunks * p.cout_chunks;
   const int units = pairs * 4;
   p.S = wgrad_x3_split(B, H, W, pairs);
@@ -2102,29 +2023,7 @@ extern "C" int sisr_wgrad3x3_c64_x3(const float* x, const int64_t* xview, const 
   const size_t lds_bytes = 3 * (size_t)(XW_X + XW_Y);
   SISR_ALLOW_LDS(wgrad3x3_c64_x3_kernel, lds_bytes);
   hipLaunchKernelGGL(wgrad3x3_c64_x3_kernel, dim3(p.S, pairs), dim3(256), lds_bytes, (hipStream_t)stream, p);
-  int rc = sisr_check_launch();
-  if (rc) return rc;
   ReduceParams r = {};
-  r.mapped = 0;
-  r.slabs = p.slabs;
-  r.bias_slabs = p.bias_slabs;
-  r.dw = dw;
-  r.db = dbias;
-  r.so = so;
-  r.si = si;
-  r.alpha = alpha;
-  r.S = p.S;
-  r.units = units;
-  r.cin_chunks = p.cin_chunks;
-  r.cout_chunks = p.cout_chunks;
-  r.flip = flip_taps;
-  r.on = out_perm_n;
-  r.oq = out_perm_q;
-  r.in_ = in_perm_n;
-  r.iq = in_perm_q;
-  r.bias_n = bias_n;
-  r.bias_q = bias_q;
-  const long total = (long)units * SLAB + (dbias ? cout : 0);
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(64, RG), 0, (hipStream_t)stream, r);
-  return sisr_check_launch();
+  return wgrad_reduce(r, p, units, alpha, dw, so, si, flip_taps, out_perm_n, out_perm_q, in_perm_n, in_perm_q, dbias, bias_n,
+                      bias_q, stream);
 }

@@ -129,6 +129,7 @@ def test_persistent_conv_is_bit_identical_to_per_tile_conv(B, H, W):
     pk = ops.pack_weight(w, "fwd")
     cases = [dict(bias=b, relu=True, gap=True), dict(res=res, alpha=0.3), dict(mask=mask), dict(mask=mask, res=res),
              dict(mask=mask, in_scale=sc, in_shift=sh), dict(in_scale=sc, res=res), dict(in_scale=sc),
+             dict(mask=mask, in_scale=sc, in_shift=sh, res=res),
              dict(bias=b, relu=True, in_scale=sc, gate_add=skip, gate_out=True),
              dict(in_scale=sc, gate_add=skip, gate_out=True, res=res), dict(gap=True, dot=dot),
              dict(gap=True, dot=dot, res=res)]

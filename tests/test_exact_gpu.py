@@ -97,6 +97,8 @@ CASES = ["bias", "bias_relu_gap", "res_alpha", "mask", "mask_affine", "affine_re
          "gate_relu", "gate_res", "dot", "dot_res", "leaky", "leaky_mask"]
 FP32_ONLY = {"leaky", "leaky_mask"}  # LeakyReLU codes exist on the fp32 kernels only (SFTMD)
 BF16_REFUSED = {"shift_only"}  # in_shift without in_scale: the fp32 entry serves it from the general kernel only
+# forms with kernels of their own in the bf16 / bf16x3 families only (the fp32 entry serves them from the general kernel)
+BF16_EXTRA = ["affine", "mask_affine_res"]
 
 
 class ConvData:
@@ -124,9 +126,9 @@ def conv_case(name, D):
     wt = w.flip(2, 3).transpose(0, 1)  # the input-gradient packing computes the transposed conv
     b, res, m, dev = dd(D.b).view(1, 64, 1, 1), dd(D.res), dd(D.m), D.dev
     pk, kw, u, wk, gap, gout, extras = "f", {}, x, w, None, None, []
-    if name in ("mask", "mask_affine", "mask_res", "leaky_mask"):
+    if name in ("mask", "mask_affine", "mask_res", "leaky_mask", "mask_affine_res"):
         pk, wk = "d", wt
-    if name in ("mask_affine", "affine_res"):
+    if name in ("mask_affine", "affine_res", "affine", "mask_affine_res"):
         u = x * v(D.sc) + v(D.sh)
         kw.update(in_scale=dev["sc"], in_shift=dev["sh"])
     if name == "shift_only":
@@ -154,13 +156,13 @@ def conv_case(name, D):
     if name == "out_scale":
         kw.update(out_scale=dev["os"], alpha=X.ALPHA)
         y = y * (X.ALPHA * v(D.os))
-    if name in ("mask", "mask_affine", "mask_res"):
+    if name in ("mask", "mask_affine", "mask_res", "mask_affine_res"):
         kw["mask"] = dev["m"]
         y = y * X.relu_mask(m)  # PyTorch's ReLU': 0 where the map is <= 0
     if name == "leaky_mask":
         kw.update(mask=dev["m"], relu=ops.LEAKY_MASK)
         y = X.fp32_round(y * X.leaky_mask(m))  # PyTorch's LeakyReLU': slope where the map is <= 0, one fp32 rounding
-    if name in ("res_alpha", "affine_res", "mask_res", "gate_res", "dot_res"):
+    if name in ("res_alpha", "affine_res", "mask_res", "gate_res", "dot_res", "mask_affine_res"):
         kw["res"] = dev["res"]
         y = y + res
         extras.append(D.res)
@@ -514,7 +516,7 @@ def test_bf16_conv_forms(mode, select, B, H, W):
         packs = ops.pack_pair(D.dev["w"])
         assert packs[0].dtype == torch.bfloat16
         fails = []
-        for n in CASES:
+        for n in CASES + (BF16_EXTRA if (B, H, W) == (1, 13, 9) else []):
             if n in FP32_ONLY or n in BF16_REFUSED:
                 pk, kw, *_ = conv_case(n, D)
                 with pytest.raises(RuntimeError):
