@@ -64,6 +64,16 @@ def _join_side(device):
         torch.cuda.current_stream(device).wait_stream(s)
 
 
+def _join_side_now(device):
+    """Mid-pass join, for a gradient that autograd is about to add to one the side stream may still be writing: the stream
+    that drives the pass waits for what this pass has issued there (nothing, and no wait, when it has issued nothing; the
+    end-of-pass join stays queued)."""
+    if device.index in _join_pending:
+        s = _side_streams.get(device.index)
+        if s is not None:
+            torch.cuda.current_stream(device).wait_stream(s)
+
+
 def _on_side(device, after_event, fn, tensors):
     """Run fn() on the side stream once `after_event` (recorded on the main stream) has passed; keep the
     caching allocator from recycling `tensors` before the side stream is done with them."""
@@ -92,19 +102,62 @@ def _empty_cl(B, C, H, W, device):
 # nothing to copy.  Keyed by the parameter's data pointer; empty in single-process runs.
 GRAD_SINK = {}
 
+# A backward pass (one autograd graph task) can produce several gradients of one tensor: a weight applied twice.  A leaf's
+# .grad stays None until ALL of its contributions have arrived, so `w.grad is None` alone does not say that nobody has been
+# promised w's sink, nor that no side-stream launch is still writing a gradient of w.  Two sets of data pointers tell the
+# second contribution apart; both are emptied whenever the graph task changes (a pass that died mid-way leaves nothing
+# behind).  Host-side only: an ordinary step gains no launch and no synchronisation.
+# Limits: the pass is told apart by torch._C._current_graph_task_id(), a private torch call (torch.utils.checkpoint uses
+# it too); a NESTED graph task (a reentrant backward, activation checkpointing) empties the sets, so a weight applied once
+# before and once after such a nested pass would be handed its sink twice.  Nothing in this package nests passes.
+_PASS_ID = -1
+_PASS_BUFS = set()    # tensors _grad_buf has handed a gradient buffer out for in this pass
+_PASS_SIDE = set()    # weights _side_ok has been asked about in this pass
+_PASS_SHARED = set()  # tensors with a second gradient in this pass: never queued by deferred_wgrads()
 
-def _grad_buf(w):
-    sink = GRAD_SINK.get(w.data_ptr())
-    # only when this backward creates the gradient: with a pre-existing .grad (zero_grad(set_to_none=False),
-    # micro-batch accumulation) autograd adds the result to it, and .grad may itself be the bucket view
+
+def _pass_id():
+    """The running autograd graph task (-1 outside a backward pass: a backward called by hand accumulates nothing, and
+    nothing is recorded); a node with many gradients asks once and hands the answer to _grad_buf."""
+    global _PASS_ID
+    gid = torch._C._current_graph_task_id()
+    if gid != _PASS_ID:
+        _PASS_ID = gid
+        _PASS_BUFS.clear()
+        _PASS_SIDE.clear()
+        _PASS_SHARED.clear()
+    return gid
+
+
+def _grad_buf(w, gid=None):
+    """The buffer a weight-gradient kernel writes the gradient of `w` into.  Contract (tests/test_autograd_contract_gpu.py):
+      * first, or only, gradient of `w` in this backward pass, no .grad yet, a sink registered: a fresh alias of the sink
+        (the optimiser's arena slice / the reducer's bucket) -- autograd adopts a gradient it holds the only reference to,
+        so the kernel's output IS .grad and nothing is copied;
+      * a pre-existing .grad (zero_grad(set_to_none=False), micro-batch accumulation): a private buffer -- autograd adds it
+        to .grad, which may itself be the sink view;
+      * a further gradient of the same `w` in one pass (a weight applied twice): a private buffer as well -- the sink holds
+        the first contribution until autograd has added the two -- handed out only after the side stream has been joined
+        and every deferred queue flushed, either of which may still hold the launch of the first one; the launch that fills
+        this buffer is never queued itself (wgrad_c64, _ReflConv).
+    gid: _pass_id(), from a node that asked already."""
+    key = w.data_ptr()
+    if (gid if gid is not None else _pass_id()) >= 0:
+        if key in _PASS_BUFS:
+            _PASS_SHARED.add(key)
+            _join_side_now(w.device)
+            _flush_deferred()
+            return torch.empty_like(w)
+        _PASS_BUFS.add(key)
+    sink = GRAD_SINK.get(key)
     if sink is not None and sink.shape == w.shape and w.grad is None:
-        return sink.view(sink.shape)  # a fresh alias: autograd adopts a gradient it holds the only reference to
+        return sink.detach()  # a fresh alias: autograd adopts a gradient it holds the only reference to
     return torch.empty_like(w)
 
 
-def _grad_buf_or(p, n, device):
+def _grad_buf_or(p, n, device, gid=None):
     """_grad_buf for an optional small parameter (bias): a plain [n] buffer when there is none."""
-    return _grad_buf(p) if p is not None else torch.empty(n, device=device)
+    return _grad_buf(p, gid) if p is not None else torch.empty(n, device=device)
 
 
 def _side_ok(*weights, pixels=None):
@@ -115,7 +168,19 @@ def _side_ok(*weights, pixels=None):
     backward pass) iff autograd will merely ADOPT them: with an existing .grad AccumulateGrad would run
     `p.grad += dw` on the main stream before the side-stream kernel has written dw.  The same holds for a weight that is not a
     leaf (one computed from parameters, e.g. SRMD's transposed-conv tail): its gradient is consumed by further backward nodes
-    on the main stream at once."""
+    on the main stream at once.  And the same holds for a weight applied twice (named twice here, or one an earlier node of
+    this pass has produced a gradient of): autograd adds the two contributions on the main stream as soon as the second node
+    returns, so the second goes out on the main stream, behind whatever the side stream still holds of the first.
+    A node asks BEFORE it requests its buffers from _grad_buf (which records them as produced): asked afterwards, every
+    weight would look like a second contribution and the node would lose the side stream on every ordinary pass
+    (tests/test_autograd_contract_cpu.py pins the order on a stand-in node)."""
+    if _pass_id() >= 0:
+        keys = [w.data_ptr() for w in weights]
+        shared = len(set(keys)) < len(keys) or not (_PASS_SIDE.isdisjoint(keys) and _PASS_BUFS.isdisjoint(keys))
+        _PASS_SIDE.update(keys)
+        if shared:
+            _join_side_now(weights[0].device)
+            return False
     if not (WGRAD_SIDE_STREAM and torch.is_grad_enabled() is False and all(w.is_leaf and w.grad is None for w in weights)):
         return False
     if _DEFERRED is not None and pixels is not None and PRECISION == "fp32" and pixels <= BATCH_WGRAD_MAX_PIXELS:
@@ -436,9 +501,15 @@ _DEFERRED_STREAM = None  # the stream the block was opened on: launches issued f
 class deferred_wgrads:
     """While open (around ONE backward pass), plain 64 -> 64 weight gradients of small launches are queued and go out eight at
     a time (WgradQueue), the rest when the block closes.  Only sound when nothing reads a parameter gradient before the block
-    closes and every gradient is merely ADOPTED by autograd (grads None on entry): the handlers open it when no reducer hook
-    can fire (single process, or hipGraph capture / replay where the buckets are reduced at the join).  The queued launches
-    write into the tensors autograd has adopted as .grad (weight AND bias of the conv: both are assumed trainable together).
+    closes: the handlers open it when no reducer hook can fire (single process, or hipGraph capture / replay where the
+    buckets are reduced at the join).  A launch is queued only when autograd will merely ADOPT its result, and then writes,
+    late, into the tensors autograd has adopted as .grad.  Two queues, two rules.  wgrad_c64 (the 64 -> 64 convs): the WEIGHT
+    is a trainable leaf whose .grad is None; the conv's bias gradient rides in the same launch -- a frozen bias's lands in a
+    buffer nobody adopts (its storage is kept until the flush), a frozen weight's launch, made for a trainable bias, is not
+    queued at all.  _ReflConv (SPARNet's convs): weight AND bias are trainable leaves without a .grad, else the launch goes
+    out directly.  With a .grad that exists already (zero_grad(set_to_none=False), micro-batch accumulation) nothing is
+    queued and autograd adds the result as usual.
+    (tests/test_autograd_contract_gpu.py pins all of this: frozen subsets, kept and shared gradients, inside the block and out.)
 
     Two guards keep a queued gradient from ever being read unwritten:
       * the block flushes on EVERY exit, exceptional ones included: a queue entry keeps the storages of its output buffers
@@ -446,7 +517,9 @@ class deferred_wgrads:
         before autograd adopted them, and every .grad that was adopted holds its gradient when the block has closed;
       * a weight is queued at most once per block: a second weight gradient of the same parameter (a conv weight used twice
         in one backward) first flushes every queue -- autograd sums the two results as soon as the second arrives, on this
-        stream -- and is launched directly."""
+        stream -- and is launched directly, into a buffer of its own.  _grad_buf does both when it is asked for a second
+        buffer of one tensor in a pass, whatever the two launches look like (one of them may be ineligible for the queue:
+        another alpha, a shuffle); the _DEFERRED_OWNERS check below covers weight gradients that bypass _grad_buf."""
 
     def __init__(self, enabled=True):
         self.enabled = enabled and BATCH_WGRAD
@@ -485,7 +558,7 @@ def wgrad_c64(x, xview, dy, dyview, dw, db, B, H, W, cin, cout, alpha=1.0, dy_sc
     """active_units (fp32 kernel): bit mask of the 32 x 32-channel blocks of the gradient to compute (0 = all).
     owner: the weight Parameter -- with it, inside a deferred_wgrads() block, an eligible launch is queued instead."""
     if (_DEFERRED is not None and hip.stream() == _DEFERRED_STREAM and owner is not None and owner.requires_grad and
-            owner.grad is None and cin == 64 and cout == 64 and shuffle == 1 and
+            owner.grad is None and owner.data_ptr() not in _PASS_SHARED and cin == 64 and cout == 64 and shuffle == 1 and
             alpha == 1.0 and not active_units and WgradQueue.wanted(B, H, W) and xview is hip.view_plain(H, W, 64) and
             dyview is hip.view_plain(H, W, 64)):
         if id(owner) in _DEFERRED_OWNERS:
@@ -840,8 +913,15 @@ class _MetaGateMany(Function):
         ws = torch.empty(L * B * (Hd + C), device=dev)
         es = tab.element_size() * L
         base = tab.data_ptr()
-        sinks = [GRAD_SINK.get(t.data_ptr()) for t in ctx.params]
-        if all(sk is not None and sk.shape == t.shape and t.grad is None for sk, t in zip(sinks, ctx.params)):
+        keys = [t.data_ptr() for t in ctx.params]
+        sinks = [GRAD_SINK.get(k) for k in keys]
+        # the sinks take the FIRST gradient of a layer in a backward pass only (_grad_buf's contract): layers applied twice
+        # (listed twice, or batched by two nodes of one pass) get private buffers, which autograd adds
+        first = len(set(keys)) == len(keys)
+        if _pass_id() >= 0:
+            first = first and _PASS_BUFS.isdisjoint(keys)
+            _PASS_BUFS.update(keys)
+        if first and all(sk is not None and sk.shape == t.shape and t.grad is None for sk, t in zip(sinks, ctx.params)):
             # every gradient goes straight into the optimiser's arena (no gather before the update, no per-layer copy)
             gt = _meta_grad_table(sinks, dev)
             ges = gt.element_size() * L
@@ -850,7 +930,7 @@ class _MetaGateMany(Function):
                                                                 L, base, base + 2 * es, int(relu), gb, gb + ges, gb + 2 * ges,
                                                                 gb + 3 * ges, hip.ptr(ws), hip.stream()),
                       "sisr_meta_gate_many_bwd_scatter")
-            return (None, None, *[sk.view(sk.shape) for sk in sinks])  # fresh aliases: autograd adopts what it alone holds
+            return (None, None, *[sk.detach() for sk in sinks])  # fresh aliases: autograd adopts what it alone holds
         dv1 = torch.empty((L,) + shapes[0], device=dev)
         dc1 = torch.empty((L,) + shapes[1], device=dev)
         dv2 = torch.empty((L,) + shapes[2], device=dev)
@@ -1083,10 +1163,10 @@ class _ResBlock(Function):
                               "sisr_sum_partials")
                     scale = g
             # conv2 backward: dt2 = dy*scale + shift is rebuilt on load, never stored
-            dw2, db2 = _grad_buf(w2), torch.empty(C, device=dev)
-            dw1, db1 = _grad_buf(w1), torch.empty(C, device=dev)
             # plain first-order backward only; not under hipGraph capture (record_stream + private pools)
             side = _side_ok(w1, w2, pixels=B * H * W)
+            dw2, db2 = _grad_buf(w2, _PASS_ID), torch.empty(C, device=dev)
+            dw1, db1 = _grad_buf(w1, _PASS_ID), torch.empty(C, device=dev)
 
             def wgrad2():
                 wgrad_c64(t1, v, dy, v, dw2, db2, B, H, W, C, C, alpha=rs, dy_scale=scale, dy_shift=shift, owner=w2)
@@ -1298,7 +1378,8 @@ class _GatedGroup(Function):
             bheads = has_ca and queue is not None and GATE_HEADS and B * H * W <= GATE_HEADS_MAX_PIXELS
             gate_jobs = []
             # tail conv: weight gradient from (u_n, dout); dU_n = convT(dout), with sum(dU_n * t2_n) on the side
-            dwt, dbt = _grad_buf(wt), _grad_buf_or(ctx.bt, 64, dev)
+            gid = _PASS_ID  # _side_ok has just asked: one look at the graph task for the group's ~8n gradient buffers
+            dwt, dbt = _grad_buf(wt, gid), _grad_buf_or(ctx.bt, 64, dev, gid)
             if queue is not None:
                 queue.add(un, dout, dwt, dbt)
             else:
@@ -1312,7 +1393,8 @@ class _GatedGroup(Function):
                     return dict(shift=None, dmv=_vec(B, 64, dev), dcaw1=None, dcab1=None, dcaw2=None, dcab2=None, dzw=None,
                                 dgp=torch.empty((B, parts, 64), device=dev, dtype=torch.float32))
                 return dict(shift=_vec(B, 64, dev), dmv=_vec(B, 64, dev) if has_m else None,
-                            dcaw1=_grad_buf(caw1), dcab1=_grad_buf(cab1), dcaw2=_grad_buf(caw2), dcab2=_grad_buf(cab2),
+                            dcaw1=_grad_buf(caw1, gid), dcab1=_grad_buf(cab1, gid), dcaw2=_grad_buf(caw2, gid),
+                            dcab2=_grad_buf(cab2, gid),
                             dgp=torch.empty((B, parts, 64), device=dev, dtype=torch.float32),
                             dzw=torch.empty((B, 80), device=dev) if queue is not None else None)
 
@@ -1322,7 +1404,7 @@ class _GatedGroup(Function):
                 """Weight gradient of block k's second conv, from (t1, the gated gradient dy * g + shift rebuilt while staging)."""
                 tens = blocks[k][0]
                 w2, t1, g = tens[2], tens[3], tens[10] if has_ca else tens[6]
-                dw2, db2 = _grad_buf(w2), _grad_buf_or(ctx.small[k][1], 64, dev)
+                dw2, db2 = _grad_buf(w2, gid), _grad_buf_or(ctx.small[k][1], 64, dev, gid)
                 shift = go["shift"]
                 if queue is not None:
                     queue.add(t1, dy, dw2, db2, dy_scale=g, dy_shift=shift)
@@ -1336,7 +1418,7 @@ class _GatedGroup(Function):
                 tens, has_m = blocks[k]
                 xk, w1 = tens[0], tens[1]
                 caw1c, s, hid = (tens[5], tens[7], tens[8]) if has_ca else (None, None, None)
-                dw1, db1 = _grad_buf(w1), _grad_buf_or(ctx.small[k][0], 64, dev)
+                dw1, db1 = _grad_buf(w1, gid), _grad_buf_or(ctx.small[k][0], 64, dev, gid)
                 if queue is not None:
                     if has_ca:
                         gate_jobs.append((go["dzw"], hid, s, go["dcaw1"], go["dcab1"], go["dcaw2"], go["dcab2"], caw1c.shape[0]))
@@ -1949,7 +2031,7 @@ class _ReflConv(Function):
                 tiles = B * ((Hv + 7) // 8) * ((Wv + 31) // 32) * n_in * n_out
                 owners = (weight, ctx.bias) if has_b else (weight,)
                 if (REFL_BATCH and _DEFERRED is not None and hip.stream() == _DEFERRED_STREAM and tiles < 128 and
-                        all(o.requires_grad and o.grad is None for o in owners)):
+                        all(o.requires_grad and o.grad is None and o.data_ptr() not in _PASS_SHARED for o in owners)):
                     if id(weight) in _DEFERRED_OWNERS:
                         _flush_deferred()  # second gradient of one weight in this pass: the first must be written first
                     else:
