@@ -746,6 +746,63 @@ int sisr_maxpool2_relu_bwd(const float* y, const float* dout, float* dy, int B, 
  * more than 2^31 - 1 blocks (-4). */
 int sisr_jpeg_roundtrip(const unsigned char* in, void* out, int C, int H, int W, int quality, int to_float, void* stream);
 
+/* ---- tile-level online degradation (csrc/degrade_tiles.hip; `[data] degrade_tiles = true`) ----------------------------
+ * A training batch's LR and HR tiles from device-resident HR images with a constant number of launches, no whole-image
+ * intermediate, no workspace, no atomics and no state (capturable; a repeat call is bit-identical).  The LR tile equals, bit
+ * for bit, the pixels that sisr_blur_quant (+ sisr_noise_quant) on the WHOLE image, the centre crop and both passes of
+ * sisr_pil_resample give at the tile's position: same tap order in the blur, reflection against the image, the whole-image
+ * coefficient tables indexed at the tile's absolute LR rows / columns; the HR window a strip of LR rows needs is read off the
+ * tables' bounds.  One record per sample: */
+typedef struct sisr_degrade_tile {
+  const float* image;                        /* [C][H][W] fp32 on the device */
+  const int *bounds_h, *coef_h;              /* device tables of (rw -> rw / scale): bounds [out][2], coef [out][ksize_h] */
+  const int *bounds_v, *coef_v;              /* ... and of (rh -> rh / scale) */
+  int H, W;                                  /* image size */
+  int t0, l0, rh, rw;                        /* centre-crop box (image_manipulation.downsample): rh, rw multiples of scale */
+  int ty, tx;                                /* the tile's origin in the un-augmented LR image (rh / scale) x (rw / scale) */
+  int ksize_h, ksize_v;                      /* row length of the coefficient tables: 4 scale + 1 */
+  int flips;                                 /* applied on the store: 1 hflip | 2 vflip | 4 transpose; out(i, j) = tile(ry, rx) with
+                                                (a, b) = transpose ? (j, i) : (i, j), ry = vflip ? c-1-a : a, rx = hflip ? c-1-b : b,
+                                                which is sisr_crop_augment's index map restricted to the tile */
+  int noise;                                 /* 0: byte(255 blur), sisr_blur_quant's; 1: sisr_noise_quant's arithmetic with ... */
+  float sigma;                               /* ... this noise level (0 allowed) and the field of `seed` below */
+  unsigned seed;
+} sisr_degrade_tile;
+size_t sisr_degrade_tile_bytes(void);
+/* tiles_host: the B records in host memory, checked here before anything is launched; tiles_dev: their device copy, which the
+ * kernel reads; kernels [B][l][l] fp32 on the device (l <= 21; odd and even l take sisr_blur_quant's padding rule); out
+ * [B][C][c][c] uint8 (to_float = 0) or fp32 = byte / 255.  One launch: a workgroup per (strip of 8 LR rows, channel, sample)
+ * keeps the strip's blurred, quantised HR window and the horizontal pass's rows in LDS.  -1: null pointers (records' included:
+ * image, or tables not supplied / of another scale's ksize), non-positive sizes, a crop box outside the image or not a
+ * multiple of the scale, a tile that leaves the LR image (ty + c > rh / scale, ...), flips outside 0..7, sigma < 0, to_float
+ * other than 0 or 1;  -4: scale outside 2..4, l > 21 or l / 2 >= H or W, B or C > 65535, a tile whose window needs more than
+ * 64 KB of LDS (c = 64 at x 4 needs 45 KB). */
+int sisr_degrade_tiles(const void* tiles_host, const void* tiles_dev, const float* kernels, void* out, int B, int C, int c,
+                       int l, int scale, int to_float, void* stream);
+/* sisr_jpeg_roundtrip on every tile of a batch, one launch: in [B][C][c][c] uint8 in source orientation, the block grid at
+ * the tile's origin (NOT the image's: a crop-level round trip, not a crop of the whole image's), edge replication to whole
+ * blocks, quality[b] (device, int32) for sample b, the scaled Annex-K tables built in the kernel; out [B][C][c][c] uint8 or
+ * fp32 = byte / 255 through flips[b] (device, the bits of sisr_degrade_tile.flips; NULL: none).  The qualities are device
+ * values, which the host cannot check: the kernel clamps them to 1..100 and degrade.degrade_tiles refuses others before the
+ * upload.  -1: null in / out / quality, in == out, B < 1, C other than 1 or 3, c < 1, to_float other than 0 or 1;  -4: B >
+ * 65535, c > 32768. */
+int sisr_jpeg_roundtrip_batch(const unsigned char* in, void* out, const int* quality, const int* flips, int B, int C, int c,
+                              int to_float, void* stream);
+/* The N(0,1) field of the tile-level noise on its own -- a pure function of (seed, channel, row, column), shared with
+ * sisr_degrade_tiles as one device function (csrc/noise_field.h):
+ *   words = Philox4x32-10(counter = (column >> 2, row, channel, 0), key = (seed, 0));
+ *   u_i = (float(words[i] >> 8) + 0.5f) * 2^-24 in fp32 (exact below 2^23, round-to-even above: u in (0, 1]);
+ *   columns 4q, 4q + 1 = r cos(a), r sin(a) with r = sqrtf(-2 logf(u_0)), a = 2 pi u_1; columns 4q + 2, 4q + 3 the same of
+ *   (u_2, u_3); precise logf / cosf / sinf.  THIS MAP IS KEPT: seeded runs depend on it.
+ * field [C][H][W] fp32 and / or words [C][H][ceil(W / 4)][4] uint32 (either may be null, not both). */
+int sisr_normal_field(unsigned seed, float* field, unsigned* words, int C, int H, int W, void* stream);
+/* sisr_crop_augment reading a centre-cropped image in place (no copy of the crop): params[b] = {rh, rw, top, left, hflip,
+ * vflip, transpose, H, W, t0, l0, 0}: src[b] is the full [C][H][W] image, (t0, l0, rh, rw) its crop box, the rest as
+ * sisr_crop_augment's record on the cropped image.  params_host is checked before the launch (box inside the image, tile
+ * inside the augmented crop), params_dev is its device copy. */
+int sisr_crop_augment_strided(const float* const* src, const int* params_host, const int* params_dev, float* dst, int B, int C,
+                              int crop, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

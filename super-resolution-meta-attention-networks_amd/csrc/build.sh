@@ -8,21 +8,24 @@ set -euo pipefail
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 SRCS=(conv3x3_mfma.hip wgrad3x3_mfma.hip conv3x3_small.hip attention.hip misc.hip han.hip san.hip degrade.hip sft.hip nonlocal.hip sparnet.hip
-      metrics.hip basic.hip interp.hip ensemble.hip perceptual.hip ssim_loss.hip jpeg.hip update.hip freq_loss.hip)
+      metrics.hip basic.hip interp.hip ensemble.hip perceptual.hip ssim_loss.hip jpeg.hip update.hip freq_loss.hip degrade_tiles.hip)
+HDRS=(sisr_common.h ca_gate.h conv_rgb_out.h degrade_common.h jpeg_block.h noise_field.h)
 
 build() {  # $1 = output, $2 = object dir, $3... = extra flags / sources
   local out=$1 odir=$2; shift 2
   local flags=() srcs=()
   for a in "$@"; do case "$a" in -D*) flags+=("$a");; *) srcs+=("$a");; esac; done
   local newest
-  newest=$(ls -t "${srcs[@]}" sisr_common.h ca_gate.h conv_rgb_out.h build.sh | head -1)
+  newest=$(ls -t "${srcs[@]}" "${HDRS[@]}" build.sh | head -1)
   if [ -f "$out" ] && [ "$out" -nt "$newest" ]; then return 0; fi
   mkdir -p "$odir"
   local objs=() pids=()
   for s in "${srcs[@]}"; do
     local o=$odir/${s%.hip}.o
     objs+=("$o")
-    if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ sisr_common.h -nt "$o" ] || [ ca_gate.h -nt "$o" ] || [ conv_rgb_out.h -nt "$o" ] || [ build.sh -nt "$o" ]; then
+    local stale=0
+    for d in "$s" "${HDRS[@]}" build.sh; do if [ ! -f "$o" ] || [ "$d" -nt "$o" ]; then stale=1; fi; done
+    if [ "$stale" = 1 ]; then
       "$HIPCC" -O3 -std=c++17 --offload-arch=gfx950 -fPIC "${flags[@]}" -c "$s" -o "$o" &
       pids+=($!)
     fi

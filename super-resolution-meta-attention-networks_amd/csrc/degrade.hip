@@ -9,19 +9,9 @@
 // precompute_coeffs / normalize_coeffs_8bpc do, so the LR image is bit-identical to PIL's given the same uint8 input.
 // The blur is an fp32 sum of l*l products in row-major tap order; the reference's MKLDNN convolution sums in another
 // order, so a pixel whose 255 x value lies within ~1e-5 of an integer can truncate to the neighbouring byte.
-#include "sisr_common.h"
+#include "degrade_common.h"
 
 #define BT 32                 // output tile edge
-#define BL_MAX 21             // largest blur kernel edge (reference default and maximum used: 21)
-
-// nn.ReflectionPad2d: -1 -> 1, n -> n-2.  Clamped into the image: the staged tile of an edge block reaches past the
-// reflection of rows / columns no output of the block reads (more than l - 1 - l / 2 beyond the image), where one
-// reflection leaves an index below 0; every index an output does read lies within one reflection and is unchanged.
-__device__ __forceinline__ int reflect_index(int i, int n) {
-  if (i < 0) i = -i;
-  if (i >= n) i = 2 * n - 2 - i;
-  return min(max(i, 0), n - 1);
-}
 
 // x: [C][H][W] fp32, k: [l][l] fp32 (cross-correlation, as F.conv2d), y: [C][H][W] uint8 = (uint8)(conv * 255)
 __global__ __launch_bounds__(256) void blur_quant_kernel(const float* __restrict__ x, const float* __restrict__ k,
@@ -48,7 +38,7 @@ __global__ __launch_bounds__(256) void blur_quant_kernel(const float* __restrict
       for (int j = 0; j < l; ++j) acc = __builtin_fmaf(tile[(r + i) * TS + q + j], kk[i * l + j], acc);
     const long at = ((long)c * H + h0 + r) * W + w0 + q;
     if (yf) yf[at] = acc;
-    if (y) y[at] = (unsigned char)(int)(acc * 255.0f);
+    if (y) y[at] = dg_quant(acc);
   }
 }
 
@@ -58,9 +48,7 @@ __global__ __launch_bounds__(256) void blur_quant_kernel(const float* __restrict
 __global__ __launch_bounds__(256) void noise_quant_kernel(const float* __restrict__ blur, const float* __restrict__ noise,
                                                           float sigma, unsigned char* __restrict__ y, long n) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    float v = __fadd_rn(__fmul_rn(noise[i], sigma), blur[i]);
-    v = fminf(fmaxf(v, 0.f), 1.f);
-    y[i] = (unsigned char)(int)(v * 255.0f);
+    y[i] = dg_noise_quant(blur[i], noise[i], sigma);
   }
 }
 
@@ -86,8 +74,7 @@ __global__ __launch_bounds__(256) void pil_resample_kernel(const unsigned char* 
     } else {
       for (int k = 0; k < n; ++k) ss += (int)src[(long)yo * Win + lo + k] * kp[k];
     }
-    int v = ss >> 22;
-    v = v < 0 ? 0 : (v > 255 ? 255 : v);
+    const int v = dg_clip8(ss);
     if (TO_FLOAT) static_cast<float*>(outp)[i] = (float)v / 255.0f;  // ToTensor: .float().div(255)
     else static_cast<unsigned char*>(outp)[i] = (unsigned char)v;
   }

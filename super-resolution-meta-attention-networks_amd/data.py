@@ -80,6 +80,19 @@ def random_matched_crop(lr, hr, crop_size, scale):
     return c_lr, c_hr
 
 
+def tile_source_box(h, w, crop, top, left, hflip, vflip, transpose):
+    """Where a tile of DeviceTileSampler.draw_for comes from: (ty, tx), the origin in the UN-augmented (h, w) image of the
+    `crop` x `crop` square that sisr_crop_augment's index map reads for the draws (top, left, hflip, vflip, transpose).  Output
+    (i, j) reads source (ty + ry, tx + rx) with (a, b) = (j, i) if transpose else (i, j), ry = crop - 1 - a if vflip else a,
+    rx = crop - 1 - b if hflip else b."""
+    y0, x0 = (left, top) if transpose else (top, left)  # the transpose swaps what top / left count along
+    ty = h - crop - y0 if vflip else y0
+    tx = w - crop - x0 if hflip else x0
+    if not (0 <= ty <= h - crop and 0 <= tx <= w - crop):
+        raise ValueError(f"a {crop}-pixel tile at ({top}, {left}) leaves the {h} x {w} image")
+    return ty, tx
+
+
 class DeviceTileSampler:
     """Training tiles cut on the GPU from a device-resident copy of the dataset.
 
@@ -153,6 +166,25 @@ class DeviceTileSampler:
         return out[0], out[1]
 
 
+    def gather_hr_strided(self, images, boxes, draws):
+        """The HR side of sample_pairs for centre-cropped images that are NOT copied out: images[b] the full (C, H, W) HR
+        image, boxes[b] = (t0, l0, rh, rw) its crop box, draws[b] = (top, left, hflip, vflip, transpose) drawn on the LR
+        size.  One gather (sisr_crop_augment_strided), one small upload."""
+        import ctypes
+        hip, s = self.hip, self.scale
+        B, c = len(images), self.crop * s
+        prm = np.zeros((B, 12), np.int32)
+        for b, (im, (t0, l0, rh, rw), (top, left, hf, vf, rot)) in enumerate(zip(images, boxes, draws)):
+            prm[b] = (rh, rw, top * s, left * s, int(hf), int(vf), int(rot), im.shape[1], im.shape[2], t0, l0, 0)
+        host = np.concatenate([np.array([im.data_ptr() for im in images], np.int64).view(np.int32), prm.reshape(-1)])
+        dev = torch.from_numpy(host).to(self.device)
+        dst = torch.empty((B, self.channels, c, c), device=self.device, dtype=torch.float32)
+        hip.check(hip.lib().sisr_crop_augment_strided(dev.data_ptr(), prm.ctypes.data_as(ctypes.c_void_p), dev.data_ptr() + 8 * B,
+                                                      hip.ptr(dst), B, self.channels, c, hip.stream()),
+                  "sisr_crop_augment_strided")
+        return dst
+
+
 class DeviceTileLoader:
     """Drop-in for the training DataLoader (`[data] device_tiles = true`): same batch dicts, same order, same
     random streams as `DataLoader(shuffle=True, num_workers=0)` over the same SuperResImages datasets -- but the
@@ -163,8 +195,11 @@ class DeviceTileLoader:
     a `torch.randperm(n)` from a generator with that seed; per sample the five `random` draws of the sampler.
     """
 
-    def __init__(self, datasets, batch_size, device, drop_last=False):
-        self.batch_size, self.drop_last = int(batch_size), bool(drop_last)
+    def __init__(self, datasets, batch_size, device, drop_last=False, degrade_tiles=False):
+        """degrade_tiles (`[data] degrade_tiles = true`, with online_degradations only): degrade the TILE, not the image --
+        every batch is one sisr_degrade_tiles launch (+ one JPEG launch) + one HR gather over the resident HR images, whatever
+        the batch size; same draws, same metadata, and without JPEG the same pixels as the whole-image mode."""
+        self.batch_size, self.drop_last, self.degrade_tiles = int(batch_size), bool(drop_last), bool(degrade_tiles)
         crops = {d.patch_crop for d in datasets}
         augs = {d.random_augment is not None for d in datasets}
         scales = {d.scale for d in datasets}
@@ -176,6 +211,8 @@ class DeviceTileLoader:
         if len(online) != 1:
             raise ValueError("device_tiles: either every training set synthesises its LR images (online_degradations) or none")
         self.online = online.pop()
+        if self.degrade_tiles and not self.online:
+            raise ValueError("degrade_tiles needs online_degradations on the training sets (and device_tiles)")
         self.degraders = []  # per image: the degrader of its dataset (each dataset builds its own PCA basis, ref :228-238)
         for d in datasets:
             if d.hr_base is None:
@@ -228,6 +265,9 @@ class DeviceTileLoader:
                 return
             B = len(idx)
             zeros = torch.zeros(B, dtype=torch.int64)
+            if self.online and self.degrade_tiles:
+                yield self._degraded_tile_batch(idx)
+                continue
             if self.online:
                 pairs, codes, kernels = [], [], []
                 for i in idx:  # per sample, in batch order: degrader draws (np.random), then flip / crop draws (random)
@@ -251,6 +291,39 @@ class DeviceTileLoader:
             yield {'lr': lr, 'hr': hr, 'tag': [self.tags[i] for i in idx], 'hr_tag': [self.hr_tags[i] for i in idx],
                    'mask': zeros.clone(), 'halfway_data': zeros.clone(), 'metadata': md,
                    'metadata_keys': [tuple(k for _ in range(B)) for k in self.metadata_keys], 'blur_kernels': zeros.clone()}
+
+
+    def _degraded_tile_batch(self, idx):
+        """One batch of the tile-level mode.  Draw order: per sample, in batch order, the degrader's draws (np.random: kernel,
+        [noise level, mask, field seed], [quality]); then per sample the five `random` draws of the crop -- which need only the
+        LR size, known without degrading.  The two streams are separate generators, so this is the whole-image mode's
+        consumption of each."""
+        from . import degrade
+        sm = self.sampler
+        B, s, c = len(idx), sm.scale, sm.crop
+        images = [sm.hr[i] for i in idx]
+        draws = [self.degraders[i].draw() for i in idx]
+        boxes = [degrade.center_crop_box(im.shape[1], im.shape[2], s) for im in images]
+        for (_, _, rh, rw) in boxes:
+            if min(rh, rw) // s < c:
+                raise ValueError(f"LR image {rh // s} x {rw // s} is smaller than the {c}-pixel tile")
+        crops = [sm.draw_for(torch.empty((0, rh // s, rw // s))) for (_, _, rh, rw) in boxes]
+        origins = [tile_source_box(rh // s, rw // s, c, *cr) for (_, _, rh, rw), cr in zip(boxes, crops)]
+        noise, jpeg = draws[0].level is not None, draws[0].quality is not None
+        if any((d.level is not None) != noise or (d.quality is not None) != jpeg for d in draws):
+            raise ValueError("degrade_tiles: the training sets disagree on the noise / jpeg stages of their degraders")
+        lr = degrade.degrade_tiles(images, np.stack([d.kernel.numpy() for d in draws]), origins, c, s,
+                                   flips=[cr[2:] for cr in crops], sigmas=[d.level for d in draws] if noise else None,
+                                   seeds=[d.seed for d in draws] if noise else None,
+                                   qualities=[d.quality for d in draws] if jpeg else None)
+        hr = sm.gather_hr_strided(images, boxes, crops)
+        codes = [d.code.numpy() if self.metadata[i] is None else np.concatenate((self.metadata[i], d.code.numpy()))
+                 for i, d in zip(idx, draws)]
+        zeros = torch.zeros(B, dtype=torch.int64)
+        return {'lr': lr, 'hr': hr, 'tag': [self.tags[i] for i in idx], 'hr_tag': [self.hr_tags[i] for i in idx],
+                'mask': zeros.clone(), 'halfway_data': zeros.clone(), 'metadata': torch.from_numpy(np.stack(codes)),
+                'metadata_keys': _collate_keys(self.metadata_keys, B),
+                'blur_kernels': torch.from_numpy(np.stack([d.kernel.numpy().squeeze() for d in draws]))}
 
 
 def _collate_keys(keys, B):
@@ -431,10 +504,13 @@ class SuperResImages(Dataset):
 
 
 def sisr_data_setup(training_sets, eval_sets, batch_size=16, eval_batch_size=1, dataloader_threads=8,
-                    drop_last_training_batch=False, device_tiles=False, device=None, **common):
+                    drop_last_training_batch=False, device_tiles=False, device=None, degrade_tiles=False, **common):
     """TOML [data] block -> (train DataLoader, val DataLoader).  ref: training/data_setup.py:9-125
     `device_tiles = true` (not a reference option): training batches are cut on the GPU from a device-resident copy
-    of the training images (DeviceTileLoader) instead of by DataLoader workers."""
+    of the training images (DeviceTileLoader) instead of by DataLoader workers.  `degrade_tiles = true` (with device_tiles
+    and online_degradations only): the on-the-fly degradation works on each batch's tiles instead of on whole images."""
+    if degrade_tiles and not (device_tiles and all((d.get('online_degradations') for d in training_sets.values()))):
+        raise ValueError("[data] degrade_tiles = true needs device_tiles = true and online_degradations on every training set")
     common = {k: v for k, v in common.items() if k in ('scale', 'input', 'colorspace')}
 
     def setup(ds, split):
@@ -463,7 +539,7 @@ def sisr_data_setup(training_sets, eval_sets, batch_size=16, eval_batch_size=1, 
     if device_tiles:
         if device is None or not torch.cuda.is_available():
             raise RuntimeError("device_tiles needs a HIP device")
-        return (DeviceTileLoader(train, batch_size, device, drop_last=drop_last_training_batch),
+        return (DeviceTileLoader(train, batch_size, device, drop_last=drop_last_training_batch, degrade_tiles=degrade_tiles),
                 DataLoader(dataset=val, batch_size=eval_batch_size))
     if any(getattr(d, 'online_degradations', False) for d in train):
         dataloader_threads = 0  # the degrader launches HIP kernels: it cannot run in forked DataLoader workers

@@ -20,7 +20,14 @@ JPEG compression (`jpeg_roundtrip`, csrc/jpeg.hip; ref: Code/data_converter.py j
 subsampling=0, quality=q)` + `open`) is the optional last stage on the LR bytes: libjpeg's integer arithmetic per 8 x 8
 block, bit-identical to PIL's decoded image.  `jpeg_roundtrip_host` states the same arithmetic in numpy for images that
 are on the host anyway (tools/make_jpeg_set.py without a GPU) and is what the CPU tests hold against PIL.
+
+Tile-level mode (`degrade_tiles`, csrc/degrade_tiles.hip; `[data] degrade_tiles = true`): the same stages on the HR window a
+batch's tiles depend on instead of on whole images -- one launch per batch, bit-identical tiles -- with the noise from a
+counter-based field (`normal_field`, numpy mirror `normal_field_host`) and JPEG on the tile.  OnlineDegrader.draw() makes an
+access's random draws, apply() the whole-image pixel work; the tile loader (data.DeviceTileLoader) uses draw() alone.
 """
+import collections
+import ctypes
 import math
 
 import numpy as np
@@ -169,11 +176,16 @@ def random_batch_noise(batch, high, rate_cln=1.0):
     return noise_level * noise_mask
 
 
-def noise_quant(blur, sigma):
+def noise_quant(blur, sigma, field=None):
     """(C, H, W) fp32 blurred image on the device -> uint8 byte(255 * clamp(N(0,1) * sigma + blur, 0, 1)).  The N(0,1) field
-    comes from numpy's global stream on the host, as in the reference (b_GaussianNoising, :306-312), and is uploaded."""
+    comes from numpy's global stream on the host, as in the reference (b_GaussianNoising, :306-312), and is uploaded;
+    `field`: one drawn already (host or device tensor of blur's size), nothing is drawn here."""
     C, H, W = blur.shape
-    field = torch.FloatTensor(np.random.normal(loc=0.0, scale=1.0, size=(1, C, H, W))).to(blur.device)
+    if field is None:
+        field = torch.FloatTensor(np.random.normal(loc=0.0, scale=1.0, size=(1, C, H, W)))
+    field = field.to(blur.device).contiguous()
+    if field.numel() != blur.numel():
+        raise ValueError(f"noise field of {field.numel()} values for an image of {blur.numel()}")
     y = torch.empty((C, H, W), device=blur.device, dtype=torch.uint8)
     hip.check(hip.lib().sisr_noise_quant(hip.ptr(blur), hip.ptr(field), float(sigma), y.data_ptr(), blur.numel(), hip.stream()),
               "sisr_noise_quant")
@@ -353,6 +365,149 @@ def center_crop_box(height, width, scale):
     return int(round((height - rh) / 2.)), int(round((width - rw) / 2.)), rh, rw
 
 
+# ----------------------------------------------------------------------------- the counter-based N(0,1) field (tile-level noise)
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al., SC'11) on arrays: counter (..., 4), key (..., 2) uint32 -> (..., 4) uint32."""
+    c = [np.asarray(counter, dtype=np.uint32)[..., i].astype(np.uint64) for i in range(4)]
+    k = [np.asarray(key, dtype=np.uint32)[..., i].astype(np.uint64) for i in range(2)]
+    mask = np.uint64(0xffffffff)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & mask, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & mask]
+        k = [(k[0] + np.uint64(0x9E3779B9)) & mask, (k[1] + np.uint64(0xBB67AE85)) & mask]
+    return np.stack(np.broadcast_arrays(*c), axis=-1).astype(np.uint32)
+
+
+def normal_field_words_host(seed, C, H, W):
+    """The Philox words behind normal_field: uint32 (C, H, ceil(W / 4), 4) = philox(counter = (column >> 2, row, channel, 0),
+    key = (seed, 0))."""
+    q = (W + 3) // 4
+    ctr = np.zeros((C, H, q, 4), np.uint32)
+    ctr[..., 0] = np.arange(q, dtype=np.uint32)[None, None, :]
+    ctr[..., 1] = np.arange(H, dtype=np.uint32)[None, :, None]
+    ctr[..., 2] = np.arange(C, dtype=np.uint32)[:, None, None]
+    return philox4x32_10(ctr, np.array([seed & 0xffffffff, 0], dtype=np.uint32))
+
+
+def normal_field_host(seed, C, H, W):
+    """numpy mirror of normal_field (csrc/noise_field.h): the same words, the same fp32 uniforms u = (float32(word >> 8) +
+    0.5) * 2^-24, Box-Muller on them in float64 -> (C, H, W) float64.  Columns 4q, 4q + 1 take r cos(a), r sin(a) of words
+    0, 1; columns 4q + 2, 4q + 3 those of words 2, 3."""
+    words = normal_field_words_host(seed, C, H, W)
+    u = ((words >> np.uint32(8)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -24)
+    u = u.astype(np.float64)
+    r = np.sqrt(-2.0 * np.log(u[..., 0::2]))
+    a = 2.0 * np.pi * u[..., 1::2]
+    out = np.stack([r * np.cos(a), r * np.sin(a)], axis=-1)  # (C, H, q, pair, cos | sin)
+    return out.reshape(C, H, -1)[:, :, :W]
+
+
+def normal_field(seed, C, H, W, device, words=False):
+    """The N(0,1) field the tile-level path adds (times the noise level) to the blurred image: a pure function of (seed,
+    channel, row, column) -> (C, H, W) fp32 on the device; words: also the raw Philox words, int32 bit patterns
+    (C, H, ceil(W / 4), 4)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("degrade.normal_field runs on a HIP device (normal_field_host is the numpy form)")
+    seed = int(seed)
+    if not 0 <= seed < 1 << 32:
+        raise ValueError(f"the noise seed is a 32-bit unsigned integer; got {seed}")
+    with torch.cuda.device(device):
+        field = torch.empty((C, H, W), device=device, dtype=torch.float32)
+        w = torch.empty((C, H, (W + 3) // 4, 4), device=device, dtype=torch.int32) if words else None
+        hip.check(hip.lib().sisr_normal_field(seed, hip.ptr(field), w.data_ptr() if words else None, C, H, W, hip.stream()),
+                  "sisr_normal_field")
+    return (field, w) if words else field
+
+
+# ----------------------------------------------------------------------------- tile-level degradation (csrc/degrade_tiles.hip)
+def _upload(parts, device):
+    """Several small host arrays as ONE host-to-device copy -> their device addresses (16-byte aligned) and the buffer that
+    keeps them alive."""
+    offs, total = [], 0
+    for p in parts:
+        offs.append(total)
+        total += (p.nbytes + 15) // 16 * 16
+    host = np.zeros(max(total, 16), np.uint8)
+    for p, o in zip(parts, offs):
+        host[o:o + p.nbytes] = np.frombuffer(p.tobytes(), np.uint8)
+    dev = torch.from_numpy(host).to(device)
+    return [dev.data_ptr() + o for o in offs], dev
+
+
+def degrade_tiles(images, kernels, origins, crop, scale, flips=None, sigmas=None, seeds=None, qualities=None, to_float=True):
+    """LR tiles of a batch straight from the device-resident HR images: sample b's tile is the `crop` x `crop` square with
+    origin origins[b] = (ty, tx) of the LR image the whole-image path would make of images[b] with kernels[b] -- blur_quant
+    [+ noise on the unquantised blur], centre crop, pil_bicubic_downsample -- bit for bit, without that image ever existing.
+
+    images: B (C, H, W) fp32 device tensors (sizes may differ); kernels: (B, l, l); flips: B (hflip, vflip, transpose), applied
+    to the finished tile as sisr_crop_augment's index map does; sigmas: B noise levels (None: no noise stage; a level of 0 keeps
+    the stage's clamp) with seeds: B 32-bit seeds of the counter-based field (normal_field); qualities: B JPEG qualities
+    (None: no JPEG stage) -- the round trip of the TILE in source orientation, block grid at the tile's origin, before the
+    flips: jpeg_roundtrip of the tile's bytes, not a crop of the whole image's round trip.
+    -> (B, C, crop, crop) fp32 / 255 or uint8.  One launch (two with JPEG) and one small upload, whatever B is."""
+    B = len(images)
+    crop, scale = int(crop), int(scale)
+    if B < 1 or len(origins) != B:
+        raise ValueError("degrade_tiles needs one tile origin per image")
+    if qualities is not None:
+        if len(qualities) != B:
+            raise ValueError("degrade_tiles needs one JPEG quality per image")
+        qualities = [_check_quality(q) for q in qualities]
+    if sigmas is not None and (seeds is None or len(sigmas) != B or len(seeds) != B):
+        raise ValueError("degrade_tiles needs one noise level and one seed per image")
+    if flips is not None and len(flips) != B:
+        raise ValueError("degrade_tiles needs one (hflip, vflip, transpose) per image")
+    dev = images[0].device
+    if any((not im.is_cuda) or im.device != dev or im.dtype != torch.float32 or im.dim() != 3 or not im.is_contiguous()
+           for im in images):
+        raise RuntimeError("degrade.degrade_tiles: contiguous (C, H, W) fp32 images on one HIP device (no CPU path)")
+    C = images[0].shape[0]
+    if any(im.shape[0] != C for im in images):
+        raise ValueError("degrade_tiles: the images differ in their channel count")
+    k = np.ascontiguousarray(torch.as_tensor(kernels, dtype=torch.float32).numpy().reshape(B, -1))
+    l = int(round(math.sqrt(k.shape[1])))
+    if l * l != k.shape[1]:
+        raise ValueError("degrade_tiles takes (B, l, l) blur kernels")
+    recs = (hip.DegradeTile * B)()
+    bits = []
+    for b, im in enumerate(images):
+        _, H, W = im.shape
+        t0, l0, rh, rw = center_crop_box(H, W, scale)
+        bh, ch, ksh = _device_table(rw, rw // scale, dev)
+        bv, cv, ksv = _device_table(rh, rh // scale, dev)
+        r = recs[b]
+        r.image, r.bounds_h, r.coef_h, r.bounds_v, r.coef_v = im.data_ptr(), bh.data_ptr(), ch.data_ptr(), bv.data_ptr(), cv.data_ptr()
+        r.H, r.W, r.t0, r.l0, r.rh, r.rw = H, W, t0, l0, rh, rw
+        r.ty, r.tx = int(origins[b][0]), int(origins[b][1])
+        r.ksize_h, r.ksize_v = ksh, ksv
+        f = flips[b] if flips is not None else (0, 0, 0)
+        bits.append(int(bool(f[0])) | int(bool(f[1])) << 1 | int(bool(f[2])) << 2)
+        r.flips = 0 if qualities is not None else bits[-1]  # with JPEG the flips wait for the round trip's store
+        r.noise = int(sigmas is not None)
+        r.sigma = float(sigmas[b]) if sigmas is not None else 0.0
+        r.seed = int(seeds[b]) & 0xffffffff if sigmas is not None else 0
+    L = hip.lib()
+    with torch.cuda.device(dev):
+        parts = [np.frombuffer(bytes(recs), np.uint8), k]
+        if qualities is not None:
+            parts += [np.asarray(qualities, np.int32), np.asarray(bits, np.int32)]
+        addr, keep = _upload(parts, dev)
+        direct = qualities is None
+        out = torch.empty((B, C, crop, crop), device=dev, dtype=torch.float32 if (to_float and direct) else torch.uint8)
+        hip.check(L.sisr_degrade_tiles(ctypes.addressof(recs), addr[0], addr[1], out.data_ptr(), B, C, crop, l, scale,
+                                       int(bool(to_float and direct)), hip.stream()), "sisr_degrade_tiles")
+        if not direct:
+            u8, out = out, torch.empty((B, C, crop, crop), device=dev, dtype=torch.float32 if to_float else torch.uint8)
+            hip.check(L.sisr_jpeg_roundtrip_batch(u8.data_ptr(), out.data_ptr(), addr[2], addr[3], B, C, crop,
+                                                  int(bool(to_float)), hip.stream()), "sisr_jpeg_roundtrip_batch")
+        del keep  # freed in stream order behind the launches that read it (torch's caching allocator)
+    return out
+
+
+DegraderDraw = collections.namedtuple("DegraderDraw", "kernel code level seed field quality")
+
+
 class OnlineDegrader:
     """SRMDPreprocessing(pca, random=True[, noise]) + ToPILImage + downsample for one image at a time, as
     SuperResImages.__getitem__ applies it (data_handler.py:446-456); returns device tensors.  With `noise` (ref
@@ -400,25 +555,48 @@ class OnlineDegrader:
             k = isotropic_gaussian_kernel(self.l, self.sig)
         return torch.FloatTensor(k)  # the reference converts the float64 kernel to float32 here (:303)
 
-    def __call__(self, hr):
-        """hr: (3, H, W) fp32 in [0, 1] on the device -> (lr (3, h, w) fp32 device, code (k,) float32 CPU tensor,
-        kernel (l, l) float32 CPU tensor, (top, left, rh, rw) the HR centre crop that matches lr)."""
+    def draw(self, field_shape=None):
+        """Every random draw of one access, on numpy's global stream in the reference's order, and nothing else: the kernel
+        draws; with `noise` the level and its clean mask (random_batch_noise) and then EITHER the host N(0,1) field of
+        `field_shape` = (C, H, W) (the whole-image path: np.random.normal, as b_GaussianNoising) OR, without a shape, one
+        np.random.randint for the 32-bit seed of the counter-based field (the tile-level path, normal_field); with `jpeg` one
+        np.random.randint for the quality, last.  -> DegraderDraw(kernel, code, level, seed, field, quality): kernel (l, l)
+        and code float32 CPU tensors (code complete: kernel code [+ 10 * level] [+ normalised quality]), level a float or
+        None, seed an int or None, field a (1, C, H, W) float32 CPU tensor or None, quality an int or None."""
         kernel = self.draw_kernel()
         code = encode_kernel(kernel, self.pca)
+        level = seed = field = quality = None
         if self.noise:
-            level = torch.FloatTensor(random_batch_noise(1, self.noise_high, self.rate_cln))  # (1, 1) float32, as the reference
-            _, blurred = blur_quant(hr, kernel, want_float=True, want_u8=False)
-            u8 = noise_quant(blurred, float(level[0, 0]))
-            code = torch.cat([code, (level * 10).view(-1)])
+            lv = torch.FloatTensor(random_batch_noise(1, self.noise_high, self.rate_cln))  # (1, 1) float32, as the reference
+            level = float(lv[0, 0])
+            if field_shape is not None:
+                field = torch.FloatTensor(np.random.normal(loc=0.0, scale=1.0, size=(1,) + tuple(field_shape)))
+            else:
+                seed = int(np.random.randint(0, 1 << 32, dtype=np.int64))
+            code = torch.cat([code, (lv * 10).view(-1)])
+        if self.jpeg:
+            quality = int(np.random.randint(self.jpeg_lo, self.jpeg_hi + 1))
+            a, b = self.jpeg_norm
+            code = torch.cat([code, torch.tensor([(quality - a) / (b - a)], dtype=torch.float32)])
+        return DegraderDraw(kernel, code, level, seed, field, quality)
+
+    def apply(self, hr, d):
+        """The pixel work of the whole-image path for the draws `d` (of draw(field_shape=hr.shape)) -> (lr, box)."""
+        if self.noise:
+            _, blurred = blur_quant(hr, d.kernel, want_float=True, want_u8=False)
+            u8 = noise_quant(blurred, d.level, field=d.field)
         else:
-            u8 = blur_quant(hr, kernel)
+            u8 = blur_quant(hr, d.kernel)
         top, left, rh, rw = center_crop_box(hr.shape[1], hr.shape[2], self.scale)
         if (rh, rw) != (hr.shape[1], hr.shape[2]):
             u8 = u8[:, top:top + rh, left:left + rw].contiguous()
         if not self.jpeg:
-            return pil_bicubic_downsample(u8, self.scale), code, kernel, (top, left, rh, rw)
-        q = int(np.random.randint(self.jpeg_lo, self.jpeg_hi + 1))
-        a, b = self.jpeg_norm
-        code = torch.cat([code, torch.tensor([(q - a) / (b - a)], dtype=torch.float32)])
-        lr = jpeg_roundtrip(pil_bicubic_downsample(u8, self.scale, to_float=False), q)
-        return lr, code, kernel, (top, left, rh, rw)
+            return pil_bicubic_downsample(u8, self.scale), (top, left, rh, rw)
+        return jpeg_roundtrip(pil_bicubic_downsample(u8, self.scale, to_float=False), d.quality), (top, left, rh, rw)
+
+    def __call__(self, hr):
+        """hr: (3, H, W) fp32 in [0, 1] on the device -> (lr (3, h, w) fp32 device, code (k,) float32 CPU tensor,
+        kernel (l, l) float32 CPU tensor, (top, left, rh, rw) the HR centre crop that matches lr)."""
+        d = self.draw(field_shape=tuple(hr.shape))
+        lr, box = self.apply(hr, d)
+        return lr, d.code, d.kernel, box

@@ -240,7 +240,22 @@ _SIGS.update({  # frequency-domain (FFT L1) loss: DFT tables, value and gradient
     "sisr_freq_loss": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
 })
 
+_SIGS.update({  # tile-level online degradation: LR + HR tiles of a batch from device-resident HR images (csrc/degrade_tiles.hip)
+    "sisr_degrade_tile_bytes": (c_size_t, []),
+    "sisr_degrade_tiles": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "sisr_jpeg_roundtrip_batch": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    "sisr_normal_field": (c_int, [ctypes.c_uint, P, P, c_int, c_int, c_int, P]),
+    "sisr_crop_augment_strided": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
+})
+
 GM_MAXL = 4
+
+
+class DegradeTile(ctypes.Structure):
+    """Host mirror of sisr_degrade_tile (include/sisr_hip.h)."""
+    _fields_ = [(n, c_void_p) for n in ("image", "bounds_h", "coef_h", "bounds_v", "coef_v")] + \
+               [(n, c_int) for n in ("H", "W", "t0", "l0", "rh", "rw", "ty", "tx", "ksize_h", "ksize_v", "flips", "noise")] + \
+               [("sigma", c_float), ("seed", ctypes.c_uint)]
 
 
 class GateMlpDesc(ctypes.Structure):
