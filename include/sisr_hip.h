@@ -643,6 +643,31 @@ size_t sisr_ssim_loss_workspace_bytes(int planes, int h, int w, int want_grad);
 int sisr_ssim_loss(const float* sr, const float* y, int planes, int h, int w, double data_range, float* value,
                    float* grad /* nullable */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- multi-scale SSIM (csrc/ms_ssim.hip) ---------------------------------------------------------------------------------
+ * MS-SSIM of two batches, plane by plane, and the gradient of its batch mean with respect to the first (no counterpart in
+ * the reference; the loss term of multiscale.MultiScaleStructuralMechanism and the metric of metrics.batch_ms_ssim).
+ * sr, y: [planes][h][w] contiguous fp32, each plane compared as given.  Scale 0 is the plane; scale j + 1 is the 2 x 2 mean
+ * of scale j with stride 2, a trailing odd row or column dropped.  On every scale the window maps of sisr_ssim_loss with the
+ * same C1, C2; c_j = mean over windows of A2 / B2 for j < levels - 1 and of S at the last scale; the plane's value is
+ * prod_j c_j^weights[j], and exactly 0 (with an exactly zero gradient) when any c_j <= 0, a scale of weight 0 included
+ * (the rule looks at the means, not at the weights).  weights: `levels` doubles on the HOST, read at call time.
+ * per_plane (optional): [planes] doubles on the device.  value (optional): one float on the device, the mean of the
+ * planes' values rounded to fp32 once.  At least one of the two is given.  grad (optional): [planes][h][w] fp32,
+ * d value / d sr.  Everything in between is float64, pow included.  3 * levels + 1 launches with value and grad (16 for
+ * five levels; `levels` fewer without grad, one fewer without value), none depending on planes; no atomics: a repeat
+ * call is bit-identical.  No allocation and no host synchronisation: capturable.  Refused before any launch: null sr / y / weights / workspace, neither
+ * per_plane nor value, planes <= 0, levels outside 1 .. 8, h or w < 11 * 2^(levels - 1), a weight that is negative or not
+ * finite, data_range not finite or <= 0, workspace_bytes < sisr_ms_ssim_workspace_bytes(planes, h, w, levels, grad != NULL)
+ * (-1); a workspace that is not 16-byte aligned, a float pointer that is not 4-byte or per_plane that is not 8-byte aligned
+ * (-2); more than 2^31 - 1 tiles (-4).  sisr_ms_ssim_workspace_bytes returns 0 for a refused shape. */
+size_t sisr_ms_ssim_workspace_bytes(int planes, int h, int w, int levels, int want_grad);
+int sisr_ms_ssim(const float* sr, const float* y, int planes, int h, int w, double data_range,
+                 const double* weights /* host */, int levels, double* per_plane /* nullable */, float* value /* nullable */,
+                 float* grad /* nullable */, void* workspace, size_t workspace_bytes, void* stream);
+/* y[n][h][w] = (0.299 R + 0.587 G) + 0.114 B of rgb[n][3][h][w] clipped to [0, 1], in fp32 and in the operation order of
+ * sisr_ssim (channels == 3): the planes metrics.batch_ms_ssim hands to sisr_ms_ssim.  One launch. */
+int sisr_luma_clip(const float* rgb, int n, int h, int w, float* y, void* stream);
+
 /* ---- frequency-domain (FFT L1) training loss (csrc/freq_loss.hip) ------------------------------------------------------
  * The mean absolute real and imaginary part of the orthonormal 2-D DFT of sr - y over the half spectrum, and its gradient
  * with respect to sr (no counterpart in the reference; the loss base + beta * value of frequency.FrequencyMechanism).

@@ -117,7 +117,7 @@ class TrainingHandler:
         wanted = list(dict.fromkeys(self.metrics or ()))  # columns follow the order the metrics are listed in
         for batch in self.val_data:
             y = batch['hr']
-            if 'SSIM' in wanted:  # SSIM on the device output, before it is copied back
+            if 'SSIM' in wanted or 'MS-SSIM' in wanted:  # measured on the device output, before it is copied back
                 rgb_out, ycbcr_out, loss, _, measured = self.model.net_run_process_and_measure(
                     **batch, metrics=wanted, max_value=self.max_im_val, request_loss=True)
             else:
@@ -134,6 +134,8 @@ class TrainingHandler:
                         losses['val-PSNR'].append(M.psnr(ycbcr_out[i, 0], y_proc[i, 0], max_value=self.max_im_val))
                 elif metric == 'SSIM':
                     losses['val-SSIM'].extend(measured['SSIM'])
+                elif metric == 'MS-SSIM':
+                    losses['val-MS-SSIM'].extend(measured['MS-SSIM'])
         return losses
 
     def run_experiment(self):
@@ -238,7 +240,8 @@ def _interpolated(lr, scale, device, want_ycbcr, timing):
 
 def eval_sisr(config=None, **kw):
     """ref: net_eval.py:64-74 / standard_eval.py full_image_protocol: per-image and average Y-PSNR CSVs, plus Y-SSIM
-    columns when the config's `metrics` lists 'SSIM' (ref: standard_eval.py:268-271).  Each model is given the input its
+    columns when the config's `metrics` lists 'SSIM' (ref: standard_eval.py:268-271) and Y-MS-SSIM columns when it lists
+    'MS-SSIM' (metrics.batch_ms_ssim; no counterpart in the reference).  Each model is given the input its
     configuration names (ref: standard_eval.py:254-260): the LR batch as read, that batch bicubic-up-sampled x scale
     ('interp' models), or the up-sampled batch in YCbCr (the Y-channel models).  The up-sampled batch is made once per batch
     (on the device when the models run there), or read from `lr_dir_interp`.  `lr_baseline = true` adds 'LR' rows: the
@@ -273,6 +276,8 @@ def eval_sisr(config=None, **kw):
                           recursive_search=bool(cfg.get('recursive')))
     loader = torch.utils.data.DataLoader(dataset=data, batch_size=cfg.get('batch_size', 1))
     with_ssim = 'SSIM' in (cfg.get('metrics') or ())
+    with_ms = 'MS-SSIM' in (cfg.get('metrics') or ())  # an 'MS-SSIM' column (five scales: images from 176 x 176)
+    on_device = (['SSIM'] if with_ssim else []) + (['MS-SSIM'] if with_ms else [])
     timing = cfg.get('time_models', True)
     baseline = bool(cfg.get('lr_baseline'))
     plus = {'self_ensemble': True} if cfg.get('self_ensemble') else {}
@@ -302,11 +307,15 @@ def eval_sisr(config=None, **kw):
             lr_y = interp_ycbcr[:, :1]
             if with_ssim:
                 lr_ssim = M.batch_ssim(lr_y, torch.from_numpy(y_proc[:, :1]), max_value=1)
+            if with_ms:
+                lr_ms = M.batch_ms_ssim(lr_y, torch.from_numpy(y_proc[:, :1]), max_value=1)
             lr_y = lr_y.cpu().numpy()
             for i, tag in enumerate(batch['tag']):
                 row = {'Image_Name': tag, 'Model': 'LR', 'PSNR': M.psnr(lr_y[i, 0], y_proc[i, 0], 1)}
                 if with_ssim:
                     row['SSIM'] = lr_ssim[i]
+                if with_ms:
+                    row['MS-SSIM'] = lr_ms[i]
                 row['runtime'] = up_secs
                 rows.append(row)
         for m in models:
@@ -318,8 +327,8 @@ def eval_sisr(config=None, **kw):
                         'hr': torch.stack([rgb_to_ycbcr(im, y_only=False) for im in batch['hr']])}
             elif m.configuration['input'] != 'unmodified':
                 feed = {**batch, 'lr': interp}
-            if with_ssim:  # SSIM on the device output (data_range 1), outside the timed window
-                rgb, ycbcr, _, secs, measured = m.net_run_process_and_measure(**feed, metrics=['SSIM'], max_value=1,
+            if on_device:  # SSIM / MS-SSIM on the device output (data_range 1), outside the timed window
+                rgb, ycbcr, _, secs, measured = m.net_run_process_and_measure(**feed, metrics=on_device, max_value=1,
                                                                               timing=timing, **plus)
             else:
                 rgb, ycbcr, _, secs = m.net_run_and_process(**feed, timing=timing, **plus)
@@ -327,6 +336,8 @@ def eval_sisr(config=None, **kw):
                 row = {'Image_Name': tag, 'Model': label(m), 'PSNR': M.psnr(ycbcr[i, 0], y_proc[i, 0], 1)}
                 if with_ssim:
                     row['SSIM'] = measured['SSIM'][i]
+                if with_ms:
+                    row['MS-SSIM'] = measured['MS-SSIM'][i]
                 row['runtime'] = secs
                 rows.append(row)
             if cfg.get('save_im'):
@@ -340,7 +351,7 @@ def eval_sisr(config=None, **kw):
     mdir = os.path.join(out_dir, 'standard_metrics')
     create_dir_if_empty(mdir)
     df.to_csv(os.path.join(mdir, 'individual_metrics.csv'), index=False)
-    avg = df.groupby('Model')[['PSNR', 'SSIM', 'runtime'] if with_ssim else ['PSNR', 'runtime']].mean().reset_index()
+    avg = df.groupby('Model')[['PSNR'] + on_device + ['runtime']].mean().reset_index()
     avg.to_csv(os.path.join(mdir, 'average_metrics.csv'), index=False)
     return df, avg
 

@@ -25,42 +25,8 @@
 // terms of the gradient are O(1 / B2) each and cancel down to O(|x - y| / B2), so maps rounded to fp32 (6e-8 relative) would
 // put back, at |x - y| ~ 2e-3, the 3e-5 relative error of an fp32 composition that this kernel exists to avoid.
 #include "sisr_common.h"
+#include "ssim_window.h"  // SL_*, SsimLossTaps, the tile counts, sl_make_taps, sl_pixel
 #include <math.h>
-
-#define SL_R 5                // filter radius: int(3.5 * 1.5 + 0.5)
-#define SL_K (2 * SL_R + 1)   // 11 taps
-#define SL_TW 64              // tile columns: one per lane
-#define SL_TH 32              // tile rows
-#define SL_SW (SL_TW + 2 * SL_R)  // staged columns per row
-
-struct SsimLossTaps {
-  double w[SL_K];
-};
-
-static inline long sl_div_up(long a, long b) { return (a + b - 1) / b; }
-// tiles of the window grid (forward) and of the pixel grid (gradient)
-static inline long sl_win_tiles_x(int w) { return sl_div_up(w - 2 * SL_R, SL_TW); }
-static inline long sl_win_tiles(int h, int w) { return sl_win_tiles_x(w) * sl_div_up(h - 2 * SL_R, SL_TH); }
-static inline long sl_pix_tiles_x(int w) { return sl_div_up(w, SL_TW); }
-static inline long sl_pix_tiles(int h, int w) { return sl_pix_tiles_x(w) * sl_div_up(h, SL_TH); }
-
-// S in scikit-image's operation order (the order of ssim_pixel in metrics.hip: symmetric, so S(x, x) is exactly 1), and
-// the three coefficients of its differential
-template <bool GRAD>
-__device__ __forceinline__ double sl_pixel(double mx, double my, double mxx, double myy, double mxy, double c1, double c2,
-                                           double& alpha, double& beta, double& gamma) {
-#pragma clang fp contract(off)
-  const double vx = mxx - mx * mx, vy = myy - my * my, vxy = mxy - mx * my;
-  const double a1 = 2.0 * mx * my + c1, a2 = 2.0 * vxy + c2;
-  const double b1 = mx * mx + my * my + c1, b2 = vx + vy + c2;
-  const double s = (a1 * a2) / (b1 * b2);
-  if (GRAD) {
-    beta = -s / b2;
-    gamma = 2.0 * a1 / (b1 * b2);
-    alpha = 2.0 * my * a2 / (b1 * b2) - 2.0 * mx * s / b1 - my * gamma - 2.0 * mx * beta;
-  }
-  return s;
-}
 
 template <bool GRAD>
 __global__ __launch_bounds__(64) void ssim_loss_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b, int h,
@@ -301,14 +267,7 @@ extern "C" int sisr_ssim_loss(const float* sr, const float* y, int planes, int h
     return SISR_ERR_ALIGN;
   const long wt = sl_win_tiles(h, w), pt = sl_pix_tiles(h, w);
   if ((long)planes * wt > 0x7fffffffL || (long)planes * pt > 0x7fffffffL) return SISR_ERR_UNSUPPORTED;
-  // scipy.ndimage._gaussian_kernel1d(1.5, 0, 5), as sisr_ssim forms it: exp(-0.5 / sigma^2 * x^2), normalised by numpy's
-  // sum of 11 terms (eight running partials paired up, then the last three added in order)
-  SsimLossTaps tp;
-  const double f = -0.5 / (1.5 * 1.5);
-  for (int k = 0; k < SL_K; ++k) tp.w[k] = exp(f * (double)((k - SL_R) * (k - SL_R)));
-  double sum = ((tp.w[0] + tp.w[1]) + (tp.w[2] + tp.w[3])) + ((tp.w[4] + tp.w[5]) + (tp.w[6] + tp.w[7]));
-  for (int k = 8; k < SL_K; ++k) sum += tp.w[k];
-  for (int k = 0; k < SL_K; ++k) tp.w[k] /= sum;
+  const SsimLossTaps tp = sl_make_taps();
   const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
   const long nwin = (long)(h - 2 * SL_R) * (long)(w - 2 * SL_R);
   const double count = (double)planes * (double)nwin;

@@ -24,7 +24,7 @@ from torch import nn, optim
 
 from . import architectures as A
 from . import ensemble, metrics, ops
-from .metrics import batch_ssim
+from .metrics import batch_ms_ssim, batch_ssim
 
 
 class L1Loss(nn.Module):
@@ -70,6 +70,16 @@ class BaseModel(nn.Module):
         self.ssim_data_range = kwargs.get('ssim_data_range', 1.0)
         if self.ssim_loss is not None and not self.ssim_loss >= 0:
             raise ValueError("ssim_loss: the weight of the structural term must be >= 0; got %r" % (self.ssim_loss,))
+        # weight of the multi-scale structural term alpha * (1 - MS-SSIM(sr, y)) added after the single-scale one (None / 0: no
+        # such term) and its scale weights (None: the five of ops.MS_SSIM_WEIGHTS, images from 176 x 176); its data range
+        # is ssim_data_range.  Model parameters as well (no counterpart in the reference)
+        self.ms_ssim_loss = kwargs.get('ms_ssim_loss')
+        self.ms_ssim_weights = kwargs.get('ms_ssim_weights')
+        if self.ms_ssim_loss is not None and not (self.ms_ssim_loss >= 0 and math.isfinite(self.ms_ssim_loss)):
+            raise ValueError("ms_ssim_loss: the weight of the multi-scale structural term must be a finite number >= 0; got %r"
+                             % (self.ms_ssim_loss,))
+        if self.ms_ssim_weights is not None:
+            self.ms_ssim_weights = ops.ms_ssim_weights(self.ms_ssim_weights)
         # weight of the frequency-domain term beta * mean |rfft2(sr - y, norm='ortho')| added after the structural one (None / 0: no
         # such term); a model parameter as well (no counterpart in the reference)
         self.freq_loss = kwargs.get('freq_loss')
@@ -190,8 +200,13 @@ class BaseModel(nn.Module):
             # every handler sets its criterion before it calls training_setup: whichever it is becomes the pixel term
             from . import structural
             self.criterion = structural.StructuralMechanism(self.criterion, self.ssim_loss, self.ssim_data_range)
+        if self.ms_ssim_loss is not None and self.ms_ssim_loss != 0 and self.eval_mode is False:
+            from . import multiscale
+            self.criterion = multiscale.MultiScaleStructuralMechanism(
+                self.criterion, self.ms_ssim_loss, self.ssim_data_range,
+                ops.MS_SSIM_WEIGHTS if self.ms_ssim_weights is None else self.ms_ssim_weights)
         if self.freq_loss is not None and self.freq_loss != 0 and self.eval_mode is False:
-            # outermost: pixel or perceptual base -> StructuralMechanism -> FrequencyMechanism
+            # outermost: pixel or perceptual base -> StructuralMechanism -> MultiScaleStructuralMechanism -> FrequencyMechanism
             from . import frequency
             self.criterion = frequency.FrequencyMechanism(self.criterion, self.freq_loss)
 
@@ -778,8 +793,8 @@ class ModelInterface:
     def net_run_process_and_measure(self, lr=None, hr=None, metrics=(), max_value=1, **kwargs):
         """net_run_and_process plus per-image image-quality metrics of the output against `hr`, measured where the output
         is (on the device, sisr_ssim, when the model runs on one) and outside the `timing` window.
-        -> (rgb, ycbcr, loss, timing, {metric: [one value per image]}).  Measured here: 'SSIM' (Y channels, data_range
-        `max_value`); PSNR stays with the callers, on the host."""
+        -> (rgb, ycbcr, loss, timing, {metric: [one value per image]}).  Measured here: 'SSIM' and 'MS-SSIM' (Y channels, data_range
+        `max_value`; MS-SSIM with the five default scale weights, so images from 176 x 176); PSNR stays with the callers, on the host."""
         if 'rgb' not in self.configuration['colorspace']:
             out_y, loss, timing = self._run_y(lr, hr, keep_on_device=True, **kwargs)
             measured = {}
@@ -788,6 +803,11 @@ class ModelInterface:
                     raise RuntimeError('Need a reference to calculate SSIM.')
                 measured['SSIM'] = batch_ssim(out_y.clamp(0, 1), hr[:, :1].to(device=out_y.device).clamp(0, 1),
                                               max_value=max_value)
+            if 'MS-SSIM' in metrics:
+                if hr is None:
+                    raise RuntimeError('Need a reference to calculate MS-SSIM.')
+                measured['MS-SSIM'] = batch_ms_ssim(out_y.clamp(0, 1), hr[:, :1].to(device=out_y.device).clamp(0, 1),
+                                                    max_value=max_value)
             return (*self._y_to_images(out_y, lr), loss, timing, measured)
         out, loss, timing = self.model.run_eval(x=lr, y=hr, keep_on_device=True, **kwargs)
         measured = {}
@@ -795,6 +815,10 @@ class ModelInterface:
             if hr is None:
                 raise RuntimeError('Need a reference to calculate SSIM.')
             measured['SSIM'] = batch_ssim(out, hr.to(device=out.device), max_value=max_value)
+        if 'MS-SSIM' in metrics:
+            if hr is None:
+                raise RuntimeError('Need a reference to calculate MS-SSIM.')
+            measured['MS-SSIM'] = batch_ms_ssim(out, hr.to(device=out.device), max_value=max_value)
         out_rgb = out.cpu()
         out_ycbcr = self.colorspace_convert(out_rgb, colorspace='rgb')
         out_rgb = self._standard_image_formatting(out_rgb.numpy())

@@ -248,6 +248,12 @@ _SIGS.update({  # tile-level online degradation: LR + HR tiles of a batch from d
     "sisr_crop_augment_strided": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
 })
 
+_SIGS.update({  # multi-scale SSIM: per-plane values, their mean and its gradient, float64 throughout (csrc/ms_ssim.hip)
+    "sisr_ms_ssim_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "sisr_ms_ssim": (c_int, [P, P, c_int, c_int, c_int, c_double, P, c_int, P, P, P, P, c_size_t, P]),
+    "sisr_luma_clip": (c_int, [P, c_int, c_int, c_int, P, P]),
+})
+
 GM_MAXL = 4
 
 

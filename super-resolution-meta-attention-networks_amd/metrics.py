@@ -64,6 +64,79 @@ def ssim(img1, img2, max_value=1):
     return float(((a1 * a2) / (b1 * b2)).mean(dtype=np.float64))
 
 
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)  # Wang et al. 2003, as given (they sum to 1.0001)
+
+
+MS_SSIM_MAX_LEVELS = 8
+
+
+def ms_ssim_weights(weights):
+    """the weights as a tuple of floats, checked: 1 .. 8 of them, each finite and >= 0 (the one check of the host form, the
+    operator, the criterion and the handlers)"""
+    try:
+        w = tuple(float(v) for v in weights)
+    except TypeError:
+        raise ValueError(f"ms_ssim_weights must be a sequence of 1 to {MS_SSIM_MAX_LEVELS} numbers; got {weights!r}") from None
+    if not 1 <= len(w) <= MS_SSIM_MAX_LEVELS or not all(np.isfinite(v) and v >= 0 for v in w):
+        raise ValueError(f"ms_ssim_weights must be 1 to {MS_SSIM_MAX_LEVELS} finite numbers >= 0; got {weights!r}")
+    return w
+
+
+def ms_ssim_min_side(levels):
+    """the smallest image side `levels` scales take: the coarsest scale must hold one 11 x 11 window"""
+    return (2 * SSIM_RADIUS + 1) << (levels - 1)
+
+
+def ms_ssim_check_size(what, hw, levels):
+    win, least = 2 * SSIM_RADIUS + 1, ms_ssim_min_side(levels)
+    if min(hw) < least:
+        raise ValueError(f"{what}: with {levels} scales both image sides must be at least {least} (one {win} x {win} window "
+                         f"on the coarsest scale); got {tuple(hw)}.  Smaller images take fewer scales: pass fewer weights in "
+                         f"ms_ssim_weights (each one less halves the minimum)")
+
+
+def _ms_ssim_levels(weights, hw):
+    """the weights as floats, after the checks of the device form: 1 .. 8 finite numbers >= 0, and an image whose coarsest
+    scale holds one window"""
+    w = ms_ssim_weights(weights)
+    ms_ssim_check_size("ms_ssim", hw, len(w))
+    return w
+
+
+def ms_ssim(img1, img2, max_value=1, weights=MS_SSIM_WEIGHTS):
+    """Multi-scale SSIM of two 2-D images in float64 (Wang, Simoncelli, Bovik 2003): prod_j c_j^weights[j], c_j the mean over
+    the windows inside scale j of the contrast-structure term A2 / B2, at the last scale of the full SSIM; every scale with the
+    window and constants of `ssim`.  Scale j + 1 is the 2 x 2 mean of scale j with stride 2, a trailing odd row or column
+    dropped (pytorch_msssim zero-pads odd sides instead: its values differ on such images).  0 when any c_j <= 0, a scale of weight 0 included: the
+    rule looks at the means, not at the weights, as the device form does."""
+    x = np.asarray(img1, dtype=np.float64)
+    y = np.asarray(img2, dtype=np.float64)
+    if x.ndim != 2 or x.shape != y.shape:
+        raise ValueError(f"ms_ssim takes two 2-D images of one shape; got {x.shape} and {y.shape}")
+    weights = _ms_ssim_levels(weights, x.shape)
+    taps = ssim_taps()
+    c1, c2 = (0.01 * max_value) ** 2, (0.03 * max_value) ** 2
+    value = 1.0
+    for j, wj in enumerate(weights):
+        if j:
+            h2, w2 = x.shape[0] // 2 * 2, x.shape[1] // 2 * 2
+            x, y = ((((t[0:h2:2, 0:w2:2] + t[0:h2:2, 1:w2:2]) + t[1:h2:2, 0:w2:2]) + t[1:h2:2, 1:w2:2]) * 0.25
+                    for t in (x, y))
+        ux, uy = _valid_gauss(x, taps), _valid_gauss(y, taps)
+        uxx, uyy, uxy = _valid_gauss(x * x, taps), _valid_gauss(y * y, taps), _valid_gauss(x * y, taps)
+        vx, vy, vxy = uxx - ux * ux, uyy - uy * uy, uxy - ux * uy
+        a2, b2 = 2 * vxy + c2, vx + vy + c2
+        if j == len(weights) - 1:
+            a1, b1 = 2 * ux * uy + c1, ux ** 2 + uy ** 2 + c1
+            c = float(((a1 * a2) / (b1 * b2)).mean(dtype=np.float64))
+        else:
+            c = float((a2 / b2).mean(dtype=np.float64))
+        if c <= 0:
+            return 0.0
+        value *= c ** wj
+    return float(value)
+
+
 def rgb_to_ycbcr_jpg(img, max_val=1):
     """C,H,W RGB -> (Y, Cb, Cr), full-range BT.601 without luma offset."""
     bias_c = 128. * (max_val / 255)
@@ -144,4 +217,46 @@ def batch_ssim(sr, hr, max_value=1):
         out = torch.empty(n, dtype=torch.float64, device=dev)
         hip.check(L.sisr_ssim(hip.ptr(a), hip.ptr(b), n, c, h, w, float(max_value), out.data_ptr(), ws.data_ptr(), nbytes,
                               hip.stream()), "sisr_ssim")
+    return out.cpu().tolist()
+
+
+def batch_ms_ssim(sr, hr, max_value=1, weights=MS_SSIM_WEIGHTS):
+    """Per-image multi-scale SSIM of two (N, C, H, W) batches -> list of N floats, as batch_ssim: C == 3 is clipped RGB
+    compared on Y, C == 1 Y planes used as given.  If either batch is a tensor on a HIP device, both go to the device
+    kernels (sisr_luma_clip for C == 3, then sisr_ms_ssim's per-plane output); anything else takes the host form `ms_ssim`.
+    An image with a side under 11 * 2^(len(weights) - 1) raises."""
+    import torch
+    dev = next((t.device for t in (sr, hr) if isinstance(t, torch.Tensor) and t.is_cuda), None)
+    if dev is None:
+        a, b = (t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in (sr, hr))
+        if a.ndim != 4 or a.shape != b.shape or a.shape[1] not in (1, 3):
+            raise ValueError(f"batch_ms_ssim takes two (N, 1|3, H, W) batches of one shape; got {a.shape} and {b.shape}")
+        if a.shape[1] == 3:
+            a, b = batch_rgb_to_ycbcr(a), batch_rgb_to_ycbcr(b)
+        return [ms_ssim(a[i, 0], b[i, 0], max_value=max_value, weights=weights) for i in range(a.shape[0])]
+    import ctypes
+    from . import hip
+    a, b = (torch.as_tensor(t).to(device=dev, dtype=torch.float32).contiguous() for t in (sr, hr))
+    if a.dim() != 4 or a.shape != b.shape or a.shape[1] not in (1, 3):
+        raise ValueError(f"batch_ms_ssim takes two (N, 1|3, H, W) batches of one shape; got {tuple(a.shape)} and "
+                         f"{tuple(b.shape)}")
+    n, c, h, w = a.shape
+    weights = _ms_ssim_levels(weights, (h, w))
+    if n == 0:
+        return []
+    L = hip.lib()
+    with torch.cuda.device(dev):
+        if c == 3:
+            planes = []
+            for t in (a, b):
+                yp = torch.empty((n, 1, h, w), dtype=torch.float32, device=dev)
+                hip.check(L.sisr_luma_clip(hip.ptr(t), n, h, w, hip.ptr(yp), hip.stream()), "sisr_luma_clip")
+                planes.append(yp)
+            a, b = planes
+        nbytes = L.sisr_ms_ssim_workspace_bytes(n, h, w, len(weights), 0)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(n, dtype=torch.float64, device=dev)
+        wv = (ctypes.c_double * len(weights))(*weights)
+        hip.check(L.sisr_ms_ssim(hip.ptr(a), hip.ptr(b), n, h, w, float(max_value), wv, len(weights), out.data_ptr(), None,
+                                 None, ws.data_ptr(), nbytes, hip.stream()), "sisr_ms_ssim")
     return out.cpu().tolist()

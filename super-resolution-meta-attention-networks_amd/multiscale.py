@@ -1,0 +1,68 @@
+"""Multi-scale structural (MS-SSIM) training loss on the HIP path.
+
+  MultiScaleStructuralMechanism   loss = base(sr, y) + alpha * (1 - mean MS-SSIM(sr, y))
+
+The reference has no such term.  It is the "MS-SSIM + L1" family of Zhao et al. 2017: contrast and structure compared on a
+pyramid of 2 x 2 means (five scales with the default weights of Wang et al. 2003), luminance on the coarsest only, so
+structure far coarser than the 11-pixel window of structural.StructuralMechanism counts.  Every plane of the output is
+compared with the target's as given; value and gradient come from csrc/ms_ssim.hip (ops.ms_ssim_mean), float64 throughout.
+The pyramid drops a trailing odd row or column (F.avg_pool2d(t, 2)); pytorch_msssim zero-pads odd sides instead, so its
+values differ on such images.  A handler builds the term when its model parameter `ms_ssim_loss` is set
+(handlers.BaseModel.training_setup), with the scale weights of `ms_ssim_weights`; unset, nothing changes.
+"""
+import ctypes
+import math
+
+import torch
+from torch import nn
+from torch.autograd import Function
+
+from . import hip, ops
+
+
+class _MsSsimMean(Function):
+    """the node of ops.ms_ssim_mean, modelled on ops._SsimMean: the gradient is computed in the forward call when `sr` needs
+    one (want_grad: torch.is_grad_enabled() at the call), backward returns grad * go"""
+
+    @staticmethod
+    def forward(ctx, sr, y, data_range, weights, want_grad):
+        sr, y = sr.contiguous(), y.contiguous()
+        B, C, H, W = sr.shape
+        L = hip.lib()
+        value = torch.empty((), device=sr.device, dtype=torch.float32)
+        grad = torch.empty_like(sr) if want_grad and ctx.needs_input_grad[0] else None
+        nbytes = L.sisr_ms_ssim_workspace_bytes(B * C, H, W, len(weights), int(grad is not None))
+        ws = hip.workspace(sr.device, nbytes)
+        wv = (ctypes.c_double * len(weights))(*weights)  # host memory, read by the call and not kept
+        hip.check(L.sisr_ms_ssim(hip.ptr(sr), hip.ptr(y), B * C, H, W, float(data_range), wv, len(weights), None,
+                                 hip.ptr(value), hip.ptr(grad), hip.ptr(ws), nbytes, hip.stream()), "sisr_ms_ssim")
+        ctx.save_for_backward(grad)
+        return value
+
+    @staticmethod
+    def backward(ctx, go):
+        (grad,) = ctx.saved_tensors
+        return grad * go, None, None, None, None
+
+
+class MultiScaleStructuralMechanism(nn.Module):
+    """Wraps the criterion a handler had by then, kept as the submodule `base`: its state dict keys appear under `base.`.
+    No parameters of its own.  Capture-safe where `base` is: the term makes no allocation of its own beyond its outputs and
+    no host synchronisation.  Both image sides must be at least 11 * 2^(len(weights) - 1): 176 for the five default weights,
+    88 for four."""
+
+    def __init__(self, base, alpha, data_range=1.0, weights=ops.MS_SSIM_WEIGHTS):
+        super().__init__()
+        alpha, data_range = float(alpha), float(data_range)
+        if not math.isfinite(alpha) or alpha < 0:
+            raise ValueError(f"ms_ssim_loss: the weight of the multi-scale structural term must be a finite number >= 0; "
+                             f"got {alpha}")
+        if not math.isfinite(data_range) or data_range <= 0:
+            raise ValueError(f"ssim_data_range must be a finite number > 0; got {data_range}")
+        self.base = base
+        self.alpha = alpha
+        self.data_range = data_range
+        self.weights = ops.ms_ssim_weights(weights)
+
+    def forward(self, sr, y):
+        return self.base(sr, y) + self.alpha * (1 - ops.ms_ssim_mean(sr, y, self.data_range, self.weights))

@@ -27,6 +27,7 @@ Operators
                  input-gradient-only backward (ref: feature_extractors/VGGNets.py:118-131, sr_tools/loss_functions.py:6-22)
 """
 import collections
+import math
 import os
 
 import torch
@@ -3522,6 +3523,36 @@ def ssim_mean(sr, y, data_range=1.0):
         raise RuntimeError("ssim_mean: the target takes no gradient; detach it")
     # needs_input_grad is set under no_grad as well (run_eval(request_loss=True)): the gradient launch and its maps are skipped there
     return _SsimMean.apply(sr, y, data_range, torch.is_grad_enabled())
+
+
+# ----------------------------------------------------------------------------- multi-scale SSIM (csrc/ms_ssim.hip)
+# the default weights (Wang et al. 2003, as given: they sum to 1.0001) and the checks of the weights and of the image size,
+# shared with the host form
+from .metrics import (MS_SSIM_MAX_LEVELS, MS_SSIM_WEIGHTS, ms_ssim_check_size, ms_ssim_min_side,  # noqa: E402,F401
+                      ms_ssim_weights)
+
+
+def ms_ssim_mean(sr, y, data_range=1.0, weights=MS_SSIM_WEIGHTS):
+    """Mean over all B * C planes of the multi-scale SSIM of two (B, C, H, W) fp32 batches: per plane prod_j c_j^w_j with c_j
+    the mean contrast-structure term A2 / B2 of scale j (full SSIM at the last), scale j + 1 = F.avg_pool2d(scale j, 2), the
+    window of ssim_mean on every scale, every plane as given; exactly 0 for a plane with a c_j <= 0 (whatever that scale's
+    weight, 0 included).  Float64 throughout, the
+    value rounded to fp32 once.  The gradient goes to `sr` only and is computed with the value."""
+    if sr.dim() != 4 or sr.shape != y.shape:
+        raise RuntimeError(f"ms_ssim_mean takes two (B, C, H, W) batches of one shape; got {tuple(sr.shape)} and "
+                           f"{tuple(y.shape)}")
+    weights = ms_ssim_weights(weights)
+    ms_ssim_check_size("ms_ssim_mean", sr.shape[2:], len(weights))
+    if sr.numel() == 0:
+        raise RuntimeError(f"ms_ssim_mean: empty batch {tuple(sr.shape)}")
+    hip.ptr(sr), hip.ptr(y)  # raises on CPU or non-fp32 tensors: there is no CPU path
+    if y.requires_grad:
+        raise RuntimeError("ms_ssim_mean: the target takes no gradient; detach it")
+    # needs_input_grad is set under no_grad as well (run_eval(request_loss=True)): the gradient launches and the maps are skipped there.
+    # The node lives beside its criterion, multiscale._MsSsimMean (that module imports this one, hence the import here): it
+    # has one differentiable input, no parameters and no gradient buffers of its own.
+    from .multiscale import _MsSsimMean
+    return _MsSsimMean.apply(sr, y, data_range, weights, torch.is_grad_enabled())
 
 
 # ----------------------------------------------------------------------------- spectral L1 (csrc/freq_loss.hip)
