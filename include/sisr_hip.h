@@ -100,6 +100,9 @@ size_t sisr_ca_tail_bytes(void);
  *   conv stored through a shuffle view and its input gradient read through one: xview and yview may differ) in the plain form: bias or none, alpha, ReLU, and none of res / mask / in_scale / in_shift /
  *   out_scale / gap_partial / gate / dot / head / LeakyReLU; any other combination at those shapes runs the direct form.
  *   Other channel counts: SISR_ERR_ARG.
+ *   14: as 12, and the Winograd kernel runs its predicated epilogue (per-element bounds tests, clamped operand addresses) on
+ *   every tile.  Under 11 / 12 a tile that lies wholly inside the image (h0 + 4 <= H and w0 + 32 <= W) takes a straight-line
+ *   epilogue instead, with the same values in the same order: 14 exists so that tests can compare the two bit for bit.
  *   U layout: one block of 65536 floats per pair of 64-channel chunks, block (q, c) at (q * cin / 64 + c) * 65536 -- the
  *   (output chunk, input chunk) order and the channel maps of the direct packing -- each [xi 16][G 4][q4 4][co 64][e 4] for
  *   transform point xi = 4 xr + xc and input channel 16 G + 4 q4 + e of the chunk. */

@@ -80,6 +80,7 @@ struct ConvParams {
   int geo_reflect, geo_up, geo_off, geo_h, geo_w;
   int geo_sub;  // with geo_up = 1 and zero padding: the virtual map is the stored one ZERO-STUFFED (value at even coordinates only:
                 // the gradient of a stride-2 conv seen at stride 1), not replicated
+  int pred_epilogue;  // conv3x3_c64_w4_kernel: the predicated epilogue on every tile, full ones included (select 14; tests)
 #ifdef SISR_DIAG
   unsigned* stamp;  // diagnostic library only: per wave {start lo, start hi, staging, K loop, epilogue, HW_ID, XCC_ID, 0}
 #endif
@@ -1106,6 +1107,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
     const int col = 2 * n + j;
     aoff[j] = (unsigned)(2 * mb * (HALO_W * 64) + col * 64 + ((q ^ (col & 15)) << 2));
   }
+  // epilogue of a full tile: the lane's byte offset in y's view from the tile's first pixel (column 8q, channel co)
+  const unsigned loff = (unsigned)(8 * q * (int)p.yv.sW + co) * 4u;
 
   if (t_begin < t_end) {
     halo_regs_t v;
@@ -1257,48 +1260,110 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
       const sisr_rsrc_t rmk = sisr_rsrc(MASK ? p.mask + (long)b * p.yv.sB : p.y);
       const sisr_rsrc_t rrs = sisr_rsrc(RES ? p.res + (long)b * p.yv.sB : p.y);
       const sisr_rsrc_t rdt = sisr_rsrc(DOT ? p.dot + (long)b * p.yv.sB : p.y);
-      float gsum[2];
+      float gsum[2] = {0.f, 0.f};
+      // A tile that lies inside the image (one scalar test, uniform over the workgroup) takes the straight-line form: no
+      // per-element predicate, exec untouched, no clamps.  Element (nb, i, j, r) is addressed as the lane's byte offset loff
+      // (pixel column 8q, channel co) + 64 nb as the instruction's immediate + a scalar offset for (row i, column 2r + j):
+      // the same sum as the predicated form's, which serves the ragged tiles -- and every tile under p.pred_epilogue.
+      // ReLU, the output scale and the partial sums are scalar branches around all 32 elements; the values, their order
+      // and the order of the partial sums are the predicated form's.
+      if (!p.pred_epilogue && h0 + THv <= H && w0 + TW <= W) {
+        const unsigned sHb = (unsigned)(int)p.yv.sH * 4u, sWb = (unsigned)(int)p.yv.sW * 4u;
+        const unsigned s0 = (unsigned)(h0 + 2 * mb) * sHb + (unsigned)w0 * sWb;
+        // in y's registers (dead behind the epilogue; the chunked form clears them at the next item)
+        auto a = [&](int k) -> f32x4& { return y[k >> 2][(k >> 1) & 1][k & 1]; };  // k = nb * 4 + i * 2 + j, registers r
+        unsigned lo = loff;
+        asm volatile("" : "+v"(lo));  // opaque per tile: lo + 64 is then formed here, where it folds into the immediate
+        // (the bias add stands on both sides of the ReLU branch: each side then writes the registers the stores read)
+        if (p.relu) {
 #pragma unroll
-      for (int nb = 0; nb < 2; ++nb) {
-        const int con = co + 16 * nb;
-        float os = p.alpha;
-        if (p.out_scale) os *= p.out_scale[(long)b * 64 + con];
-        float mk[2][2][4], rs[2][2][4], dt[2][2][4];
+          for (int k = 0; k < 8; ++k) a(k) = sisr_relu4(sisr_pk4_add(a(k), (f32x4){bv[k >> 2], bv[k >> 2], bv[k >> 2], bv[k >> 2]}));
+        } else {
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+          for (int k = 0; k < 8; ++k) a(k) = sisr_pk4_add(a(k), (f32x4){bv[k >> 2], bv[k >> 2], bv[k >> 2], bv[k >> 2]});
+        }
+        if (scaled) {
 #pragma unroll
-          for (int j = 0; j < 2; ++j)
+          for (int nb = 0; nb < 2; ++nb) {
+            float os = p.alpha;
+            if (p.out_scale) os *= p.out_scale[(long)b * 64 + co + 16 * nb];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int row = min(h0 + 2 * mb + i, H - 1), col = min(w0 + 8 * q + 2 * r + j, W - 1);
-              const unsigned vo = (unsigned)(col * (int)p.yv.sW + con) * 4u, so = (unsigned)(row * (int)p.yv.sH) * 4u;
-              if (MASK) mk[i][j][r] = sisr_buf_load1(rmk, vo, so);
-              if (RES) rs[i][j][r] = sisr_buf_load1(rrs, vo, so);
-              if (DOT) dt[i][j][r] = sisr_buf_load1(rdt, vo, so);
-            }
-        float gs = 0.f;
-        const f32x4 bv4 = {bv[nb], bv[nb], bv[nb], bv[nb]};
+            for (int k = 0; k < 4; ++k) sisr_pk4_scale(a(nb * 4 + k), (f32x2){os, os});
+          }
+        }
+        // the operand maps one N block at a time (sixteen registers each), as in the predicated form
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+        for (int nb = 0; nb < 2; ++nb) {
+          const unsigned vo = lo + 64u * nb;
+          float mk[16], rs[16], dt[16];  // [(i * 2 + j) * 4 + r]
+          if (MASK || RES || DOT) {
 #pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const f32x4 yb = sisr_pk4_add(y[nb][i][j], bv4);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              float a = yb[r];
-              if (p.relu) a = fmaxf(a, 0.f);
-              if (scaled) a *= os;
-              if (MASK) a = mk[i][j][r] > 0.f ? a : 0.f;
-              if (RES) a += rs[i][j][r];
-              const int row = h0 + 2 * mb + i, col = w0 + 8 * q + 2 * r + j;
-              if (row < H && col < W) {
-                sisr_buf_store1(a, ry, (unsigned)(col * (int)p.yv.sW + con) * 4u, (unsigned)(row * (int)p.yv.sH) * 4u);
-                gs = DOT ? __builtin_fmaf(a, dt[i][j][r], gs) : gs + a;
-              }
+            for (int e = 0; e < 16; ++e) {
+              const unsigned so = s0 + (e >> 3) * sHb + (2 * (e & 3) + ((e >> 2) & 1)) * sWb;
+              if (MASK) mk[e] = sisr_buf_load1(rmk, vo, so);
+              if (RES) rs[e] = sisr_buf_load1(rrs, vo, so);
+              if (DOT) dt[e] = sisr_buf_load1(rdt, vo, so);
             }
           }
-        gs += __shfl_xor(gs, 16);
-        gsum[nb] = gs + __shfl_xor(gs, 32);
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            float t = a(nb * 4 + (e >> 2))[e & 3];
+            if (MASK) t = mk[e] > 0.f ? t : 0.f;
+            if (RES) t += rs[e];
+            sisr_buf_store1(t, ry, vo, s0 + (e >> 3) * sHb + (2 * (e & 3) + ((e >> 2) & 1)) * sWb);
+            a(nb * 4 + (e >> 2))[e & 3] = t;
+          }
+          if (DOT || p.gap) {
+            float gs = 0.f;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) gs = DOT ? __builtin_fmaf(a(nb * 4 + (e >> 2))[e & 3], dt[e], gs) : gs + a(nb * 4 + (e >> 2))[e & 3];
+            gs += __shfl_xor(gs, 16);
+            gsum[nb] = gs + __shfl_xor(gs, 32);
+          }
+        }
+      } else {
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+          const int con = co + 16 * nb;
+          float os = p.alpha;
+          if (p.out_scale) os *= p.out_scale[(long)b * 64 + con];
+          float mk[2][2][4], rs[2][2][4], dt[2][2][4];
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const int row = min(h0 + 2 * mb + i, H - 1), col = min(w0 + 8 * q + 2 * r + j, W - 1);
+                const unsigned vo = (unsigned)(col * (int)p.yv.sW + con) * 4u, so = (unsigned)(row * (int)p.yv.sH) * 4u;
+                if (MASK) mk[i][j][r] = sisr_buf_load1(rmk, vo, so);
+                if (RES) rs[i][j][r] = sisr_buf_load1(rrs, vo, so);
+                if (DOT) dt[i][j][r] = sisr_buf_load1(rdt, vo, so);
+              }
+          float gs = 0.f;
+          const f32x4 bv4 = {bv[nb], bv[nb], bv[nb], bv[nb]};
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              const f32x4 yb = sisr_pk4_add(y[nb][i][j], bv4);
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                float a = yb[r];
+                if (p.relu) a = fmaxf(a, 0.f);
+                if (scaled) a *= os;
+                if (MASK) a = mk[i][j][r] > 0.f ? a : 0.f;
+                if (RES) a += rs[i][j][r];
+                const int row = h0 + 2 * mb + i, col = w0 + 8 * q + 2 * r + j;
+                if (row < H && col < W) {
+                  sisr_buf_store1(a, ry, (unsigned)(col * (int)p.yv.sW + con) * 4u, (unsigned)(row * (int)p.yv.sH) * 4u);
+                  gs = DOT ? __builtin_fmaf(a, dt[i][j][r], gs) : gs + a;
+                }
+              }
+            }
+          gs += __shfl_xor(gs, 16);
+          gsum[nb] = gs + __shfl_xor(gs, 32);
+        }
       }
       if (p.gap && q == 0) {
         const long parts = (long)p.tiles_w * ((H + 3) / 4) * 2;
@@ -2665,6 +2730,8 @@ enum ConvSelect {
   SEL_WINOGRAD = 11,         // the Winograd weights follow the direct packing: as SEL_DEFAULT, Winograd where it pays
   SEL_WINOGRAD_FORCED = 12,  // ... as SEL_PERSISTENT, Winograd forced
   SEL_DIAG_ABL3 = 13,        // -DSISR_DIAG only: ablations 3 / 6 of the general kernel
+  SEL_WINOGRAD_PREDICATED = 14,  // as SEL_WINOGRAD_FORCED, with the predicated epilogue on every tile (tests: the full-tile
+                                 // epilogue against it, bit for bit)
   SEL_DIAG_ABL6 = 16,
 };
 
@@ -2681,12 +2748,12 @@ static inline bool sisr_use_persistent(int variant, long nblk) {
 }
 // The Winograd form (conv3x3_c64_w4_kernel) replaces the persistent one where the caller asserts that the packed weight
 // carries the transform (select 11: where it pays, 12: forced, with the persistent form forced as by 7), from more than
-// 8 x 128^2 output pixels per launch up: below that, gate heads and batched weight gradients change how a batch is
-// launched, and both forms must run one kernel.  SISR_CONV_WINOGRAD=0 switches it off per call.  The same rule selects the
+// 8 x 128^2 output pixels per launch up (14: as 12, with ConvParams::pred_epilogue set): below that, gate heads and batched
+// weight gradients change how a batch is launched, and both forms must run one kernel.  SISR_CONV_WINOGRAD=0 switches it off per call.  The same rule selects the
 // chunked instantiation for the plain form of the fused-shuffle upsampler convs and of their input gradients.
 #define SISR_WINO_MIN_PIXELS (8L * 128 * 128)
 static inline bool sisr_use_winograd(int select, long pixels) {  // select: as the caller passed it
-  if (select == SEL_WINOGRAD_FORCED) return true;
+  if (select == SEL_WINOGRAD_FORCED || select == SEL_WINOGRAD_PREDICATED) return true;
   if (select != SEL_WINOGRAD) return false;
   const char* e = getenv("SISR_CONV_WINOGRAD");
   if (e && e[0] == '0') return false;
@@ -2844,16 +2911,17 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
   const ConvArgs a = {x, xview, wpacked, bias, bias_n, bias_q, y, yview, res, mask, in_scale, in_shift, out_scale, alpha,
                       gap_partial, gate_add, gate_out, dot, B, H, W, cin, cout};
   if (conv_args_missing(a)) return SISR_ERR_ARG;
-  // 11 / 12: the Winograd weights follow the direct packing (64 -> 64, or the shapes of a conv with a fused PixelShuffle(r)
+  // 11 / 12 / 14: the Winograd weights follow the direct packing (64 -> 64, or the shapes of a conv with a fused PixelShuffle(r)
   // and of its input gradient, 64 -> 64 r^2 and 64 r^2 -> 64: the chunked plain form); otherwise as 0 / 7
   const int asked = select;
-  const bool wino_avail = select == SEL_WINOGRAD || select == SEL_WINOGRAD_FORCED;
+  const bool wino_forced = select == SEL_WINOGRAD_FORCED || select == SEL_WINOGRAD_PREDICATED;
+  const bool wino_avail = select == SEL_WINOGRAD || wino_forced;
   if (wino_avail) {
     const int wide = cin > cout ? cin : cout;
     int r = 1;
     while (64 * r * r < wide) ++r;
     if ((cin != 64 && cout != 64) || wide != 64 * r * r) return SISR_ERR_ARG;
-    select = select == SEL_WINOGRAD_FORCED ? SEL_PERSISTENT : SEL_DEFAULT;
+    select = wino_forced ? SEL_PERSISTENT : SEL_DEFAULT;
   }
   const bool wino_chunked = wino_avail && (cin != 64 || cout != 64);
   const sisr_ca_tail_host* head = static_cast<const sisr_ca_tail_host*>(ca_tail);
@@ -2895,6 +2963,7 @@ extern "C" int sisr_conv3x3_c64(const float* x, const int64_t* xview, const floa
   if (relu < 0 || relu > 6 || (relu & 3) == 3 || ((relu & 4) && !mask)) return SISR_ERR_ARG;
   p.relu = relu & 3;
   p.mask_leaky = (relu & 4) != 0;
+  p.pred_epilogue = asked == SEL_WINOGRAD_PREDICATED;
   const bool leaky = p.relu == 2 || p.mask_leaky;
   if (leaky && (gate_add || gate_out || dot || in_scale || in_shift || (p.relu == 2 && (mask || res)) ||
                 (p.mask_leaky && res)))

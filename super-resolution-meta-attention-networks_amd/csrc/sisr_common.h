@@ -72,6 +72,25 @@ __device__ __forceinline__ f32x4 sisr_pk4_sub(f32x4 a, f32x4 b) {
   return (f32x4){lo.x, lo.y, hi.x, hi.y};
 }
 
+// ... the product with one scalar s, passed as the pair (s, s), in place
+__device__ __forceinline__ void sisr_pk4_scale(f32x4& a, f32x2 s) {
+  f32x2 lo = a.xy, hi = a.zw;
+  asm volatile("v_pk_mul_f32 %0, %0, %1" : "+v"(lo) : "v"(s));
+  asm volatile("v_pk_mul_f32 %0, %0, %1" : "+v"(hi) : "v"(s));
+  a = (f32x4){lo.x, lo.y, hi.x, hi.y};
+}
+// max(a, 0), one v_max_f32 per element.  fmaxf(a, 0.f) on a value that comes out of inline assembly costs two: hipcc
+// cannot know that it is canonical and puts a self-max in front.  Same bits for every finite a (-0 gives +0, denormals
+// stay: the kernels keep fp32 denormals) and for infinities; a quiet NaN gives 0 either way.
+__device__ __forceinline__ f32x4 sisr_relu4(f32x4 a) {
+  f32x4 r;
+  asm volatile("v_max_f32 %0, 0, %1" : "=v"(r.x) : "v"(a.x));
+  asm volatile("v_max_f32 %0, 0, %1" : "=v"(r.y) : "v"(a.y));
+  asm volatile("v_max_f32 %0, 0, %1" : "=v"(r.z) : "v"(a.z));
+  asm volatile("v_max_f32 %0, 0, %1" : "=v"(r.w) : "v"(a.w));
+  return r;
+}
+
 // Buffer addressing.  Beside the fp32 MFMA stream a vector-memory instruction with a 64-bit per-lane address
 // (`global_load_dwordx4 v, v[a:a+1], off`) costs its SIMD 30-40 cycles, and every VALU instruction that builds such an
 // address ~4.5 more; the same access as SGPR resource + 32-bit lane offset + SGPR offset (`buffer_load_dwordx4 v, voff,

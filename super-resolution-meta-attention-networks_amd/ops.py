@@ -245,6 +245,7 @@ _STEP_PACKS = {}
 _PACK_WINOGRAD = 0x100  # PackJob.r flag (conv3x3_mfma.hip: SISR_PACK_WINOGRAD)
 WINOGRAD_FLOATS = 16 * 64 * 64  # transformed 64 x 64 weight block, behind the whole direct packing: one per pair of chunks
 SELECT_WINOGRAD, SELECT_WINOGRAD_FORCE = 11, 12  # `select` codes: the packed weight carries the transform (auto / forced)
+SELECT_WINOGRAD_PREDICATED = 14  # ... forced, with the predicated epilogue on every tile (tests of the full-tile epilogue)
 
 
 class _PackPlan:
