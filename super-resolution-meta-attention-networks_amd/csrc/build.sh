@@ -2,14 +2,14 @@
 # Build libsisr_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU).
 #   build.sh        the product library (no diagnostic code, no process-wide state)
 #   build.sh diag   additionally libsisr_hip_diag.so: the same sources with -DSISR_DIAG (ablation / phase-stamp kernel
-#                   builds, occupancy query, MFMA-peak probe) for tools/conv_phases.py, tools/x3_phases.py, tools/mfma_peak.py
+#                   builds, occupancy query, MFMA-peak probe) for tools/conv_phases.py, tools/conv_timeline.py, tools/mfma_peak.py
 #                   -- select it with SISR_HIP_LIB=.../libsisr_hip_diag.so
 set -euo pipefail
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 SRCS=(conv3x3_mfma.hip wgrad3x3_mfma.hip conv3x3_small.hip attention.hip misc.hip han.hip san.hip degrade.hip sft.hip nonlocal.hip sparnet.hip
       metrics.hip basic.hip interp.hip ensemble.hip perceptual.hip ssim_loss.hip jpeg.hip update.hip freq_loss.hip degrade_tiles.hip ms_ssim.hip)
-HDRS=(sisr_common.h ssim_window.h ca_gate.h conv_rgb_out.h degrade_common.h jpeg_block.h noise_field.h)
+HDRS=(sisr_common.h conv_tiles.h ssim_window.h ca_gate.h conv_rgb_out.h degrade_common.h jpeg_block.h noise_field.h)
 
 build() {  # $1 = output, $2 = object dir, $3... = extra flags / sources
   local out=$1 odir=$2; shift 2

@@ -19,78 +19,20 @@
 // Fused prologue: per-(b,ci) affine on the input (used for dRes = dOut*g + c in the RCAB backward).
 // Fused epilogue: +bias, ReLU, scalar and per-(b,co) scale, ReLU-mask, residual add, pixel-shuffle
 // address map, and per-wave partial sums for the global average pool.
-#include "sisr_common.h"
+#include "conv_tiles.h"  // TH, TW, the halo geometry, ConvParams; tile map / walk, fp32 halo staging
 #include "ca_gate.h"
 #include <string.h>
 #include <stdlib.h>
 #include <type_traits>
 
-#define TH 4
-#define TW 32
-#define HALO_H (TH + 2)
-#define HALO_W (TW + 2)
 #define HALO_ITEMS (HALO_H * HALO_W * 16)            // float4 items in the halo
 #define STAGE_ITERS ((HALO_ITEMS + 255) / 256)        // 13
-
-struct ConvParams {
-  const float* x;
-  View xv;
-  float* y;
-  View yv;
-  const float* res;
-  const float* mask;
-  const float* w;
-  const float* bias;
-  const float* in_scale;
-  const float* in_shift;
-  const float* out_scale;
-  float* gap;
-  const float* gate_add;  // GATE prologue: input = x * in_scale[b,c] + gate_add (x's layout), ...
-  float* gate_out;        // ... whose in-image value is also written here once (by the tile that owns the pixel)
-  const float* dot;       // DOT epilogue: gap partials hold sum(v * dot) instead of sum(v) (y's layout)
-  float alpha;
-  int bias_n, bias_q;
-  int B, H, W, cin_chunks, cout_chunks, relu, tiles_w, tiles_h;
-  int mask_leaky;  // relu: 0 none, 1 ReLU, 2 LeakyReLU(0.2); mask_leaky: the mask is LeakyReLU's derivative, not ReLU's
-  // Gate HEADS (template HEAD of conv3x3_c64_v4_kernel, 64 -> 64 fp32): the CONSUMER of a channel-attention gate computes
-  // it -- every workgroup, for its own sample, from the partial sums the previous launch wrote -- instead of a launch of its
-  // own on the serial chain.  Same arithmetic and summation order as ca_gate_fwd / ca_gate_bwd (ca_gate.h).  fwd_gate: the
-  // gate's operands and outputs (HEAD 1); bwd_gate: the per-sample part of its backward (HEAD 2; the parameter gradients
-  // are summed by a launch of their own).
-  struct {
-    const float *w1, *b1, *w2, *b2, *mul;
-    float *s, *hid, *ca, *g;
-    float inv_hw;
-    int R;
-  } fwd_gate;
-  struct {
-    const float *w1, *w2, *hid, *ca, *mul;
-    float *shift, *dmul, *dz2, *dz1;
-    float inv_hw;
-    int R;
-  } bwd_gate;
-  const float* head_part;  // [B][head_parts][64]
-  int head_parts;
-  // Generalised input geometry (template GEO of conv3x3_c64_v4_kernel; all zero elsewhere).  Output pixel (h, w) of the H x W
-  // output reads the VIRTUAL input map of geo_h x geo_w pixels at (h + kh - 1 - geo_off, w + kw - 1 - geo_off):
-  //   geo_reflect: coordinates outside the virtual map are reflected (-1 -> 1, n -> n - 2: ReflectionPad2d(1)) instead of
-  //                reading zeros;  geo_up: the stored map is the virtual one subsampled by 2^geo_up (nearest upsampling read
-  //                in place: stored pixel = virtual >> geo_up);  geo_off = 1 with geo_h = H - 2: the transposed ("full")
-  //                form, an input-gradient map two pixels larger than the gradient it is computed from.
-  int geo_reflect, geo_up, geo_off, geo_h, geo_w;
-  int geo_sub;  // with geo_up = 1 and zero padding: the virtual map is the stored one ZERO-STUFFED (value at even coordinates only:
-                // the gradient of a stride-2 conv seen at stride 1), not replicated
-  int pred_epilogue;  // conv3x3_c64_w4_kernel: the predicated epilogue on every tile, full ones included (select 14; tests)
-#ifdef SISR_DIAG
-  unsigned* stamp;  // diagnostic library only: per wave {start lo, start hi, staging, K loop, epilogue, HW_ID, XCC_ID, 0}
-#endif
-};
 
 // General kernel: every prologue / epilogue combination, XOR-swizzled LDS (16-B chunk k of halo pixel p lives
 // at slot k ^ (p & 15)), 52 KB per workgroup so three fit a CU (register budget 168), rolled tap loop with A two
 // and B six K-steps ahead.  The hot combinations run on the leaner conv3x3_c64_v4_kernel below; this one stays
 // as the fallback and as the carrier of the diagnostic builds that led to it:
-// ABL (selected with sisr_conv3x3_c64_set_variant 13 / 16): 3 = no A and no B loads (pure MFMA + staging + stores),
+// ABL (diagnostic library, `select` 13 / 16): 3 = no A and no B loads (pure MFMA + staging + stores),
 // 6 = phase stamps (s_memtime at start / after staging / after the K loop / at the end, written per wave into the
 // gap buffer as uint32 cycles).  Outputs of ABL builds are meaningless.
 template <int ABL = 0>
@@ -104,19 +46,8 @@ __global__ __launch_bounds__(256, 3) void conv3x3_c64_kernel(ConvParams p) {
   const int lane = tid & 63;
   const int wave = tid >> 6;
   const int q = blockIdx.y;
-  // Workgroups are dealt round-robin over the 8 XCDs (block b -> b % 8, a speed-only assumption): give each
-  // XCD a contiguous run of tiles so vertically adjacent tiles, which share two halo rows, meet in one L2.
-  int bid;
-  {
-    const unsigned nb = gridDim.x, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const unsigned qn = nb >> 3, rn = nb & 7;
-    bid = (int)((xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + idx);
-  }
-  const int tw = bid % p.tiles_w;
-  bid /= p.tiles_w;
-  const int th = bid % p.tiles_h;
-  const int b = bid / p.tiles_h;
-  const int h0 = th * TH, w0 = tw * TW;
+  const TileCoord tc = sisr_tile_decode<TH>(sisr_xcd_tile_id(), p.tiles_w, p.tiles_h);
+  const int b = tc.b, th = tc.th, tw = tc.tw, h0 = tc.h0, w0 = tc.w0;
   const int ph = wave >> 1, ch = wave & 1;
   const int n = lane & 31, hh = lane >> 5;
   const int H = p.H, W = p.W;
@@ -335,17 +266,8 @@ __global__ __launch_bounds__(256, KSEL == 3 ? 2 : 4) void conv3x3_c64_v4_kernel(
   // or 1-2 % longer: the pipe is busy either way.)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int q = blockIdx.y;
-  int bid;
-  {
-    const unsigned nb = gridDim.x, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const unsigned qn = nb >> 3, rn = nb & 7;
-    bid = (int)((xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + idx);
-  }
-  const int tw = bid % p.tiles_w;
-  bid /= p.tiles_w;
-  const int th = bid % p.tiles_h;
-  const int b = bid / p.tiles_h;
-  const int h0 = th * THv, w0 = tw * TW;
+  const TileCoord tc = sisr_tile_decode<THv>(sisr_xcd_tile_id(), p.tiles_w, p.tiles_h);
+  const int b = tc.b, th = tc.th, tw = tc.tw, h0 = tc.h0, w0 = tc.w0;
   const int ph = __builtin_amdgcn_readfirstlane(wave >> 1), ch = __builtin_amdgcn_readfirstlane(wave & 1);
   const int n = lane & 31, hh = lane >> 5;
   const int H = p.H, W = p.W;
@@ -747,6 +669,7 @@ __global__ __launch_bounds__(256, KSEL == 3 ? 2 : 4) void conv3x3_c64_v4_kernel(
 template <bool AFFINE, bool MASK, bool RES, bool GATE, bool DOT>
 __global__ __launch_bounds__(256, 2) void conv3x3_c64_p4_kernel(ConvParams p, int total_tiles) {
   constexpr int MT = 2, THv = 4, HHv = 6;
+  static_assert(THv == TH && HHv == HALO_H, "halo_issue / halo_commit (conv_tiles.h) stage the 4-row tile's halo");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ph = __builtin_amdgcn_readfirstlane(wave >> 1), ch = __builtin_amdgcn_readfirstlane(wave & 1);
@@ -764,103 +687,30 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_p4_kernel(ConvParams p, in
   const unsigned boff = hh * 256 + co * 4;
   const sisr_rsrc_t rw = sisr_rsrc(p.w);
 
-  // tile walk: every XCD sweeps a contiguous eighth of the tiles (vertically adjacent tiles share halo rows through one L2)
-  const int G = gridDim.x;
-  int t_begin = blockIdx.x, t_end = total_tiles, t_step = G;
-  if ((G & 7) == 0) {
-    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3, per = (total_tiles + 7) >> 3;
-    t_begin = xcd * per + idx;
-    t_end = min(total_tiles, (xcd + 1) * per);
-    t_step = G >> 3;
-  }
-  auto decode = [&](int tile, int& b, int& h0, int& w0) {
-    const int tw = tile % p.tiles_w;
-    const int t2 = tile / p.tiles_w;
-    b = t2 / p.tiles_h;
-    h0 = (t2 - b * p.tiles_h) * THv;
-    w0 = tw * TW;
-  };
-  // staging thread map: (16-B piece c4 of a pixel, halo column pcol + {0, 16, 32}), rows 0..5
-  const int c4 = tid & 15, pcol = tid >> 4;
-  f32x4 v[HHv][3];
-  auto issue = [&](int tile) {
-    int b, h0, w0;
-    decode(tile, b, h0, w0);
-    const sisr_rsrc_t rx = sisr_rsrc(p.x + (long)b * p.xv.sB);
-#pragma unroll
-    for (int r = 0; r < HHv; ++r) {
-      const unsigned ro = (unsigned)(min(max(h0 - 1 + r, 0), H - 1) * (int)p.xv.sH) * 4u;  // scalar, bytes
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-        if (k < 2 || pcol < 2) {
-          const unsigned go = (unsigned)(min(max(w0 - 1 + pcol + 16 * k, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u;
-          v[r][k] = sisr_buf_load4(rx, go, ro);
-        }
-    }
-  };
-  auto commit = [&](int tile) {
-    int b, h0, w0;
-    decode(tile, b, h0, w0);
-    const bool interior = h0 >= 1 && h0 + THv + 1 <= H && w0 >= 1 && w0 + TW + 1 <= W;  // scalar
-    f32x4 s4 = {1.f, 1.f, 1.f, 1.f}, t4 = {0.f, 0.f, 0.f, 0.f};
-    if (AFFINE || GATE) s4 = *reinterpret_cast<const f32x4*>(p.in_scale + (long)b * 64 + c4 * 4);
-    if (AFFINE && p.in_shift) t4 = *reinterpret_cast<const f32x4*>(p.in_shift + (long)b * 64 + c4 * 4);
-    const sisr_rsrc_t ro_ = sisr_rsrc(GATE ? p.gate_out + (long)b * p.xv.sB : p.y);
-    // GATE: the skip map is fetched here, not a tile ahead (two prefetched maps would not fit 256 registers beside the K
-    // loop's); its round trip is covered by the other resident workgroup's K loop
-    f32x4 u[GATE ? HHv : 1][3];
-    if (GATE) {
-      const sisr_rsrc_t ru = sisr_rsrc(p.gate_add + (long)b * p.xv.sB);
-#pragma unroll
-      for (int r = 0; r < HHv; ++r) {
-        const unsigned ro = (unsigned)(min(max(h0 - 1 + r, 0), H - 1) * (int)p.xv.sH) * 4u;
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-          if (k < 2 || pcol < 2)
-            u[r][k] = sisr_buf_load4(ru, (unsigned)(min(max(w0 - 1 + pcol + 16 * k, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u, ro);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < HHv; ++r) {
-      const int gh = h0 - 1 + r;
-      const bool rok = gh >= 0 && gh < H;                 // scalar
-      const bool rown = r >= 1 && r <= THv && gh < H;      // scalar: a row this tile owns
-      const unsigned ro = (unsigned)(min(max(gh, 0), H - 1) * (int)p.xv.sH) * 4u;
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-        if (k < 2 || pcol < 2) {
-          const int col = pcol + 16 * k, gw = w0 - 1 + col;
-          const bool cok = gw >= 0 && gw < W && col < HALO_W;
-          f32x4 t = v[r][k];
-          if (AFFINE) t = t * s4 + t4;
-          if (GATE) {
-            t = sisr_mul_add4(t, s4, u[r][k]);
-            if (rown && cok && col >= 1 && col <= TW)
-              sisr_buf_store4(t, ro_, (unsigned)(min(max(gw, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u, ro);
-          }
-          if (!interior) t = sisr_keep_if(t, rok && cok);
-          *reinterpret_cast<f32x4*>(lds + r * (HALO_W * 64) + col * 64 + ((c4 ^ (col & 15)) << 2)) = t;
-        }
-    }
-  };
-
-  if (t_begin < t_end) {
-    issue(t_begin);
-    commit(t_begin);
+  const TileWalk walk(total_tiles, gridDim.x);
+  const HaloLane ln(p, tid);
+  halo_regs_t v;  // the next tile's halo, requested before the K loop and committed after the epilogue (conv_tiles.h)
+  if (walk.begin < walk.end) {
+    const TileCoord first = sisr_tile_decode<THv>(walk.begin, p.tiles_w, p.tiles_h);
+    halo_issue<false>(v, p, ln, first, 0, 0, HHv);
+    halo_commit<AFFINE, GATE>(v, p, ln, first, lds);
   }
   __syncthreads();
   const int Cout = 64;
-  for (int tile = t_begin; tile < t_end; tile += t_step) {
-    const bool has_next = tile + t_step < t_end;  // uniform
-    int b, h0, w0;
-    decode(tile, b, h0, w0);
+  for (int tile = walk.begin; tile < walk.end; tile += walk.step) {
+    const bool has_next = tile + walk.step < walk.end;  // uniform
+    const TileCoord tc = sisr_tile_decode<THv>(tile, p.tiles_w, p.tiles_h);
+    const int b = tc.b, h0 = tc.h0, w0 = tc.w0;
     f32x16 acc0, acc1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = bv;
     f32x4 bq[8];
 #pragma unroll
     for (int s = 0; s < 6; ++s) bq[s] = sisr_buf_load4(rw, boff * 4u, (unsigned)(s * 2048));
-    if (has_next) issue(tile + t_step);  // in flight across the K loop and the epilogue of this tile
+    // decoded outside the guard (past walk.end on the last tile, where it is not used): one decode serves the issue here and
+    // the commit below, which sit in two separate has_next regions
+    const TileCoord next = sisr_tile_decode<THv>(tile + walk.step, p.tiles_w, p.tiles_h);
+    if (has_next) halo_issue<false>(v, p, ln, next, 0, 0, HHv);  // in flight across the K loop and the epilogue of this tile
     {
 #define P4_LOAD_B(s) sisr_buf_load4(rw, boff * 4u, (unsigned)((s) * 2048))
 #define P4_LOAD_A(m, s) \
@@ -975,7 +825,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_p4_kernel(ConvParams p, in
       }
     }
     if (has_next) {
-      commit(tile + t_step);
+      halo_commit<AFFINE, GATE>(v, p, ln, next, lds);
       __syncthreads();
     }
   }
@@ -1010,6 +860,7 @@ template <bool AFFINE, bool MASK, bool RES, bool GATE, bool DOT, bool CHUNKS = f
 __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, int total_tiles, const float* __restrict__ wu) {
   static_assert(!CHUNKS || !(AFFINE || MASK || RES || GATE || DOT), "the chunked form is the plain one");
   constexpr int THv = 4, HHv = 6;
+  static_assert(THv == TH && HHv == HALO_H, "halo_issue / halo_commit (conv_tiles.h) stage the 4-row tile's halo");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1022,83 +873,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
   const unsigned boff = (unsigned)(q * 64 + co) * 16u;  // N block nb: + 256 B
   const int cc = CHUNKS ? p.cin_chunks : 1, n_items = CHUNKS ? p.cin_chunks * p.cout_chunks : 1;
 
-  const int nwg = gridDim.x;
-  int t_begin = blockIdx.x, t_end = total_tiles, t_step = nwg;
-  if ((nwg & 7) == 0) {
-    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3, per = (total_tiles + 7) >> 3;
-    t_begin = xcd * per + idx;
-    t_end = min(total_tiles, (xcd + 1) * per);
-    t_step = nwg >> 3;
-  }
-  auto decode = [&](int tile, int& b, int& h0, int& w0) {
-    const int tw = tile % p.tiles_w;
-    const int t2 = tile / p.tiles_w;
-    b = t2 / p.tiles_h;
-    h0 = (t2 - b * p.tiles_h) * THv;
-    w0 = tw * TW;
-  };
-  // halo staging: conv3x3_c64_p4_kernel's issue / commit; the staged rows live in the caller's scope (one tile's worth:
-  // a kernel-wide array would be one live range around the tile loop)
-  const int c4 = tid & 15, pcol = tid >> 4;
-  typedef f32x4 halo_regs_t[HHv][3];
-  auto issue = [&](halo_regs_t& v, int tile, int chunk, int r0, int r1) {  // halo rows [r0, r1) of input chunk `chunk`
-    int b, h0, w0;
-    decode(tile, b, h0, w0);
-    const sisr_rsrc_t rx = sisr_rsrc(p.x + (long)b * p.xv.sB + (CHUNKS ? p.xv.chunk(chunk) : 0L));
-#pragma unroll
-    for (int r = r0; r < r1; ++r) {
-      const unsigned ro = (unsigned)(min(max(h0 - 1 + r, 0), H - 1) * (int)p.xv.sH) * 4u;
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-        if (k < 2 || pcol < 2) {
-          const unsigned go = (unsigned)(min(max(w0 - 1 + pcol + 16 * k, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u;
-          v[r][k] = sisr_buf_load4(rx, go, ro);
-        }
-    }
-  };
-  auto commit = [&](const halo_regs_t& v, int tile) {
-    int b, h0, w0;
-    decode(tile, b, h0, w0);
-    const bool interior = h0 >= 1 && h0 + THv + 1 <= H && w0 >= 1 && w0 + TW + 1 <= W;
-    f32x4 s4 = {1.f, 1.f, 1.f, 1.f}, t4 = {0.f, 0.f, 0.f, 0.f};
-    if (AFFINE || GATE) s4 = *reinterpret_cast<const f32x4*>(p.in_scale + (long)b * 64 + c4 * 4);
-    if (AFFINE && p.in_shift) t4 = *reinterpret_cast<const f32x4*>(p.in_shift + (long)b * 64 + c4 * 4);
-    const sisr_rsrc_t ro_ = sisr_rsrc(GATE ? p.gate_out + (long)b * p.xv.sB : p.y);
-    f32x4 u[GATE ? HHv : 1][3];
-    if (GATE) {
-      const sisr_rsrc_t ru = sisr_rsrc(p.gate_add + (long)b * p.xv.sB);
-#pragma unroll
-      for (int r = 0; r < HHv; ++r) {
-        const unsigned ro = (unsigned)(min(max(h0 - 1 + r, 0), H - 1) * (int)p.xv.sH) * 4u;
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-          if (k < 2 || pcol < 2)
-            u[r][k] = sisr_buf_load4(ru, (unsigned)(min(max(w0 - 1 + pcol + 16 * k, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u, ro);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < HHv; ++r) {
-      const int gh = h0 - 1 + r;
-      const bool rok = gh >= 0 && gh < H;
-      const bool rown = r >= 1 && r <= THv && gh < H;
-      const unsigned ro = (unsigned)(min(max(gh, 0), H - 1) * (int)p.xv.sH) * 4u;
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-        if (k < 2 || pcol < 2) {
-          const int col = pcol + 16 * k, gw = w0 - 1 + col;
-          const bool cok = gw >= 0 && gw < W && col < HALO_W;
-          f32x4 t = v[r][k];
-          if (AFFINE) t = t * s4 + t4;
-          if (GATE) {
-            t = sisr_mul_add4(t, s4, u[r][k]);
-            if (rown && cok && col >= 1 && col <= TW)
-              sisr_buf_store4(t, ro_, (unsigned)(min(max(gw, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u, ro);
-          }
-          if (!interior) t = sisr_keep_if(t, rok && cok);
-          *reinterpret_cast<f32x4*>(lds + r * (HALO_W * 64) + col * 64 + ((c4 ^ (col & 15)) << 2)) = t;
-        }
-    }
-  };
+  const TileWalk walk(total_tiles, gridDim.x);
+  const HaloLane ln(p, tid);
+  // halo staging (conv_tiles.h): the staged rows live in the tile's scope (one tile's worth: a kernel-wide array would be
+  // one live range around the tile loop)
 
   // A fragments: halo float offset of (row 2mb, column 2n + j, piece q ^ (col & 15)); step G flips bits 4..5 (piece 4G + q)
   unsigned aoff[4];
@@ -1110,23 +888,26 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
   // epilogue of a full tile: the lane's byte offset in y's view from the tile's first pixel (column 8q, channel co)
   const unsigned loff = (unsigned)(8 * q * (int)p.yv.sW + co) * 4u;
 
-  if (t_begin < t_end) {
+  if (walk.begin < walk.end) {
     halo_regs_t v;
-    issue(v, t_begin, 0, 0, HHv);
-    commit(v, t_begin);
+    const TileCoord first = sisr_tile_decode<THv>(walk.begin, p.tiles_w, p.tiles_h);
+    halo_issue<CHUNKS>(v, p, ln, first, 0, 0, HHv);
+    halo_commit<AFFINE, GATE>(v, p, ln, first, lds);
   }
   __syncthreads();
   f32x4 y[2][2][2];  // [nb][out row i][out col j], registers = the lane's four tiles 4q + reg
   // one loop over (tile, item): nested, the epilogue's per-tile addresses would be hoisted over the items' K loops
-  for (int tile = t_begin, item = 0; tile < t_end; tile = (CHUNKS && item + 1 < n_items) ? tile : tile + t_step,
+  for (int tile = walk.begin, item = 0; tile < walk.end; tile = (CHUNKS && item + 1 < n_items) ? tile : tile + walk.step,
            item = (CHUNKS && item + 1 < n_items) ? item + 1 : 0) {
     // item = (output chunk oq, input chunk ic); the next item's halo is another one where the input chunk or the tile moves
     const int oq = CHUNKS ? item / cc : 0, ic = CHUNKS ? item - oq * cc : 0;
     const bool last_item = item + 1 == n_items, last_ic = ic + 1 == cc;
-    const int ntile = last_item ? tile + t_step : tile, nic = last_ic ? 0 : ic + 1;
-    const bool has_next = (last_item ? tile + t_step < t_end : true) && (!CHUNKS || cc > 1 || last_item);
-    int b, h0, w0;
-    decode(tile, b, h0, w0);
+    const int ntile = last_item ? tile + walk.step : tile, nic = last_ic ? 0 : ic + 1;
+    const bool has_next = (last_item ? tile + walk.step < walk.end : true) && (!CHUNKS || cc > 1 || last_item);
+    const TileCoord tc = sisr_tile_decode<THv>(tile, p.tiles_w, p.tiles_h);
+    const int b = tc.b, h0 = tc.h0, w0 = tc.w0;
+    // the next tile is decoded at each of its three uses: its coordinates held across the K loop cost this kernel 12 B of scratch
+    auto next = [&] { return sisr_tile_decode<THv>(ntile, p.tiles_w, p.tiles_h); };
     if (CHUNKS) {
       rw = sisr_rsrc(wu + (long)item * (16 * 64 * 64));
       if (ic == 0) {
@@ -1181,8 +962,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
       const int xr = s >> 2, G = s & 3;
       // the next tile's halo is requested in two halves, at steps 12 and 14 of 16 (few registers held across the K loop),
       // and written to LDS right after the loop
-      if (s == 12 && has_next) issue(v, ntile, nic, 0, 3);
-      if (s == 14 && has_next) issue(v, ntile, nic, 3, HHv);
+      if (s == 12 && has_next) halo_issue<CHUNKS>(v, p, ln, next(), nic, 0, 3);
+      if (s == 14 && has_next) halo_issue<CHUNKS>(v, p, ln, next(), nic, 3, HHv);
       // step s + 1 is read and transformed under the MFMAs of step s, half the columns at a time
       if (s + 1 < 16) read_half(s + 1, 0);
 #pragma unroll
@@ -1248,7 +1029,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_w4_kernel(ConvParams p, in
     }
 #undef W4_LOAD_B
     if (!CHUNKS || has_next) __syncthreads();  // every wave is done with this tile's halo
-    if (has_next) commit(v, ntile);
+    if (has_next) halo_commit<AFFINE, GATE>(v, p, ln, next(), lds);
     // ---- epilogue: pixel (h0 + 2 mb + i, w0 + 8 q + 2 reg + j), channel co + 16 nb
     if (!CHUNKS || last_ic) {
       if (CHUNKS && p.bias) {
@@ -1409,17 +1190,8 @@ __global__ __launch_bounds__(256, 3) void conv3x3_c64_bf16_kernel(ConvParams p) 
   extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int q = blockIdx.y;
-  int bid;
-  {
-    const unsigned nb = gridDim.x, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const unsigned qn = nb >> 3, rn = nb & 7;
-    bid = (int)((xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + idx);
-  }
-  const int tw = bid % p.tiles_w;
-  bid /= p.tiles_w;
-  const int th = bid % p.tiles_h;
-  const int b = bid / p.tiles_h;
-  const int h0 = th * TH, w0 = tw * TW;
+  const TileCoord tc = sisr_tile_decode<TH>(sisr_xcd_tile_id(), p.tiles_w, p.tiles_h);
+  const int b = tc.b, th = tc.th, tw = tc.tw, h0 = tc.h0, w0 = tc.w0;
   const int ph = __builtin_amdgcn_readfirstlane(wave >> 1), ch = __builtin_amdgcn_readfirstlane(wave & 1);
   const int n = lane & 31, hh = lane >> 5;
   const int H = p.H, W = p.W;
@@ -1703,6 +1475,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_x3_kernel(ConvParams p, lo
   __builtin_amdgcn_s_setprio(3);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int q = blockIdx.y;
+  // sisr_xcd_tile_id() and sisr_tile_decode<TH>() of conv_tiles.h, written out: with the shared functions hipcc waits for the
+  // kernel arguments earlier in this kernel's prologue, and its forms ran 0.7 - 1.3 % slower at 32 x 128^2 (profiles/README.md,
+  // round 12)
   int bid;
   {
     const unsigned nb = gridDim.x, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
@@ -2049,12 +1824,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16_persist_kernel(ConvPa
   extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int G = gridDim.x;
-  int g;
-  {
-    const unsigned nb = gridDim.x, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const unsigned qn = nb >> 3, rn = nb & 7;
-    g = (int)((xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + idx);
-  }
+  const int g = sisr_xcd_tile_id();  // the first tile of this workgroup: the XCD map of the per-tile launches
   const int ph = __builtin_amdgcn_readfirstlane(wave >> 1), ch = __builtin_amdgcn_readfirstlane(wave & 1);
   const int n = lane & 31, hh = lane >> 5;
   const int H = p.H, W = p.W;
@@ -2082,11 +1852,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_bf16_persist_kernel(ConvPa
   Halo v;
   const int eidx = tid % 96, er = eidx >> 4, eside = (eidx >> 3) & 1, ec8 = eidx & 7;
   auto decode = [&](int tile, int& b, int& h0, int& w0) {
-    b = tile / tiles_per_img;
-    const int r = tile - b * tiles_per_img;
-    const int th = r / p.tiles_w;
-    h0 = th * TH;
-    w0 = (r - th * p.tiles_w) * TW;
+    const TileCoord tc = sisr_tile_decode_by_image<TH>(tile, tiles_per_img, p.tiles_w);
+    b = tc.b, h0 = tc.h0, w0 = tc.w0;
   };
   // Every map access below is {resource on a wave-uniform base, 32-bit lane byte offset, scalar byte offset}: beside the
   // other resident workgroup's MFMA stream a vector-memory instruction with a 64-bit lane address costs the SIMD tens of
@@ -3294,7 +3061,7 @@ extern "C" int sisr_conv3x3_c64_x3(const float* x, const int64_t* xview, const v
   hipStream_t st = (hipStream_t)stream;
   const long wplane = (long)cin * cout * 9 * 2;  // bytes between the hi / mid / lo planes of the packed weights
 #ifdef SISR_DIAG
-  if (getenv("SISR_X3_STAMP") && dot && !gate_add && !in_scale && !mask && !res) {  // tools/x3_phases.py
+  if (getenv("SISR_X3_STAMP") && dot && !gate_add && !in_scale && !mask && !res) {  // tools/conv_timeline.py
     SISR_ALLOW_LDS((conv3x3_c64_x3_kernel<false, false, false, false, false, true>), lb);
     hipLaunchKernelGGL((conv3x3_c64_x3_kernel<false, false, false, false, false, true>), grid, dim3(256), lb, st, p, wplane);
     return sisr_check_launch();

@@ -16,7 +16,7 @@
 // slab; a second kernel adds the S slabs in index order (deterministic, no atomics) and scatters
 // into the OIHW gradient.  Splitting the OUTPUT four ways instead of giving each wave a quadrant
 // cuts the slab traffic 4x (36.9 KB per workgroup) at the price of re-reading the inputs from L2.
-#include "sisr_common.h"
+#include "conv_tiles.h"  // TileWalk, tile decode (and sisr_common.h)
 #include <string.h>
 #include <stdlib.h>
 
@@ -273,14 +273,7 @@ static __device__ __forceinline__ void wgrad3x3_c64_full_body(const WgradParams&
 
   const int tiles_per_img = p.tiles_w * p.tiles_h;
   const int total = tiles_per_img * p.B;
-  // every XCD sweeps a contiguous eighth of the tiles (vertically adjacent tiles share two halo rows through one L2)
-  int t_begin = blockIdx.x, t_end = total, t_step = p.S;
-  if ((p.S & 7) == 0) {
-    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3, per = (total + 7) >> 3;
-    t_begin = xcd * per + idx;
-    t_end = min(total, (xcd + 1) * per);
-    t_step = p.S >> 3;
-  }
+  const TileWalk walk(total, p.S);
   struct Stage {
     f32x4 x[WH_H][2];
     f32x4 xe[2];
@@ -290,11 +283,8 @@ static __device__ __forceinline__ void wgrad3x3_c64_full_body(const WgradParams&
   const int c8 = tid & 7, pcol = tid >> 3;
   const int eidx = tid % 160, er = eidx >> 4, eside = (eidx >> 3) & 1, ec8 = eidx & 7;
   auto decode = [&](int tile, int& b, int& h0, int& w0) {
-    b = tile / tiles_per_img;
-    const int tr = tile - b * tiles_per_img;
-    const int th = tr / p.tiles_w;
-    h0 = th * WT_H;
-    w0 = (tr - th * p.tiles_w) * WT_W;
+    const TileCoord tc = sisr_tile_decode_by_image<WT_H, WT_W>(tile, tiles_per_img, p.tiles_w);
+    b = tc.b, h0 = tc.h0, w0 = tc.w0;
   };
   const bool refl = GEO && p.geo_reflect;  // scalar
   const int gup = GEO ? p.geo_up : 0, ysub = GEO ? p.geo_ysub : 0;
@@ -399,14 +389,14 @@ static __device__ __forceinline__ void wgrad3x3_c64_full_body(const WgradParams&
     }
   };
 
-  if (t_begin < t_end) {
-    issue(t_begin);
-    commit(t_begin);
+  if (walk.begin < walk.end) {
+    issue(walk.begin);
+    commit(walk.begin);
   }
   __syncthreads();
-  for (int tile = t_begin; tile < t_end; tile += t_step) {
-    const bool has_next = tile + t_step < t_end;  // uniform
-    if (has_next) issue(tile + t_step);
+  for (int tile = walk.begin; tile < walk.end; tile += walk.step) {
+    const bool has_next = tile + walk.step < walk.end;  // uniform
+    if (has_next) issue(tile + walk.step);
     // ---- K loop: 8 rows x 16 pixel pairs x 9 taps; K index (lane >> 5) = pixel parity.  One wave per SIMD: nobody else
     // covers an LDS round trip, so the ten operands of pair u + 1 (or of the next row's first pair) are requested before
     // the nine MFMAs of pair u are issued.
@@ -447,7 +437,7 @@ static __device__ __forceinline__ void wgrad3x3_c64_full_body(const WgradParams&
     }
     __syncthreads();  // every wave is done with this tile's LDS image
     if (has_next) {
-      commit(tile + t_step);
+      commit(tile + walk.step);
       __syncthreads();
     }
   }
@@ -564,13 +554,7 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
   const int tiles_w = p.tiles_w, tiles_h = (H + W4_TH - 1) / W4_TH;
   const int tiles_per_img = tiles_w * tiles_h;
   const int total = tiles_per_img * p.B;
-  int t_begin = blockIdx.x, t_end = total, t_step = p.S;
-  if ((p.S & 7) == 0) {
-    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3, per = (total + 7) >> 3;
-    t_begin = xcd * per + idx;
-    t_end = min(total, (xcd + 1) * per);
-    t_step = p.S >> 3;
-  }
+  const TileWalk walk(total, p.S);
   struct Stage {
     f32x4 x[W4_HH][2];
     f32x4 xe[2];
@@ -583,11 +567,8 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
   const int c8 = tid & 7, pcol = tid >> 3;
   const int eidx = tid % 96, er = eidx >> 4, eside = (eidx >> 3) & 1, ec8 = eidx & 7;  // edge columns: 6 x 2 x 8 items
   auto decode = [&](int tile, int& b, int& h0, int& w0) {
-    b = tile / tiles_per_img;
-    const int tr = tile - b * tiles_per_img;
-    const int th = tr / tiles_w;
-    h0 = th * W4_TH;
-    w0 = (tr - th * tiles_w) * WT_W;
+    const TileCoord tc = sisr_tile_decode_by_image<W4_TH, WT_W>(tile, tiles_per_img, tiles_w);
+    b = tc.b, h0 = tc.h0, w0 = tc.w0;
   };
   auto issue = [&](int tile) {
     int b, h0, w0;
@@ -775,18 +756,18 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
   // the next tile is committed in front of step 15's MFMAs and its step 0 is fetched and transformed between them (read,
   // unused, from the stale image after the last tile).
   Ops ops[2];
-  if (t_begin < t_end) {
-    issue(t_begin);
-    commit(t_begin);
+  if (walk.begin < walk.end) {
+    issue(walk.begin);
+    commit(walk.begin);
     __syncthreads();
     Raw rw;
     fetch(0, rw);
 #pragma unroll
     for (int k = 0; k < 12; ++k) transform_op(k, rw, ops[0]);
   }
-  for (int tile = t_begin; tile < t_end; tile += t_step) {
-    const bool has_next = tile + t_step < t_end;  // uniform
-    if (has_next) issue(tile + t_step);
+  for (int tile = walk.begin; tile < walk.end; tile += walk.step) {
+    const bool has_next = tile + walk.step < walk.end;  // uniform
+    if (has_next) issue(tile + walk.step);
 #pragma unroll
     for (int ks = 0; ks < 15; ++ks) {  // reads behind the first MFMA, three MFMAs for them to land, then four adds to a gap
       const int cur = ks & 1, nxt = cur ^ 1;
@@ -812,7 +793,7 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
       __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();  // no wave reads the raw image again
-    if (has_next) commit(tile + t_step);
+    if (has_next) commit(tile + walk.step);
 #pragma unroll
     for (int t = 0; t < 8; ++t) mfma(t, ops[1]);
     __builtin_amdgcn_sched_barrier(0);  // the commit's LDS writes drain under those eight MFMAs
@@ -971,17 +952,8 @@ static __device__ __forceinline__ void wgrad3x3_c64_bf16_body(const WgradParams&
 
   const int tiles_per_img = p.tiles_w * p.tiles_h;
   const int total = tiles_per_img * p.B;
-  // Tile walk.  Workgroup s lands on XCD s % 8; give every XCD a contiguous eighth of the tiles and let its S / 8
-  // workgroups sweep it together, so that vertically adjacent tiles (whose 10-row halos share two rows) are read
-  // through the same L2 at about the same time.  (HBM-bound kernel: measured 316 MB read per launch with the
-  // strided walk against 268 MB algorithmic.)  Falls back to the strided walk when S is not a multiple of 8.
-  int t_begin = blockIdx.x, t_end = total, t_step = p.S;
-  if ((p.S & 7) == 0) {
-    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3, per = (total + 7) >> 3;
-    t_begin = xcd * per + idx;
-    t_end = min(total, (xcd + 1) * per);
-    t_step = p.S >> 3;
-  }
+  // the per-XCD walk (conv_tiles.h).  HBM-bound kernel: the strided walk read 316 MB per launch against 268 MB algorithmic
+  const TileWalk walk(total, p.S);
   // ---- staging split into "issue the loads" and "convert + write LDS": one workgroup per CU (512 VGPRs per wave),
   // the loads of tile i+1 (38 float4 per thread) are in flight while tile i is in its K loop.  Thread (c8, pcol)
   // owns channels 8 c8 .. +7 of x halo column pcol + 1 (ten rows) and of dY column pcol (eight rows); the two edge
@@ -1002,11 +974,8 @@ static __device__ __forceinline__ void wgrad3x3_c64_bf16_body(const WgradParams&
     b[2] = __uint_as_float(w[3] << 16); b[3] = __uint_as_float(w[3] & 0xffff0000u);
   };
   auto decode = [&](int tile, int& b, int& h0, int& w0) {
-    b = tile / tiles_per_img;
-    const int tr = tile - b * tiles_per_img;
-    const int th = tr / p.tiles_w;
-    h0 = th * WT_H;
-    w0 = (tr - th * p.tiles_w) * WT_W;
+    const TileCoord tc = sisr_tile_decode_by_image<WT_H, WT_W>(tile, tiles_per_img, p.tiles_w);
+    b = tc.b, h0 = tc.h0, w0 = tc.w0;
   };
   auto issue = [&](int tile) {
     int b, h0, w0;
@@ -1097,15 +1066,15 @@ static __device__ __forceinline__ void wgrad3x3_c64_bf16_body(const WgradParams&
   unsigned long long st_life = 0, st_a = 0, st_k = 0, st_c = 0;
   unsigned st_tiles = 0;
   if (stamp) st_life = __builtin_amdgcn_s_memtime();
-  if (t_begin < t_end) {
-    issue(t_begin);
-    commit(t_begin);
+  if (walk.begin < walk.end) {
+    issue(walk.begin);
+    commit(walk.begin);
   }
   __syncthreads();
-  for (int tile = t_begin; tile < t_end; tile += t_step) {
-    const bool has_next = tile + t_step < t_end;  // uniform
+  for (int tile = walk.begin; tile < walk.end; tile += walk.step) {
+    const bool has_next = tile + walk.step < walk.end;  // uniform
     if (stamp) st_a = __builtin_amdgcn_s_memtime();
-    if (has_next) issue(tile + t_step);
+    if (has_next) issue(tile + walk.step);
 
     // ---- 16 K-steps of 16 pixels (tile row r = ks >> 1, half hf = ks & 1), nine taps each.  One wave per SIMD: nobody
     // else covers an LDS round trip, so the ten fragments of K-step ks + 1 are requested before the nine MFMAs of step ks
@@ -1137,7 +1106,7 @@ static __device__ __forceinline__ void wgrad3x3_c64_bf16_body(const WgradParams&
     }
     __syncthreads();  // every wave is done with this tile's LDS image
     if (has_next) {
-      commit(tile + t_step);
+      commit(tile + walk.step);
       __syncthreads();
     }
     if (stamp) st_c += __builtin_amdgcn_s_memtime() - st_a;
@@ -1251,17 +1220,7 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_x3_kernel(WgradParams p) 
 
   const int tiles_per_img = p.tiles_w * p.tiles_h;
   const int total = tiles_per_img * p.B;
-  // Tile walk.  Workgroup s lands on XCD s % 8; give every XCD a contiguous eighth of the tiles and let its S / 8
-  // workgroups sweep it together, so that vertically adjacent tiles (whose 10-row halos share two rows) are read
-  // through the same L2 at about the same time.  (HBM-bound kernel: measured 316 MB read per launch with the
-  // strided walk against 268 MB algorithmic.)  Falls back to the strided walk when S is not a multiple of 8.
-  int t_begin = blockIdx.x, t_end = total, t_step = p.S;
-  if ((p.S & 7) == 0) {
-    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3, per = (total + 7) >> 3;
-    t_begin = xcd * per + idx;
-    t_end = min(total, (xcd + 1) * per);
-    t_step = p.S >> 3;
-  }
+  const TileWalk walk(total, p.S);
   // ---- staging split into "issue the loads" and "convert + write LDS": one workgroup per CU (512 VGPRs per wave),
   // the loads of tile i+1 (38 float4 per thread) are in flight while tile i is in its K loop.  Thread (c8, pcol)
   // owns channels 8 c8 .. +7 of x halo column pcol + 1 (ten rows) and of dY column pcol (eight rows); the two edge
@@ -1275,11 +1234,8 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_x3_kernel(WgradParams p) 
   const int c8 = tid & 7, pcol = tid >> 3;
   const int eidx = tid % (XW_HH * 16), er = eidx >> 4, eside = (eidx >> 3) & 1, ec8 = eidx & 7;
   auto decode = [&](int tile, int& b, int& h0, int& w0) {
-    b = tile / tiles_per_img;
-    const int tr = tile - b * tiles_per_img;
-    const int th = tr / p.tiles_w;
-    h0 = th * XW_TH;
-    w0 = (tr - th * p.tiles_w) * WT_W;
+    const TileCoord tc = sisr_tile_decode_by_image<XW_TH, WT_W>(tile, tiles_per_img, p.tiles_w);
+    b = tc.b, h0 = tc.h0, w0 = tc.w0;
   };
   auto issue = [&](int tile) {
     int b, h0, w0;
@@ -1348,14 +1304,14 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_x3_kernel(WgradParams p) 
     }
   };
 
-  if (t_begin < t_end) {
-    issue(t_begin);
-    commit(t_begin);
+  if (walk.begin < walk.end) {
+    issue(walk.begin);
+    commit(walk.begin);
   }
   __syncthreads();
-  for (int tile = t_begin; tile < t_end; tile += t_step) {
-    const bool has_next = tile + t_step < t_end;  // uniform
-    if (has_next) issue(tile + t_step);
+  for (int tile = walk.begin; tile < walk.end; tile += walk.step) {
+    const bool has_next = tile + walk.step < walk.end;  // uniform
+    if (has_next) issue(tile + walk.step);
 
     // ---- 8 K-steps of 16 pixels (tile row r, half hf), nine taps each, six products per tap:
     // hi*hi, hi*mid, mid*hi, hi*lo, lo*hi, mid*mid (A = x planes, B = dY planes)
@@ -1387,7 +1343,7 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_x3_kernel(WgradParams p) 
     }
     __syncthreads();  // every wave is done with this tile's LDS image
     if (has_next) {
-      commit(tile + t_step);
+      commit(tile + walk.step);
       __syncthreads();
     }
   }

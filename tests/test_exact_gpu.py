@@ -220,6 +220,24 @@ def test_fp32_conv_every_form_and_option(select, B, H, W):
     assert not fails, "\n".join(fails)
 
 
+# The shapes at which the shared tile map, tile walk and fp32 halo staging (csrc/conv_tiles.h) take each branch:
+#   (3, 8, 64)     12 full 4 x 32 tiles, a workgroup count that is no multiple of 8: the round-robin walk
+#   (2, 7, 45)     ragged in both directions
+#   (3, 100, 250)  600 tiles on 512 workgroups: the per-XCD walk (75 tiles per XCD, step 64), one or two tiles per workgroup
+#   (1, 6, 64)     the tile's second strip is partly outside the image
+# (tests/test_conv_w4_epilogue_gpu.py runs the Winograd kernel at the same four.)
+WALK = [(3, 8, 64), (2, 7, 45), (3, 100, 250), (1, 6, 64)]
+
+
+@pytest.mark.parametrize("B,H,W", WALK)
+def test_fp32_persistent_conv_tile_walk(B, H, W):
+    """conv3x3_c64_p4_kernel (select 7), every form and option, at the WALK shapes"""
+    D = ConvData(B, H, W, seed=150 + B + H + W)
+    packs = ops.pack_pair(D.dev["w"])
+    fails = [f for f in (check_conv_case(n, D, packs, 7) for n in CASES) if f]
+    assert not fails, "\n".join(fails)
+
+
 @pytest.mark.parametrize("B", [7, 8, 9])
 def test_fp32_conv_selection_thresholds(B):
     """persistent form: nblk = ceil(H/4)*ceil(W/32)*B >= 1024 (B = 7: 896 per-tile, 8: 1024, 9: 1152 = a ragged last round
@@ -384,6 +402,30 @@ def test_fp32_wgrad_multi_pair(form, cin, cout, B, H, W):
     X.assert_exact(db, db_ref, "db")
 
 
+@pytest.mark.parametrize("B,H,W", WALK + [(3, 150, 300)])
+def test_fp32_wgrad_tile_walk(B, H, W):
+    """the default form at the WALK shapes: (3, 100, 250) is 312 tiles of 8 x 32 on 256 workgroups (dense kernel, per-XCD
+    walk, a ragged last eighth), the others the quadrant kernel; (3, 150, 300) is more than 8 x 128^2 pixels: the Winograd
+    form, 570 tiles on 256 workgroups, ragged both ways.  Plain and dy_scale / dy_shift."""
+    x, dy = X.ints((B, 64, H, W), 420 + B), X.ints((B, 64, H, W), 421 + H)
+    sc, sh = X.scales((B, 64), 422), X.shifts((B, 64), 423)
+    for kw, opts in ((dict(), dict()), (dict(sc=sc, sh=sh), dict(dy_scale=sc.to(DEV), dy_shift=sh.to(DEV)))):
+        dw_ref, db_ref, _ = wgrad_exact(x, dy, **kw)
+        dw, db = run_wgrad(dev4(x), dev4(dy), B, H, W, **opts)
+        X.assert_exact(dw, dw_ref, f"dw {list(opts)}")
+        X.assert_exact(db, db_ref, f"db {list(opts)}")
+
+
+def test_fp32_wgrad_winograd_round_robin_walk():
+    """128 -> 192 (six chunk pairs: a K-split of 42 workgroups, no multiple of 8) above the Winograd threshold"""
+    B, H, W, cin, cout = 3, 150, 300, 128, 192
+    x, dy = X.ints((B, cin, H, W), 430, lo=-1, hi=1), X.ints((B, cout, H, W), 431, lo=-1, hi=1)
+    dw_ref, db_ref, _ = wgrad_exact(x, dy)
+    dw, db = run_wgrad(dev4(x), dev4(dy), B, H, W, cin, cout)
+    X.assert_exact(dw, dw_ref, "dw")
+    X.assert_exact(db, db_ref, "db")
+
+
 @pytest.mark.parametrize("cin,cout,units", [(64, 64, 0b0110), (64, 64, 0b1001), (64, 128, 0xC3), (128, 64, 0x3F),
                                             (128, 128, 0x9669)])
 def test_fp32_wgrad_active_units(cin, cout, units):
@@ -528,6 +570,18 @@ def test_bf16_conv_forms(mode, select, B, H, W):
     assert not fails, "\n".join(fails)
 
 
+@pytest.mark.parametrize("B,H,W", WALK)
+@pytest.mark.parametrize("mode,select", [("bf16", 1), ("bf16x3", 0)])
+def test_bf16_per_tile_conv_tile_walk(mode, select, B, H, W):
+    """the per-tile bf16 and bf16x3 kernels (block map, float4 epilogue through the LDS transpose buffer) at the WALK shapes"""
+    D = ConvData(B, H, W, seed=620 + B + H)
+    with precision(mode):
+        packs = ops.pack_pair(D.dev["w"])
+        fails = [f for f in (check_conv_case(n, D, packs, select) for n in CASES + BF16_EXTRA
+                             if n not in FP32_ONLY and n not in BF16_REFUSED) if f]
+    assert not fails, "\n".join(fails)
+
+
 @pytest.mark.parametrize("B,H,W", [(1, 13, 9), (2, 16, 40), (9, 128, 128)])
 def test_bf16_storage_conv_codes(B, H, W):
     """sisr_conv3x3_c64_bf16s, storage bits 1 = x / gate_add / gate_out, 2 = y, 4 = mask / dot, 8 = res bf16 maps: the codes
@@ -600,6 +654,20 @@ def test_bf16_wgrad_forms(mode, storage, B, H, W):
             dw, db = run_wgrad(xin, dyin, B, H, W, storage=storage, **opts)
             X.assert_exact(dw, dw_ref, f"{mode} storage {storage} dw")
             X.assert_exact(db, db_ref, f"{mode} storage {storage} db")
+
+
+@pytest.mark.parametrize("B,H,W", WALK)
+@pytest.mark.parametrize("mode", ["bf16", "bf16x3"])
+def test_bf16_wgrad_tile_walk(mode, B, H, W):
+    """the persistent bf16 and bf16x3 weight-gradient kernels at the WALK shapes, plain and dy_scale / dy_shift"""
+    x, dy = X.ints((B, 64, H, W), 710 + B), X.ints((B, 64, H, W), 711 + H)
+    sc, sh = X.scales((B, 64), 712), X.shifts((B, 64), 713)
+    with precision(mode):
+        for kw, opts in ((dict(), dict()), (dict(sc=sc, sh=sh), dict(dy_scale=sc.to(DEV), dy_shift=sh.to(DEV)))):
+            dw_ref, db_ref, _ = wgrad_exact(x, dy, **kw)
+            dw, db = run_wgrad(dev4(x), dev4(dy), B, H, W, **opts)
+            X.assert_exact(dw, dw_ref, f"{mode} dw {list(opts)}")
+            X.assert_exact(db, db_ref, f"{mode} db {list(opts)}")
 
 
 @pytest.mark.parametrize("mode,B", [("bf16", 8), ("bf16", 2), ("bf16x3", 2)])
