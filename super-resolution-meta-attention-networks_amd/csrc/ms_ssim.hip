@@ -14,24 +14,25 @@
 //
 // Gradient.  For cs = A2 / B2 the coefficients of the differential are
 //   beta = d cs / d Exx = -cs / B2,  gamma = d cs / d Exy = 2 / B2,  alpha = d cs / d mx = -my gamma - 2 mx beta
-// (sl_pixel's alpha without its two luminance terms); at the last scale they are sl_pixel's.  With
+// (SlSsim::pixel's alpha without its two luminance terms); at the last scale they are SlSsim::pixel's.  With
 //   g_j = G^T alpha + 2 x_j G^T beta + y_j G^T gamma            (x_j, y_j: the planes at scale j)
 //   f_j = w_j MS / (c_j windows_j planes)                        (per plane; 0 when the plane's value is 0)
 // the gradient at scale j is D_j = f_j g_j + (1/4) D_{j+1}[parent pixel], the second term absent at the last scale and on
 // the pixels of a dropped row or column; D_0, rounded to fp32, is the result.
 //
-// Launches, 3 M + 1 for M scales with `value` and a gradient (16 for five; the M of ms_grad_kernel fewer without a
-// gradient: 2 M + 1; one fewer, ms_value_kernel, without `value`: 3 M and 2 M), none depending on the batch:
+// Entry points sisr_ms_ssim (planes as given -> per-plane float64 values, the fp32 mean, the fp32 gradient) and
+// sisr_luma_clip (clipped RGB -> Y planes, for the metric).  Launches of sisr_ms_ssim, 3 M + 1 for M scales with `value` and
+// a gradient (16 for five; the M of sl_grad_kernel fewer without a gradient: 2 M + 1; one fewer, sl_finish_kernel, without
+// `value`: 3 M and 2 M), none depending on the batch; the sl_* kernels are those of csrc/ssim_window.h:
 //   ms_pool_kernel   x (M - 1)   scale j -> j + 1 of both operands, float64 (the sum of four floats is exact there)
-//   ms_fwd_kernel    x M         the shape of ssim_loss_fwd_kernel: one wave per tile of 64 x 32 windows, rows staged in LDS,
-//                                five 11-slot float64 rings; the tile's sum of cs or S and, with a gradient, alpha, beta, gamma
+//   sl_fwd_kernel    x M         LOAD = SlPlane<float> at scale 0, SlPlane<double> above; PIXEL = MsContrastStructure, SlSsim
+//                                at the last scale; the tile's sum of cs or S and, with a gradient, alpha, beta, gamma
 //   ms_plane_kernel  x 1         one wave per plane: the tile sums of every scale added in a fixed order, c_j, MS (pow in
 //                                float64) and the factors f_j
-//   ms_value_kernel  x 1         (with `value`) the planes' MS added in a fixed order, divided by the plane count, rounded
+//   sl_finish_kernel x 1         (with `value`) the planes' MS added in a fixed order, divided by the plane count, rounded
 //                                to fp32 once
-//   ms_grad_kernel   x M         coarsest scale first, the shape of ssim_loss_grad_kernel: one wave per tile of 64 x 32 pixels;
-//                                scaled by f_j, a quarter of the parent pixel of D_{j+1} added, D_j stored in float64 (j >= 1)
-//                                or the result in fp32 (j = 0)
+//   sl_grad_kernel   x M         coarsest scale first; SCALE = MsPlaneFactor: scaled by f_j, a quarter of the parent pixel
+//                                of D_{j+1} added (PARENT), D_j stored in float64 (j >= 1) or the result in fp32 (j = 0)
 // No atomics: a repeat call is bit-identical.  No allocation, no host synchronisation.  Everything between the fp32 inputs
 // and the two fp32 roundings of the outputs is float64, in registers and in memory.
 #include "sisr_common.h"
@@ -48,23 +49,32 @@ struct MsPlan {
   double weight[MS_MAX_LEVELS];
 };
 
-// cs = A2 / B2 (or S at the last scale) in the operation order of sl_pixel, with the coefficients of its differential
-template <bool LAST, bool GRAD>
-__device__ __forceinline__ double ms_pixel(double mx, double my, double mxx, double myy, double mxy, double c1, double c2,
-                                           double& alpha, double& beta, double& gamma) {
+// the per-window quantity of every scale but the last: cs = A2 / B2 in the operation order of SlSsim::pixel, with the
+// coefficients of its differential
+struct MsContrastStructure {
+  template <bool GRAD>
+  static __device__ __forceinline__ double pixel(double mx, double my, double mxx, double myy, double mxy, double c1,
+                                                 double c2, double& alpha, double& beta, double& gamma) {
 #pragma clang fp contract(off)
-  if (LAST) return sl_pixel<GRAD>(mx, my, mxx, myy, mxy, c1, c2, alpha, beta, gamma);
-  const double vx = mxx - mx * mx, vy = myy - my * my, vxy = mxy - mx * my;
-  const double a2 = 2.0 * vxy + c2;
-  const double b2 = vx + vy + c2;
-  const double cs = a2 / b2;
-  if (GRAD) {
-    beta = -cs / b2;
-    gamma = 2.0 / b2;
-    alpha = -my * gamma - 2.0 * mx * beta;
+    const double vx = mxx - mx * mx, vy = myy - my * my, vxy = mxy - mx * my;
+    const double a2 = 2.0 * vxy + c2;
+    const double b2 = vx + vy + c2;
+    const double cs = a2 / b2;
+    if (GRAD) {
+      beta = -cs / b2;
+      gamma = 2.0 / b2;
+      alpha = -my * gamma - 2.0 * mx * beta;
+    }
+    return cs;
   }
-  return cs;
-}
+};
+
+// the last step of the gradient at one scale: times the plane's factor f_j (`factor` points at [0][j] of [planes][8])
+struct MsPlaneFactor {
+  const double* factor;
+  __device__ __forceinline__ double of(int plane) const { return factor[(long)plane * MS_MAX_LEVELS]; }
+  static __device__ __forceinline__ double apply(double f, double g) { return f * g; }
+};
 
 // scale j -> j + 1 of both operands: out[r][c] = mean of in[2r .. 2r + 1][2c .. 2c + 1]; ho = h / 2, wo = w / 2
 template <typename T>
@@ -80,108 +90,6 @@ __global__ __launch_bounds__(256) void ms_pool_kernel(const T* __restrict__ xin,
     xout[i] = ((((double)xin[s] + (double)xin[s + 1]) + (double)xin[s + w]) + (double)xin[s + w + 1]) * 0.25;
     yout[i] = ((((double)yin[s] + (double)yin[s + 1]) + (double)yin[s + w]) + (double)yin[s + w + 1]) * 0.25;
   }
-}
-
-// ssim_loss_fwd_kernel on planes of T (float at scale 0, double above), with cs in place of S unless LAST
-template <typename T, bool LAST, bool GRAD>
-__global__ __launch_bounds__(64) void ms_fwd_kernel(const T* __restrict__ a, const T* __restrict__ b, int h, int w,
-                                                    int tiles_x, int tiles_per_plane, double c1, double c2, SsimLossTaps tp,
-                                                    double* __restrict__ part, double* __restrict__ ma,
-                                                    double* __restrict__ mb, double* __restrict__ mg) {
-  __shared__ T sx[2][SL_SW], sy[2][SL_SW];
-  const int plane_i = blockIdx.x / tiles_per_plane, t = blockIdx.x - plane_i * tiles_per_plane;
-  const int ty = t / tiles_x, tx = t - ty * tiles_x;
-  const int lane = threadIdx.x;
-  const int c0 = tx * SL_TW, r0 = ty * SL_TH;
-  const int hw = h - 2 * SL_R, ww = w - 2 * SL_R;              // the window grid
-  const int n_in = min(SL_TH, hw - r0) + 2 * SL_R;             // input rows r0 .. r0 + n_in - 1, all < h
-  const T* pa = a + (long)plane_i * h * w;
-  const T* pb = b + (long)plane_i * h * w;
-  // staged columns: c0 + lane, and c0 + 64 + lane on the first 10 lanes; clamped into the image on a right-edge tile,
-  // where those values only reach windows that are not output
-  const long col0 = min(c0 + lane, w - 1), col1 = min(c0 + SL_TW + lane, w - 1);
-  const bool halo = lane < 2 * SL_R;
-  const bool out_col = c0 + lane < ww;
-  const long mbase = (long)plane_i * hw * ww + c0 + lane;      // + row * ww: this lane's window in the maps
-
-  long off = (long)r0 * w;
-  T x0 = pa[off + col0], y0 = pb[off + col0];
-  T x1 = 0, y1 = 0;
-  if (halo) {
-    x1 = pa[off + col1];
-    y1 = pb[off + col1];
-  }
-
-  double rx[SL_K], ry[SL_K], rxx[SL_K], ryy[SL_K], rxy[SL_K];  // horizontal sums of the last 11 rows
-  double acc = 0.0;
-  for (int i0 = 0; i0 < n_in; i0 += SL_K) {
-#pragma unroll
-    for (int j = 0; j < SL_K; ++j) {  // input row i = i0 + j sits in ring slot j
-      const int i = i0 + j;
-      if (i < n_in) {
-        T* bx = sx[i & 1];
-        T* by = sy[i & 1];
-        bx[lane] = x0;
-        by[lane] = y0;
-        if (halo) {
-          bx[SL_TW + lane] = x1;
-          by[SL_TW + lane] = y1;
-        }
-        __syncthreads();
-        if (i + 1 < n_in) {  // the next row's loads fly while this one is filtered
-          off += w;
-          x0 = pa[off + col0];
-          y0 = pb[off + col0];
-          if (halo) {
-            x1 = pa[off + col1];
-            y1 = pb[off + col1];
-          }
-        }
-        double hx = 0.0, hy = 0.0, hxx = 0.0, hyy = 0.0, hxy = 0.0;
-#pragma unroll
-        for (int k = 0; k < SL_K; ++k) {
-          const double xv = (double)bx[lane + k], yv = (double)by[lane + k];
-          const double wx = tp.w[k] * xv, wy = tp.w[k] * yv;
-          hx += wx;
-          hy += wy;
-          hxx += wx * xv;
-          hyy += wy * yv;
-          hxy += wx * yv;
-        }
-        rx[j] = hx;
-        ry[j] = hy;
-        rxx[j] = hxx;
-        ryy[j] = hyy;
-        rxy[j] = hxy;
-        if (i >= 2 * SL_R) {  // window row r0 + i - 10: input rows i - 10 .. i are ring slots (j + 1 + k) % 11
-          double mx = 0.0, my = 0.0, mxx = 0.0, myy = 0.0, mxy = 0.0;
-#pragma unroll
-          for (int k = 0; k < SL_K; ++k) {
-            const int s = (j + 1 + k) % SL_K;
-            mx += tp.w[k] * rx[s];
-            my += tp.w[k] * ry[s];
-            mxx += tp.w[k] * rxx[s];
-            myy += tp.w[k] * ryy[s];
-            mxy += tp.w[k] * rxy[s];
-          }
-          double al = 0.0, be = 0.0, ga = 0.0;
-          const double s = ms_pixel<LAST, GRAD>(mx, my, mxx, myy, mxy, c1, c2, al, be, ga);
-          if (out_col) {
-            acc += s;
-            if (GRAD) {
-              const long m = mbase + (long)(r0 + i - 2 * SL_R) * ww;  // row < hw by n_in, column < ww by out_col
-              ma[m] = al;
-              mb[m] = be;
-              mg[m] = ga;
-            }
-          }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-  if (lane == 0) part[blockIdx.x] = acc;
 }
 
 // One wave per plane: c_j = (tile sums of scale j, in a fixed order) / windows_j; MS = prod c_j^{w_j}, or 0 when a c_j <= 0;
@@ -219,141 +127,12 @@ __global__ __launch_bounds__(64) void ms_plane_kernel(const double* __restrict__
       factor[(long)p * MS_MAX_LEVELS + j] = dead ? 0.0 : pl.weight[j] * ms / (c[j] * pl.windows[j] * (double)planes);
 }
 
-// value = (sum of the planes' MS, in a fixed order) / planes, rounded to fp32 once
-__global__ __launch_bounds__(256) void ms_value_kernel(const double* __restrict__ per_plane, int planes,
-                                                       float* __restrict__ value) {
-  __shared__ double red[256];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < planes; i += 256) s += per_plane[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) value[0] = (float)(red[0] / (double)planes);
-}
-
-// ssim_loss_grad_kernel on planes of T: the pixel gradient of this scale's mean times the plane's factor, plus a quarter of
-// the parent pixel of the next coarser scale's gradient (hp x wp; pixels of a dropped odd row or column have no parent)
-template <typename T, typename O, bool PARENT>
-__global__ __launch_bounds__(64) void ms_grad_kernel(const T* __restrict__ a, const T* __restrict__ b, int h, int w,
-                                                     int tiles_x, int tiles_per_plane, const double* __restrict__ factor,
-                                                     SsimLossTaps tp, const double* __restrict__ ma,
-                                                     const double* __restrict__ mb, const double* __restrict__ mg,
-                                                     const double* __restrict__ parent, int hp, int wp,
-                                                     O* __restrict__ grad) {
-  __shared__ double sa[2][SL_SW], sb[2][SL_SW], sg[2][SL_SW];
-  const int plane_i = blockIdx.x / tiles_per_plane, t = blockIdx.x - plane_i * tiles_per_plane;
-  const int ty = t / tiles_x, tx = t - ty * tiles_x;
-  const int lane = threadIdx.x;
-  const int c0 = tx * SL_TW, r0 = ty * SL_TH;
-  const int hw = h - 2 * SL_R, ww = w - 2 * SL_R;
-  const int n_out = min(SL_TH, h - r0);   // pixel rows r0 .. r0 + n_out - 1
-  const int n_in = n_out + 2 * SL_R;      // window rows r0 - 10 .. r0 + n_out - 1, those outside [0, hw) read as zero
-  const long wbase = (long)plane_i * hw * ww;
-  // staged window columns: c0 - 10 + lane, and c0 + 54 + lane on the first 10 lanes.  The address is clamped into the
-  // row and the value replaced by zero where the column is outside the window grid.
-  const int wc0 = c0 - 2 * SL_R + lane, wc1 = c0 + SL_TW - 2 * SL_R + lane;
-  const bool in0 = wc0 >= 0 && wc0 < ww, in1 = wc1 < ww;  // wc1 >= 54
-  const long cc0 = min(max(wc0, 0), ww - 1), cc1 = min(wc1, ww - 1);
-  const bool halo = lane < 2 * SL_R;
-  const bool out_col = c0 + lane < w;
-  const long pcol = min(c0 + lane, w - 1);
-  const T* pa = a + (long)plane_i * h * w;
-  const T* pb = b + (long)plane_i * h * w;
-  O* pg = grad + (long)plane_i * h * w;
-  const double f = factor[(long)plane_i * MS_MAX_LEVELS];
-  // the parent's column; in range where has_parent
-  const bool has_parent = PARENT && out_col && (int)(pcol >> 1) < wp;
-  const double* pp = PARENT ? parent + (long)plane_i * hp * wp + (has_parent ? (pcol >> 1) : 0) : nullptr;
-
-  double a0 = 0.0, b0 = 0.0, g0 = 0.0, a1 = 0.0, b1 = 0.0, g1 = 0.0;
-  auto fetch = [&](int ii) {  // window row r0 - 10 + ii into the six registers
-    const int wr = r0 - 2 * SL_R + ii;
-    const bool row_ok = wr >= 0 && wr < hw;
-    const long ro = wbase + (long)min(max(wr, 0), hw - 1) * ww;
-    const bool k0 = row_ok && in0, k1 = row_ok && in1;
-    const double ta = ma[ro + cc0], tb = mb[ro + cc0], tg = mg[ro + cc0];
-    a0 = k0 ? ta : 0.0;
-    b0 = k0 ? tb : 0.0;
-    g0 = k0 ? tg : 0.0;
-    if (halo) {
-      const double ua = ma[ro + cc1], ub = mb[ro + cc1], ug = mg[ro + cc1];
-      a1 = k1 ? ua : 0.0;
-      b1 = k1 ? ub : 0.0;
-      g1 = k1 ? ug : 0.0;
-    }
-  };
-  fetch(0);
-
-  double ra[SL_K], rb[SL_K], rg[SL_K];  // horizontal sums of the last 11 window rows
-  for (int i0 = 0; i0 < n_in; i0 += SL_K) {
-#pragma unroll
-    for (int j = 0; j < SL_K; ++j) {  // window row ii = i0 + j sits in ring slot j
-      const int ii = i0 + j;
-      if (ii < n_in) {
-        double* ba = sa[ii & 1];
-        double* bb = sb[ii & 1];
-        double* bg = sg[ii & 1];
-        ba[lane] = a0;
-        bb[lane] = b0;
-        bg[lane] = g0;
-        if (halo) {
-          ba[SL_TW + lane] = a1;
-          bb[SL_TW + lane] = b1;
-          bg[SL_TW + lane] = g1;
-        }
-        __syncthreads();
-        if (ii + 1 < n_in) fetch(ii + 1);  // the next row's loads fly while this one is filtered
-        // pixel column c = c0 + lane collects window columns c - 10 .. c = staged slots lane .. lane + 10, tap c - j = 10 - k
-        double ha = 0.0, hb = 0.0, hg = 0.0;
-#pragma unroll
-        for (int k = 0; k < SL_K; ++k) {
-          const double wk = tp.w[SL_K - 1 - k];
-          ha += wk * ba[lane + k];
-          hb += wk * bb[lane + k];
-          hg += wk * bg[lane + k];
-        }
-        ra[j] = ha;
-        rb[j] = hb;
-        rg[j] = hg;
-        if (ii >= 2 * SL_R) {  // pixel row r = r0 + ii - 10: window rows r - 10 .. r are ring slots (j + 1 + k) % 11, tap 10 - k
-          double va = 0.0, vb = 0.0, vg = 0.0;
-#pragma unroll
-          for (int k = 0; k < SL_K; ++k) {
-            const int s = (j + 1 + k) % SL_K;
-            const double wk = tp.w[SL_K - 1 - k];
-            va += wk * ra[s];
-            vb += wk * rb[s];
-            vg += wk * rg[s];
-          }
-          const int r = r0 + ii - 2 * SL_R;  // < h by n_out
-          const long p = (long)r * w + pcol;
-          const double xv = (double)pa[p], yv = (double)pb[p];
-          double d = f * (va + 2.0 * xv * vb + yv * vg);
-          if (PARENT) {
-            if (has_parent && (r >> 1) < hp) d += 0.25 * pp[(long)(r >> 1) * wp];
-          }
-          if (out_col) pg[p] = (O)d;
-        }
-      }
-    }
-  }
-}
-
-// Y of the clipped RGB pixel in fp32, in the operation order of sisr_ssim: (0.299 R + 0.587 G) + 0.114 B after np.clip(v, 0, 1)
+// the Y planes that sisr_ssim stages on the way into LDS, written out: y[n][q] = sl_clip_luma of pixel q of RGB image n
 __global__ __launch_bounds__(256) void ms_luma_kernel(const float* __restrict__ rgb, long plane, long total,
                                                       float* __restrict__ y) {
-#pragma clang fp contract(off)
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const long n = i / plane, q = i - n * plane;
-    const float* p = rgb + n * 3 * plane + q;
-    float r = p[0], g = p[plane], b = p[2 * plane];
-    r = r < 0.f ? 0.f : (r > 1.f ? 1.f : r);
-    g = g < 0.f ? 0.f : (g > 1.f ? 1.f : g);
-    b = b < 0.f ? 0.f : (b > 1.f ? 1.f : b);
-    y[i] = (0.299f * r + 0.587f * g) + 0.114f * b;
+    y[i] = SlClippedLuma::load(rgb + n * 3 * plane, plane, q);
   }
 }
 
@@ -416,29 +195,17 @@ extern "C" size_t sisr_ms_ssim_workspace_bytes(int planes, int h, int w, int lev
   return ms_layout(planes, h, w, levels, want_grad != 0).total;
 }
 
-template <typename T, bool LAST>
-static void ms_launch_fwd(bool want_grad, unsigned blocks, hipStream_t s, const T* a, const T* b, int h, int w, double c1,
-                          double c2, const SsimLossTaps& tp, double* part, double* ma, double* mb, double* mg) {
-  const int tx = (int)sl_win_tiles_x(w), wt = (int)sl_win_tiles(h, w);
-  if (want_grad)
-    hipLaunchKernelGGL((ms_fwd_kernel<T, LAST, true>), dim3(blocks), dim3(64), 0, s, a, b, h, w, tx, wt, c1, c2, tp, part, ma,
-                       mb, mg);
-  else
-    hipLaunchKernelGGL((ms_fwd_kernel<T, LAST, false>), dim3(blocks), dim3(64), 0, s, a, b, h, w, tx, wt, c1, c2, tp, part,
-                       (double*)nullptr, (double*)nullptr, (double*)nullptr);
-}
-
 template <typename T, typename O>
 static void ms_launch_grad(bool has_parent, unsigned blocks, hipStream_t s, const T* a, const T* b, int h, int w,
                            const double* factor, const SsimLossTaps& tp, const double* ma, const double* mb,
                            const double* mg, const double* parent, O* out) {
   const int tx = (int)sl_pix_tiles_x(w), pt = (int)sl_pix_tiles(h, w);
   if (has_parent)
-    hipLaunchKernelGGL((ms_grad_kernel<T, O, true>), dim3(blocks), dim3(64), 0, s, a, b, h, w, tx, pt, factor, tp, ma, mb, mg,
-                       parent, h >> 1, w >> 1, out);
+    hipLaunchKernelGGL((sl_grad_kernel<T, O, MsPlaneFactor, true>), dim3(blocks), dim3(64), 0, s, a, b, h, w, tx, pt,
+                       MsPlaneFactor{factor}, tp, ma, mb, mg, parent, h >> 1, w >> 1, out);
   else
-    hipLaunchKernelGGL((ms_grad_kernel<T, O, false>), dim3(blocks), dim3(64), 0, s, a, b, h, w, tx, pt, factor, tp, ma, mb, mg,
-                       (const double*)nullptr, 0, 0, out);
+    hipLaunchKernelGGL((sl_grad_kernel<T, O, MsPlaneFactor, false>), dim3(blocks), dim3(64), 0, s, a, b, h, w, tx, pt,
+                       MsPlaneFactor{factor}, tp, ma, mb, mg, (const double*)nullptr, 0, 0, out);
 }
 
 extern "C" int sisr_ms_ssim(const float* sr, const float* y, int planes, int h, int w, double data_range,
@@ -495,11 +262,11 @@ extern "C" int sisr_ms_ssim(const float* sr, const float* y, int planes, int h, 
     const double* xj = px + l.pyr_off[j];
     const double* yj = py + l.pyr_off[j];
     if (j == 0) {
-      if (last) ms_launch_fwd<float, true>(want_grad, blocks, s, sr, y, hj, wj, c1, c2, tp, pj, ma, mb, mg);
-      else ms_launch_fwd<float, false>(want_grad, blocks, s, sr, y, hj, wj, c1, c2, tp, pj, ma, mb, mg);
+      if (last) sl_launch_fwd<float, SlSsim>(want_grad, blocks, s, sr, y, hj, wj, c1, c2, tp, pj, ma, mb, mg);
+      else sl_launch_fwd<float, MsContrastStructure>(want_grad, blocks, s, sr, y, hj, wj, c1, c2, tp, pj, ma, mb, mg);
     } else {
-      if (last) ms_launch_fwd<double, true>(want_grad, blocks, s, xj, yj, hj, wj, c1, c2, tp, pj, ma, mb, mg);
-      else ms_launch_fwd<double, false>(want_grad, blocks, s, xj, yj, hj, wj, c1, c2, tp, pj, ma, mb, mg);
+      if (last) sl_launch_fwd<double, SlSsim>(want_grad, blocks, s, xj, yj, hj, wj, c1, c2, tp, pj, ma, mb, mg);
+      else sl_launch_fwd<double, MsContrastStructure>(want_grad, blocks, s, xj, yj, hj, wj, c1, c2, tp, pj, ma, mb, mg);
     }
     if ((rc = sisr_check_launch())) return rc;
     if (!last) {  // the next scale of both operands
@@ -518,7 +285,7 @@ extern "C" int sisr_ms_ssim(const float* sr, const float* y, int planes, int h, 
   hipLaunchKernelGGL(ms_plane_kernel, dim3((unsigned)planes), dim3(64), 0, s, part, pl, planes, pplane, factor);
   if ((rc = sisr_check_launch())) return rc;
   if (value) {
-    hipLaunchKernelGGL(ms_value_kernel, dim3(1), dim3(256), 0, s, pplane, planes, value);
+    hipLaunchKernelGGL(sl_finish_kernel<float>, dim3(1), dim3(256), 0, s, pplane, (long)planes, (double)planes, value);
     if ((rc = sisr_check_launch())) return rc;
   }
   if (!want_grad) return SISR_OK;

@@ -189,24 +189,34 @@ def y_ssim(sr, hr, max_value=1):
     return ssim(a, b, max_value=max_value)
 
 
-def batch_ssim(sr, hr, max_value=1):
-    """Per-image SSIM of two (N, C, H, W) batches -> list of N floats.  C == 3: clipped RGB compared on Y (as y_ssim);
-    C == 1: Y planes used as given.  If either batch is a tensor on a HIP device, both go to the device kernel (sisr_ssim,
-    fp32 contiguous copies made here); anything else takes the host float64 form."""
+def _batch_pair(name, sr, hr):
+    """The front half of batch_ssim / batch_ms_ssim: two (N, 1|3, H, W) batches of one shape -> (device, a, b).  If either is a
+    tensor on a HIP device, both as fp32 contiguous tensors on it; otherwise device None and numpy arrays whose plane 0 is Y
+    (C == 3: of the clipped RGB, batch_rgb_to_ycbcr)."""
     import torch
     dev = next((t.device for t in (sr, hr) if isinstance(t, torch.Tensor) and t.is_cuda), None)
     if dev is None:
         a, b = (t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in (sr, hr))
         if a.ndim != 4 or a.shape != b.shape or a.shape[1] not in (1, 3):
-            raise ValueError(f"batch_ssim takes two (N, 1|3, H, W) batches of one shape; got {a.shape} and {b.shape}")
+            raise ValueError(f"{name} takes two (N, 1|3, H, W) batches of one shape; got {a.shape} and {b.shape}")
         if a.shape[1] == 3:
             a, b = batch_rgb_to_ycbcr(a), batch_rgb_to_ycbcr(b)
-        return [ssim(a[i, 0], b[i, 0], max_value=max_value) for i in range(a.shape[0])]
-    from . import hip
+        return None, a, b
     a, b = (torch.as_tensor(t).to(device=dev, dtype=torch.float32).contiguous() for t in (sr, hr))
     if a.dim() != 4 or a.shape != b.shape or a.shape[1] not in (1, 3):
-        raise ValueError(f"batch_ssim takes two (N, 1|3, H, W) batches of one shape; got {tuple(a.shape)} and "
-                         f"{tuple(b.shape)}")
+        raise ValueError(f"{name} takes two (N, 1|3, H, W) batches of one shape; got {tuple(a.shape)} and {tuple(b.shape)}")
+    return dev, a, b
+
+
+def batch_ssim(sr, hr, max_value=1):
+    """Per-image SSIM of two (N, C, H, W) batches -> list of N floats.  C == 3: clipped RGB compared on Y (as y_ssim);
+    C == 1: Y planes used as given.  If either batch is a tensor on a HIP device, both go to the device kernel (sisr_ssim,
+    fp32 contiguous copies made here); anything else takes the host float64 form."""
+    dev, a, b = _batch_pair("batch_ssim", sr, hr)
+    if dev is None:
+        return [ssim(a[i, 0], b[i, 0], max_value=max_value) for i in range(a.shape[0])]
+    import torch
+    from . import hip
     n, c, h, w = a.shape
     L = hip.lib()
     nbytes = L.sisr_ssim_workspace_bytes(n, h, w)
@@ -225,21 +235,12 @@ def batch_ms_ssim(sr, hr, max_value=1, weights=MS_SSIM_WEIGHTS):
     compared on Y, C == 1 Y planes used as given.  If either batch is a tensor on a HIP device, both go to the device
     kernels (sisr_luma_clip for C == 3, then sisr_ms_ssim's per-plane output); anything else takes the host form `ms_ssim`.
     An image with a side under 11 * 2^(len(weights) - 1) raises."""
-    import torch
-    dev = next((t.device for t in (sr, hr) if isinstance(t, torch.Tensor) and t.is_cuda), None)
+    dev, a, b = _batch_pair("batch_ms_ssim", sr, hr)
     if dev is None:
-        a, b = (t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in (sr, hr))
-        if a.ndim != 4 or a.shape != b.shape or a.shape[1] not in (1, 3):
-            raise ValueError(f"batch_ms_ssim takes two (N, 1|3, H, W) batches of one shape; got {a.shape} and {b.shape}")
-        if a.shape[1] == 3:
-            a, b = batch_rgb_to_ycbcr(a), batch_rgb_to_ycbcr(b)
         return [ms_ssim(a[i, 0], b[i, 0], max_value=max_value, weights=weights) for i in range(a.shape[0])]
     import ctypes
+    import torch
     from . import hip
-    a, b = (torch.as_tensor(t).to(device=dev, dtype=torch.float32).contiguous() for t in (sr, hr))
-    if a.dim() != 4 or a.shape != b.shape or a.shape[1] not in (1, 3):
-        raise ValueError(f"batch_ms_ssim takes two (N, 1|3, H, W) batches of one shape; got {tuple(a.shape)} and "
-                         f"{tuple(b.shape)}")
     n, c, h, w = a.shape
     weights = _ms_ssim_levels(weights, (h, w))
     if n == 0:

@@ -17,27 +17,17 @@ import torch
 from torch import nn
 from torch.autograd import Function
 
-from . import hip, ops
+from . import ops
 
 
 class _MsSsimMean(Function):
-    """the node of ops.ms_ssim_mean, modelled on ops._SsimMean: the gradient is computed in the forward call when `sr` needs
-    one (want_grad: torch.is_grad_enabled() at the call), backward returns grad * go"""
+    """the node of ops.ms_ssim_mean: ops._SsimMean bound to sisr_ms_ssim, with the scale weights and no per-plane output"""
 
     @staticmethod
     def forward(ctx, sr, y, data_range, weights, want_grad):
-        sr, y = sr.contiguous(), y.contiguous()
-        B, C, H, W = sr.shape
-        L = hip.lib()
-        value = torch.empty((), device=sr.device, dtype=torch.float32)
-        grad = torch.empty_like(sr) if want_grad and ctx.needs_input_grad[0] else None
-        nbytes = L.sisr_ms_ssim_workspace_bytes(B * C, H, W, len(weights), int(grad is not None))
-        ws = hip.workspace(sr.device, nbytes)
         wv = (ctypes.c_double * len(weights))(*weights)  # host memory, read by the call and not kept
-        hip.check(L.sisr_ms_ssim(hip.ptr(sr), hip.ptr(y), B * C, H, W, float(data_range), wv, len(weights), None,
-                                 hip.ptr(value), hip.ptr(grad), hip.ptr(ws), nbytes, hip.stream()), "sisr_ms_ssim")
-        ctx.save_for_backward(grad)
-        return value
+        return ops._value_and_grad(ctx, sr, y, data_range, want_grad, "sisr_ms_ssim", (len(weights),),
+                                   (wv, len(weights), None))
 
     @staticmethod
     def backward(ctx, go):

@@ -3487,20 +3487,28 @@ def l1_loss(a, b, rounded_once=False):
 SSIM_WINDOW = 11  # the Gaussian window's side: the smallest image side the loss term takes
 
 
+def _value_and_grad(ctx, sr, y, data_range, want_grad, entry, ws_args=(), args=()):
+    """The forward half of a node whose entry point computes the fp32 mean and, in the same call, its gradient with respect to
+    `sr` when `sr` needs one (want_grad: torch.is_grad_enabled() at the call); the gradient is saved and backward returns
+    grad * go.  `entry` names the entry point; `ws_args` go between (planes, H, W) and want_grad of its workspace query, `args`
+    between data_range and `value` of the call."""
+    sr, y = sr.contiguous(), y.contiguous()
+    B, C, H, W = sr.shape
+    L = hip.lib()
+    value = torch.empty((), device=sr.device, dtype=torch.float32)
+    grad = torch.empty_like(sr) if want_grad and ctx.needs_input_grad[0] else None
+    nbytes = getattr(L, entry + "_workspace_bytes")(B * C, H, W, *ws_args, int(grad is not None))
+    ws = hip.workspace(sr.device, nbytes)
+    hip.check(getattr(L, entry)(hip.ptr(sr), hip.ptr(y), B * C, H, W, float(data_range), *args, hip.ptr(value), hip.ptr(grad),
+                                hip.ptr(ws), nbytes, hip.stream()), entry)
+    ctx.save_for_backward(grad)
+    return value
+
+
 class _SsimMean(Function):
     @staticmethod
     def forward(ctx, sr, y, data_range, want_grad):
-        sr, y = sr.contiguous(), y.contiguous()
-        B, C, H, W = sr.shape
-        L = hip.lib()
-        value = torch.empty((), device=sr.device, dtype=torch.float32)
-        grad = torch.empty_like(sr) if want_grad and ctx.needs_input_grad[0] else None
-        nbytes = L.sisr_ssim_loss_workspace_bytes(B * C, H, W, int(grad is not None))
-        ws = hip.workspace(sr.device, nbytes)
-        hip.check(L.sisr_ssim_loss(hip.ptr(sr), hip.ptr(y), B * C, H, W, float(data_range), hip.ptr(value), hip.ptr(grad),
-                                   hip.ptr(ws), nbytes, hip.stream()), "sisr_ssim_loss")
-        ctx.save_for_backward(grad)
-        return value
+        return _value_and_grad(ctx, sr, y, data_range, want_grad, "sisr_ssim_loss")
 
     @staticmethod
     def backward(ctx, go):
@@ -3508,20 +3516,31 @@ class _SsimMean(Function):
         return grad * go, None, None, None
 
 
+def _ssim_operands(name, sr, y, sized):
+    """The operand checks of ssim_mean and ms_ssim_mean, in their order: two 4-D batches of one shape, the form's own size
+    check `sized(hw)` (whose result is returned), a batch that is not empty, fp32 tensors on a device, a target that takes no
+    gradient."""
+    if sr.dim() != 4 or sr.shape != y.shape:
+        raise RuntimeError(f"{name} takes two (B, C, H, W) batches of one shape; got {tuple(sr.shape)} and {tuple(y.shape)}")
+    out = sized(sr.shape[2:])
+    if sr.numel() == 0:
+        raise RuntimeError(f"{name}: empty batch {tuple(sr.shape)}")
+    hip.ptr(sr), hip.ptr(y)  # raises on CPU or non-fp32 tensors: there is no CPU path
+    if y.requires_grad:
+        raise RuntimeError(f"{name}: the target takes no gradient; detach it")
+    return out
+
+
 def ssim_mean(sr, y, data_range=1.0):
     """Mean SSIM over all (H - 10) x (W - 10) windows of all B * C planes of two (B, C, H, W) fp32 batches: Gaussian window
     (11 taps, sigma 1.5), population covariance, every plane as given (no clipping, no Y conversion), float64 statistics, the
     value rounded to fp32 once.  The gradient goes to `sr` only and is computed with the value."""
-    if sr.dim() != 4 or sr.shape != y.shape:
-        raise RuntimeError(f"ssim_mean takes two (B, C, H, W) batches of one shape; got {tuple(sr.shape)} and {tuple(y.shape)}")
-    if min(sr.shape[2:]) < SSIM_WINDOW:
-        raise ValueError(f"ssim_mean: the {SSIM_WINDOW} x {SSIM_WINDOW} window exceeds the image extent {tuple(sr.shape[2:])}; "
-                         f"both sides must be at least {SSIM_WINDOW}")
-    if sr.numel() == 0:
-        raise RuntimeError(f"ssim_mean: empty batch {tuple(sr.shape)}")
-    hip.ptr(sr), hip.ptr(y)  # raises on CPU or non-fp32 tensors: there is no CPU path
-    if y.requires_grad:
-        raise RuntimeError("ssim_mean: the target takes no gradient; detach it")
+    def sized(hw):
+        if min(hw) < SSIM_WINDOW:
+            raise ValueError(f"ssim_mean: the {SSIM_WINDOW} x {SSIM_WINDOW} window exceeds the image extent {tuple(hw)}; "
+                             f"both sides must be at least {SSIM_WINDOW}")
+
+    _ssim_operands("ssim_mean", sr, y, sized)
     # needs_input_grad is set under no_grad as well (run_eval(request_loss=True)): the gradient launch and its maps are skipped there
     return _SsimMean.apply(sr, y, data_range, torch.is_grad_enabled())
 
@@ -3539,16 +3558,12 @@ def ms_ssim_mean(sr, y, data_range=1.0, weights=MS_SSIM_WEIGHTS):
     window of ssim_mean on every scale, every plane as given; exactly 0 for a plane with a c_j <= 0 (whatever that scale's
     weight, 0 included).  Float64 throughout, the
     value rounded to fp32 once.  The gradient goes to `sr` only and is computed with the value."""
-    if sr.dim() != 4 or sr.shape != y.shape:
-        raise RuntimeError(f"ms_ssim_mean takes two (B, C, H, W) batches of one shape; got {tuple(sr.shape)} and "
-                           f"{tuple(y.shape)}")
-    weights = ms_ssim_weights(weights)
-    ms_ssim_check_size("ms_ssim_mean", sr.shape[2:], len(weights))
-    if sr.numel() == 0:
-        raise RuntimeError(f"ms_ssim_mean: empty batch {tuple(sr.shape)}")
-    hip.ptr(sr), hip.ptr(y)  # raises on CPU or non-fp32 tensors: there is no CPU path
-    if y.requires_grad:
-        raise RuntimeError("ms_ssim_mean: the target takes no gradient; detach it")
+    def sized(hw):
+        w = ms_ssim_weights(weights)
+        ms_ssim_check_size("ms_ssim_mean", hw, len(w))
+        return w
+
+    weights = _ssim_operands("ms_ssim_mean", sr, y, sized)
     # needs_input_grad is set under no_grad as well (run_eval(request_loss=True)): the gradient launches and the maps are skipped there.
     # The node lives beside its criterion, multiscale._MsSsimMean (that module imports this one, hence the import here): it
     # has one differentiable input, no parameters and no gradient buffers of its own.

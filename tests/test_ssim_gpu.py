@@ -9,6 +9,7 @@ import torch
 
 import sisr_amd
 from _ssim_common import set5_rgb_pairs, set5_y_pairs
+from _ssim_loss import SHAPES
 from conftest import GOLDEN, golden_json
 
 M = sisr_amd.metrics
@@ -70,6 +71,26 @@ def test_rgb_inputs_are_clipped_to_the_hosts_y_bit_for_bit():
     sr[0, 1, 5, 7] = np.nan  # NaN stays NaN through the clip, as with np.clip
     out = _device_ssim(sr, hr, 1, 3)
     assert np.isnan(out[0]) and not np.isnan(out[1:]).any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hw", [s[2:] for s in SHAPES], ids=lambda hw: f"{hw[0]}x{hw[1]}")
+def test_edge_tiles_of_the_shared_window_kernel(hw):
+    """the metric runs the loss's tile kernel: the smallest shapes at which its tiling can go wrong (tests/_ssim_loss.py),
+    as Y planes and as RGB with overshoot"""
+    h, w = hw
+    g = np.random.default_rng(14 + h * w)
+    a, b = _planes(g, 2, h, w)
+    for r in (1, 255):
+        ar, br = a * np.float32(r), b * np.float32(r)
+        want = [M.ssim(ar[i, 0], br[i, 0], max_value=r) for i in range(2)]
+        np.testing.assert_allclose(_device_ssim(ar, br, r, 1), want, rtol=0, atol=1e-12)
+    sr = g.random((2, 3, h, w), dtype=np.float32) * np.float32(1.5) - np.float32(0.25)
+    hr = g.random((2, 3, h, w), dtype=np.float32)
+    ys, yh = M.batch_rgb_to_ycbcr(sr)[:, :1], M.batch_rgb_to_ycbcr(hr)[:, :1]
+    rgb = _device_ssim(sr, hr, 1, 3)
+    assert rgb.tobytes() == _device_ssim(ys, yh, 1, 1).tobytes()
+    np.testing.assert_allclose(rgb, [M.ssim(ys[i, 0], yh[i, 0]) for i in range(2)], rtol=0, atol=1e-12)
 
 
 @pytest.mark.gpu
