@@ -831,6 +831,42 @@ int sisr_normal_field(unsigned seed, float* field, unsigned* words, int C, int H
 int sisr_crop_augment_strided(const float* const* src, const int* params_host, const int* params_dev, float* dst, int B, int C,
                               int crop, void* stream);
 
+/* ---- tile-level degradation for interpolated-input and Y-channel models (csrc/interp_tiles.hip) -------------------------
+ * sisr_upsample_tiles: the c x c tiles of a batch's bicubic pre-up-sampled LR images -- per sample Pillow's
+ * `resize((w * s, h * s), BICUBIC)` of the LR bytes, ToTensor -- from the cw x cw LR WINDOW each tile depends on
+ * (sisr_degrade_tiles' uint8 output, source orientation), without the up-sampled image ever existing.  Both passes of
+ * libImaging/Resample.c's 8-bit resampler run on the whole-image tables of (h -> H) and (w -> W), indexed at the tile's
+ * absolute rows / columns, with the tap addresses taken relative to the window's origin; the horizontal rows of a 32 x 32
+ * output block stay in LDS (the block-level resampler of sisr_pil_upsample, one copy).  A tile equals the crop of
+ * sisr_pil_upsample's image through the same flips, bit for bit.  One record per sample: */
+typedef struct sisr_upsample_tile {
+  const int *bounds_h, *coef_h;              /* device tables of (w -> W): bounds [W][2], coef [W][5] */
+  const int *bounds_v, *coef_v;              /* ... and of (h -> H) */
+  int h, w;                                  /* LR image size */
+  int H, W;                                  /* size of the up-sampled image: H = s h, W = s w for one integer s >= 1 */
+  int wy, wx;                                /* the window's origin in the LR image */
+  int ty, tx;                                /* the tile's origin in the un-augmented up-sampled image (any residue mod s) */
+  int flips;                                 /* applied on the store, as sisr_degrade_tile.flips */
+  int pad;
+} sisr_upsample_tile;
+size_t sisr_upsample_tile_bytes(void);
+/* tiles_host: the B records in host memory, checked here before anything is launched; tiles_dev: their device copy, which the
+ * kernel reads; windows [B][C][cw][cw] uint8 on the device; out fp32 on the device in one of three forms:
+ *   0: RGB [B][C][c][c] (any C; a grey source, C = 1, is written as it is);  1: BT.601 'jpg' YCbCr [B][3][c][c];
+ *   2: Y alone [B][1][c][c] -- 1 and 2 with the fp32 roundings of sisr_pil_upsample's second output.
+ * One launch whatever B is, no workspace, no atomics, no state: capturable, a repeat call is bit-identical.  -1: null pointers
+ * (the records' tables included), non-positive sizes, a tile that leaves the up-sampled image, a window that leaves the LR
+ * image or does not cover every tap of the tile's rows and columns (the taps are recomputed on the host as Resample.c
+ * computes them), flips outside 0..7, form outside 0..2;  -4: ksize != 5, form 1 or 2 with C != 3, H / h != W / w or not
+ * an integer, B (or B * ceil(C / 3)) > 65535. */
+int sisr_upsample_tiles(const void* tiles_host, const void* tiles_dev, const unsigned char* windows, float* out, int ksize, int B,
+                        int C, int c, int cw, int form, void* stream);
+/* rgb [B][3][n] fp32 -> out [B][3][n] BT.601 'jpg' YCbCr, or [B][1][n] Y alone with y_only = 1: every product and sum rounded
+ * to fp32 on its own in the order data.rgb_to_ycbcr(im_type='jpg') writes them (sisr_pil_upsample's conversion, one copy), so
+ * bit-identical to it.  For the HR tiles of a 'ycbcr' batch and for LR tiles that are not up-sampled.  One launch.  -1: null
+ * pointers, rgb == out, B or n < 1, y_only other than 0 or 1;  -4: B > 65535. */
+int sisr_rgb_to_ycbcr(const float* rgb, float* out, int B, long n, int y_only, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,3 +29,10 @@ __device__ __forceinline__ int dg_clip8(int ss) {
   const int v = ss >> 22;
   return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
+
+// The store map of the tile kernels (degrade_tiles.hip, interp_tiles.hip), sisr_crop_augment's index map restricted to a c x c
+// tile: destination (i, j) in the augmented tile of source-orientation pixel (ry, rx); flips: 1 hflip, 2 vflip, 4 transpose
+__device__ __forceinline__ long dt_store_index(int ry, int rx, int c, int flips) {
+  const int a = (flips & 2) ? c - 1 - ry : ry, b = (flips & 1) ? c - 1 - rx : rx;
+  return (flips & 4) ? (long)b * c + a : (long)a * c + b;
+}

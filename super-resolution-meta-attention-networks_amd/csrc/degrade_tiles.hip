@@ -33,12 +33,6 @@ struct DegradeTile {  // sisr_degrade_tile of include/sisr_hip.h
 
 __host__ __device__ static inline int dt_up16(int n) { return (n + 15) & ~15; }
 
-// destination (i, j) in the augmented tile of source-orientation pixel (ry, rx); flips: 1 hflip, 2 vflip, 4 transpose
-__device__ __forceinline__ long dt_store_index(int ry, int rx, int c, int flips) {
-  const int a = (flips & 2) ? c - 1 - ry : ry, b = (flips & 1) ? c - 1 - rx : rx;
-  return (flips & 4) ? (long)b * c + a : (long)a * c + b;
-}
-
 template <bool TO_FLOAT>
 __global__ __launch_bounds__(DT_THREADS) void degrade_tiles_kernel(const DegradeTile* __restrict__ recs, const float* __restrict__ kernels,
                                                             void* __restrict__ outp, int C, int c, int l, int wr_cap, int wc_pitch) {

@@ -146,7 +146,9 @@ class DeviceTileSampler:
         return self.sample_pairs([(self.lr[i], self.hr[i]) for i in indices], rng)
 
     def sample_pairs(self, pairs, rng=random):
-        """The same for explicit (LR, HR) device image pairs (contiguous planar fp32, HR = scale x LR): one gather per side."""
+        """The same for explicit (LR, HR) device image pairs (contiguous planar fp32, HR = scale x LR): one gather per side.
+        Each side has the channel count of the pairs' images on that side (a Y-only LR image has one plane next to an RGB
+        HR image), not that of the resident images."""
         hip, s = self.hip, self.scale
         B = len(pairs)
         rec_lr, rec_hr = [], []
@@ -159,8 +161,11 @@ class DeviceTileSampler:
         for side, recs, c in ((0, rec_lr, self.crop), (1, rec_hr, self.crop * s)):
             ptrs = torch.tensor([p[side].data_ptr() for p in pairs], dtype=torch.int64).to(self.device)
             prm = torch.tensor(recs, dtype=torch.int32).to(self.device)
-            dst = torch.empty((B, self.channels, c, c), device=self.device, dtype=torch.float32)
-            hip.check(hip.lib().sisr_crop_augment(ptrs.data_ptr(), prm.data_ptr(), hip.ptr(dst), B, self.channels, c,
+            channels = pairs[0][side].shape[0]
+            if any(p[side].shape[0] != channels for p in pairs):
+                raise ValueError("sample_pairs: the images of one side differ in their channel count")
+            dst = torch.empty((B, channels, c, c), device=self.device, dtype=torch.float32)
+            hip.check(hip.lib().sisr_crop_augment(ptrs.data_ptr(), prm.data_ptr(), hip.ptr(dst), B, channels, c,
                                                   hip.stream()), "sisr_crop_augment")
             out.append(dst)
         return out[0], out[1]
@@ -214,6 +219,12 @@ class DeviceTileLoader:
         if self.degrade_tiles and not self.online:
             raise ValueError("degrade_tiles needs online_degradations on the training sets (and device_tiles)")
         self.degraders = []  # per image: the degrader of its dataset (each dataset builds its own PCA basis, ref :228-238)
+        self.ycbcr = self.y_only = False  # stored images are uploaded as RGB whatever the data set's colorspace
+        if self.online:
+            forms = {(g.interp, g.scale, g.lr_form()) for g in (d.degrader for d in datasets)}
+            if len(forms) != 1:
+                raise ValueError("device_tiles: the training sets disagree on input, degradation_scale or colorspace")
+            self.ycbcr, self.y_only = datasets[0].degrader.ycbcr, datasets[0].degrader.y_only
         for d in datasets:
             if d.hr_base is None:
                 raise ValueError("device_tiles needs HR images (training sets)")
@@ -277,7 +288,10 @@ class DeviceTileLoader:
                     pairs.append((lr_dev.contiguous(), hr_c))
                     codes.append(code.numpy() if self.metadata[i] is None else np.concatenate((self.metadata[i], code.numpy())))
                     kernels.append(kernel.numpy().squeeze())
-                lr, hr = self.sampler.sample_pairs(pairs)
+                lr, hr = self.sampler.sample_pairs(pairs)  # lr: the degrader's final form (interpolated, YCbCr / Y)
+                if self.ycbcr:  # element-wise, so converting the gathered RGB tiles is converting the image first
+                    from . import degrade
+                    hr = degrade.rgb_to_ycbcr(hr, self.y_only)
                 yield {'lr': lr, 'hr': hr, 'tag': [self.tags[i] for i in idx], 'hr_tag': [self.hr_tags[i] for i in idx],
                        'mask': zeros.clone(), 'halfway_data': zeros.clone(), 'metadata': torch.from_numpy(np.stack(codes)),
                        'metadata_keys': _collate_keys(self.metadata_keys, B),
@@ -300,23 +314,45 @@ class DeviceTileLoader:
         consumption of each."""
         from . import degrade
         sm = self.sampler
-        B, s, c = len(idx), sm.scale, sm.crop
+        B, c = len(idx), sm.crop
+        g = self.degraders[idx[0]]
+        s, interp = g.scale, g.interp  # the degradation factor: the data set's scale unless `interp` names another
+        if interp and not 2 <= s <= 4:
+            raise ValueError(f"degrade_tiles takes degradation factors 2..4 (sisr_degrade_tiles); degradation_scale = {s} "
+                             "needs the whole-image mode (degrade_tiles = false)")
         images = [sm.hr[i] for i in idx]
         draws = [self.degraders[i].draw() for i in idx]
         boxes = [degrade.center_crop_box(im.shape[1], im.shape[2], s) for im in images]
-        for (_, _, rh, rw) in boxes:
-            if min(rh, rw) // s < c:
-                raise ValueError(f"LR image {rh // s} x {rw // s} is smaller than the {c}-pixel tile")
-        crops = [sm.draw_for(torch.empty((0, rh // s, rw // s))) for (_, _, rh, rw) in boxes]
-        origins = [tile_source_box(rh // s, rw // s, c, *cr) for (_, _, rh, rw), cr in zip(boxes, crops)]
+        # the image the crops are drawn on: the LR image, or with `interp` its up-sampled form of the crop box's size
+        sizes = [(rh, rw) if interp else (rh // s, rw // s) for (_, _, rh, rw) in boxes]
+        for (h, w) in sizes:
+            if min(h, w) < c:
+                raise ValueError(f"LR image {h} x {w} is smaller than the {c}-pixel tile")
+        crops = [sm.draw_for(torch.empty((0, h, w))) for (h, w) in sizes]
+        origins = [tile_source_box(h, w, c, *cr) for (h, w), cr in zip(sizes, crops)]
         noise, jpeg = draws[0].level is not None, draws[0].quality is not None
         if any((d.level is not None) != noise or (d.quality is not None) != jpeg for d in draws):
             raise ValueError("degrade_tiles: the training sets disagree on the noise / jpeg stages of their degraders")
-        lr = degrade.degrade_tiles(images, np.stack([d.kernel.numpy() for d in draws]), origins, c, s,
-                                   flips=[cr[2:] for cr in crops], sigmas=[d.level for d in draws] if noise else None,
-                                   seeds=[d.seed for d in draws] if noise else None,
-                                   qualities=[d.quality for d in draws] if jpeg else None)
+        stages = dict(sigmas=[d.level for d in draws] if noise else None, seeds=[d.seed for d in draws] if noise else None,
+                      qualities=[d.quality for d in draws] if jpeg else None)
+        kernels = np.stack([d.kernel.numpy() for d in draws])
+        if interp:
+            # the LR window behind each tile (one edge for the batch), its bytes in source orientation -- with JPEG the round
+            # trip of the WINDOW, block grid at its origin --, then both up-sampling passes, the colour form and the flips
+            lr_sizes = [(rh // s, rw // s) for (_, _, rh, rw) in boxes]
+            windows = [(degrade.interp_window(h, s, c, ty), degrade.interp_window(w, s, c, tx))
+                       for (h, w), (ty, tx) in zip(lr_sizes, origins)]
+            cw = windows[0][0][1]
+            w_origins = [(wy, wx) for ((wy, _), (wx, _)) in windows]
+            win = degrade.degrade_tiles(images, kernels, w_origins, cw, s, flips=None, to_float=False, **stages)
+            lr = degrade.upsample_tiles(win, lr_sizes, s, w_origins, origins, c, flips=[cr[2:] for cr in crops], form=g.lr_form())
+        else:
+            lr = degrade.degrade_tiles(images, kernels, origins, c, s, flips=[cr[2:] for cr in crops], **stages)
+            if self.ycbcr:
+                lr = degrade.rgb_to_ycbcr(lr, self.y_only)
         hr = sm.gather_hr_strided(images, boxes, crops)
+        if self.ycbcr:
+            hr = degrade.rgb_to_ycbcr(hr, self.y_only)
         codes = [d.code.numpy() if self.metadata[i] is None else np.concatenate((self.metadata[i], d.code.numpy()))
                  for i, d in zip(idx, draws)]
         zeros = torch.zeros(B, dtype=torch.int64)
@@ -392,14 +428,12 @@ class SuperResImages(Dataset):
             raise RuntimeError('"lr_type" must be one of: interp | unmodified')  # ref: data_handler.py:193-194
         if 'rgb' not in colorspace and colorspace != 'ycbcr':
             raise NotImplementedError("colorspace must be an RGB one or 'ycbcr' (got %r)" % (colorspace,))
-        if colorspace == 'ycbcr' and online_degradations:
-            raise NotImplementedError("online degradations produce RGB images: colorspace = 'ycbcr' does not go with them")
+        if colorspace == 'ycbcr' and online_degradations and conv_type != 'jpg':
+            raise NotImplementedError("online degradations convert to YCbCr on the device with conv_type = 'jpg' only "
+                                      "(got %r)" % (conv_type,))
         # ref: data_handler.py:392-423: a 'ycbcr' request converts both images right after ToTensor (before flips / crops);
         # y_only keeps the luminance plane alone, (1, H, W)
         self.ycbcr, self.y_only, self.conv_type = colorspace == 'ycbcr', y_only, conv_type
-        if input == 'interp' and online_degradations:
-            raise NotImplementedError("online degradations produce low-resolution images: input = 'interp' (LR images stored "
-                                      "at HR size, SPARNet) does not go with them")
         self.lr_type = input
         for k in ('mask_data', 'halfway_data', 'blacklist', 'data_attributes', 'image_shortlist',
                   'legacy_blur_kernels', 'request_crops', 'group_select', 'attribute_amplification'):
@@ -413,8 +447,13 @@ class SuperResImages(Dataset):
             # built here, from 30 000 random kernels of numpy's global stream, before any file is listed
             if hr_dir is None:
                 raise RuntimeError('Cannot synthesize LR images without specifying HR images.')
+            # Not in the reference (its interpolated and Y-channel sets are prepared offline, data_converter.py `downscale` then
+            # `upscale`): with input = 'interp' the LR bytes are up-sampled back to the HR size by Pillow's bicubic resize, by
+            # `degradation_scale` of online_degradation_params (default: `scale` when that is above 1) -- crops, flips and the
+            # LR / HR matching keep using `scale`; with colorspace = 'ycbcr' both images are converted as rgb_to_ycbcr does
             from . import degrade
-            self.degrader = degrade.OnlineDegrader(scale=scale, **(online_degradation_params or {}))
+            self.degrader = degrade.OnlineDegrader(**dict(online_degradation_params or {}, scale=scale, interp=input == 'interp',
+                                                          ycbcr=self.ycbcr, y_only=y_only))
             self.lr_base, lr_dir = None, hr_dir
         groups = {}
         for f in image_names(lr_dir, recursive_search):
@@ -489,8 +528,8 @@ class SuperResImages(Dataset):
             raise RuntimeError('online degradations run on a HIP device (no CPU path in this package)')
         hr_im = to_tensor(read_image(os.path.join(self.hr_base, base_name)))
         lr_dev, code, kernel, (top, left, rh, rw) = self.degrader(hr_im.cuda())
-        lr_im = lr_dev.cpu()
-        hr_im = hr_im[:, top:top + rh, left:left + rw]  # center_crop to LR size x scale (ref :470-476)
+        lr_im = lr_dev.cpu()  # interpolated / colour-converted by the degrader, as the data set asked for
+        hr_im = self._colorspace(hr_im[:, top:top + rh, left:left + rw])  # center_crop to LR size x scale (ref :470-476)
         if self.random_augment is not None:
             lr_im, hr_im = random_flip_rotate(lr_im, hr_im)
         if self.patch_crop is not None:

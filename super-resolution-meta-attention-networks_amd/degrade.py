@@ -25,6 +25,13 @@ Tile-level mode (`degrade_tiles`, csrc/degrade_tiles.hip; `[data] degrade_tiles 
 batch's tiles depend on instead of on whole images -- one launch per batch, bit-identical tiles -- with the noise from a
 counter-based field (`normal_field`, numpy mirror `normal_field_host`) and JPEG on the tile.  OnlineDegrader.draw() makes an
 access's random draws, apply() the whole-image pixel work; the tile loader (data.DeviceTileLoader) uses draw() alone.
+
+Interpolated-input and Y-channel models (`input = 'interp'`, `colorspace = 'ycbcr'`; no reference counterpart: the reference
+prepares such sets offline, data_converter.py `downscale` then `upscale`): OnlineDegrader(interp=True) up-samples the LR bytes
+back to the HR size with Pillow's bicubic resize (pil_bicubic_upsample), `ycbcr` converts to BT.601 'jpg' YCbCr or Y.  In the
+tile-level mode `interp_window` names the LR window a tile of the up-sampled image depends on, degrade_tiles makes that
+window's bytes and `upsample_tiles` (csrc/interp_tiles.hip) turns a batch's windows into its tiles; `rgb_to_ycbcr` converts
+the HR tiles.
 """
 import collections
 import ctypes
@@ -151,6 +158,37 @@ def _device_table(in_size, out_size, device):
     return t
 
 
+_host_tables = {}
+
+
+def _host_table(in_size, out_size):
+    t = _host_tables.get((in_size, out_size))
+    if t is None:
+        t = _host_tables[(in_size, out_size)] = pil_bicubic_table(in_size, out_size)
+    return t
+
+
+def interp_window_edge(crop, scale):
+    """Edge of the LR window behind a `crop`-pixel tile of the x `scale` up-sampled image: output o reads the LR pixels
+    floor((o + 0.5) / s - 1.5) .. floor((o + 0.5) / s + 2.5) - 1 (clipped to the image), so `crop` consecutive outputs read at
+    most floor((crop - 1) / s) + 5 of them, whatever the tile's origin is modulo s."""
+    return (int(crop) - 1) // int(scale) + 5
+
+
+def interp_window(size, scale, crop, origin):
+    """Along one axis: the LR window that outputs origin .. origin + crop - 1 of the bicubic up-sampling (size -> size * scale)
+    depend on -> (first, edge).  `edge` = interp_window_edge(crop, scale) for every origin, so one batch has one window edge;
+    `first` is the first tap of output `origin` in the whole-image table, moved back where the window would leave the image."""
+    size, scale, crop, origin = int(size), int(scale), int(crop), int(origin)
+    edge = interp_window_edge(crop, scale)
+    if not 0 <= origin <= size * scale - crop:
+        raise ValueError(f"a {crop}-pixel tile at {origin} leaves the {size * scale}-pixel up-sampled image")
+    if size < edge:
+        raise ValueError(f"LR image side {size} is smaller than the {edge}-pixel window of a {crop}-pixel tile at x {scale}")
+    bounds = _host_table(size, size * scale)[0]
+    return min(int(bounds[origin, 0]), size - edge), edge
+
+
 # ----------------------------------------------------------------------------- device pipeline
 def blur_quant(hr, kernel, want_float=False, want_u8=True):
     """(C, H, W) fp32 on the device, (l, l) kernel -> uint8 (C, H, W) = byte(255 * BatchBlur(hr)); want_float: also
@@ -238,6 +276,23 @@ def pil_bicubic_upsample(lr, scale, rgb=True, ycbcr=False):
                                               bv.data_ptr(), cv.data_ptr(), ksh, B, C, h, w, H, W, hip.stream()),
                   "sisr_pil_upsample")
     return (out_rgb, out_ycc) if rgb and ycbcr else (out_rgb if rgb else out_ycc)
+
+
+def rgb_to_ycbcr(rgb, y_only=True):
+    """data.rgb_to_ycbcr(im_type='jpg') on the device, bit for bit: (3, H, W) or (B, 3, H, W) fp32 RGB -> the same with 3
+    (YCbCr) or 1 (Y alone) planes.  One launch."""
+    if not rgb.is_cuda:
+        raise RuntimeError("degrade.rgb_to_ycbcr: the image must be on a HIP device (data.rgb_to_ycbcr is the host form)")
+    if rgb.dtype != torch.float32 or rgb.dim() not in (3, 4) or rgb.shape[-3] != 3:
+        raise ValueError(f"rgb_to_ycbcr takes a (3, H, W) or (B, 3, H, W) fp32 image; got {rgb.dtype} {tuple(rgb.shape)}")
+    rgb = rgb.contiguous()
+    B = rgb.shape[0] if rgb.dim() == 4 else 1
+    H, W = rgb.shape[-2:]
+    with torch.cuda.device(rgb.device):
+        out = torch.empty(tuple(rgb.shape[:-3]) + (1 if y_only else 3, H, W), device=rgb.device, dtype=torch.float32)
+        hip.check(hip.lib().sisr_rgb_to_ycbcr(hip.ptr(rgb), hip.ptr(out), B, H * W, int(bool(y_only)), hip.stream()),
+                  "sisr_rgb_to_ycbcr")
+    return out
 
 
 # ----------------------------------------------------------------------------- JPEG round trip (libjpeg's integer arithmetic)
@@ -505,6 +560,51 @@ def degrade_tiles(images, kernels, origins, crop, scale, flips=None, sigmas=None
     return out
 
 
+UPSAMPLE_FORMS = {"rgb": 0, "ycbcr": 1, "y": 2}
+
+
+def upsample_tiles(windows, lr_sizes, scale, window_origins, tile_origins, crop, flips=None, form="rgb"):
+    """Tiles of the bicubic pre-up-sampled LR images from their LR windows: sample b's tile is the `crop` x `crop` square with
+    origin tile_origins[b] = (ty, tx) of the image that pil_bicubic_upsample makes of the WHOLE (h, w) = lr_sizes[b] LR image,
+    bit for bit, computed from windows[b] -- the (C, cw, cw) uint8 square of that LR image at window_origins[b] = (wy, wx), as
+    degrade_tiles(..., crop=cw, flips=None, to_float=False) returns it (interp_window names the window a tile needs).
+    flips: B (hflip, vflip, transpose), applied on the store as degrade_tiles' are; form: 'rgb' -> (B, C, crop, crop), 'ycbcr'
+    -> (B, 3, crop, crop) BT.601 'jpg', 'y' -> (B, 1, crop, crop), fp32.  One launch and one small upload, whatever B is."""
+    if form not in UPSAMPLE_FORMS:
+        raise ValueError(f"upsample_tiles: form must be one of {sorted(UPSAMPLE_FORMS)}; got {form!r}")
+    if not windows.is_cuda:
+        raise RuntimeError("degrade.upsample_tiles: the windows must be on a HIP device (no CPU path)")
+    if windows.dtype != torch.uint8 or windows.dim() != 4 or windows.shape[2] != windows.shape[3]:
+        raise ValueError(f"upsample_tiles takes (B, C, cw, cw) uint8 windows; got {windows.dtype} {tuple(windows.shape)}")
+    B, C, cw, _ = windows.shape
+    crop, scale = int(crop), int(scale)
+    if not (len(lr_sizes) == len(window_origins) == len(tile_origins) == B) or (flips is not None and len(flips) != B):
+        raise ValueError("upsample_tiles needs one LR size, window origin, tile origin and (hflip, vflip, transpose) per window")
+    dev = windows.device
+    windows = windows.contiguous()
+    recs = (hip.UpsampleTile * B)()
+    ks = 5
+    with torch.cuda.device(dev):
+        for b in range(B):
+            h, w = int(lr_sizes[b][0]), int(lr_sizes[b][1])
+            bh, ch, ksh = _device_table(w, w * scale, dev)
+            bv, cv, ksv = _device_table(h, h * scale, dev)
+            ks = ksh if ksh == ksv else 0
+            r = recs[b]
+            r.bounds_h, r.coef_h, r.bounds_v, r.coef_v = bh.data_ptr(), ch.data_ptr(), bv.data_ptr(), cv.data_ptr()
+            r.h, r.w, r.H, r.W = h, w, h * scale, w * scale
+            r.wy, r.wx = int(window_origins[b][0]), int(window_origins[b][1])
+            r.ty, r.tx = int(tile_origins[b][0]), int(tile_origins[b][1])
+            f = flips[b] if flips is not None else (0, 0, 0)
+            r.flips = int(bool(f[0])) | int(bool(f[1])) << 1 | int(bool(f[2])) << 2
+        addr, keep = _upload([np.frombuffer(bytes(recs), np.uint8)], dev)
+        out = torch.empty((B, {"rgb": C, "ycbcr": 3, "y": 1}[form], crop, crop), device=dev, dtype=torch.float32)
+        hip.check(hip.lib().sisr_upsample_tiles(ctypes.addressof(recs), addr[0], windows.data_ptr(), hip.ptr(out), ks, B, C, crop,
+                                                cw, UPSAMPLE_FORMS[form], hip.stream()), "sisr_upsample_tiles")
+        del keep  # freed in stream order behind the launch that reads it
+    return out
+
+
 DegraderDraw = collections.namedtuple("DegraderDraw", "kernel code level seed field quality")
 
 
@@ -517,11 +617,27 @@ class OnlineDegrader:
     With `jpeg` (not a reference option; its offline counterpart is data_converter.py's jpeg_compress): the LR bytes go
     through a JPEG round trip at a quality drawn per image from `jpeg_quality` = q or [lo, hi] (inclusive) -- the last draw
     of the call, one np.random.randint -- and (q - a) / (b - a) is appended to the code, [a, b] = `jpeg_norm` (default: the
-    quality range; [0, 100] for a single quality): the min-max normalisation the reference applies to an integer CSV column."""
+    quality range; [0, 100] for a single quality): the min-max normalisation the reference applies to an integer CSV column.
+    With `interp` (no reference counterpart online; offline it is data_converter.py's `downscale` then `upscale`): the LR bytes
+    are up-sampled back by the same factor with Pillow's `resize((w * s, h * s), BICUBIC)` and ToTensor, so the image has the
+    size of the centre-cropped HR image.  `degradation_scale`: the down (and up) factor when it is not the data set's `scale`
+    -- interpolated-input sets that crop pair LR and HR by scale = 1.  `ycbcr` (likewise no reference counterpart online): the
+    image in BT.601 'jpg' YCbCr, bit for bit data.rgb_to_ycbcr's; `y_only`: its plane 0 alone."""
 
     def __init__(self, scale=4, pca=None, kernel=21, sig_min=0.2, sig_max=4.0, rate_iso=1.0, scaling=3, noise=False,
                  random=True, sig=2.6, para_input=10, rate_cln=0.2, noise_high=0.08, jpeg=False, jpeg_quality=(30, 95),
-                 jpeg_norm=None, **unused):
+                 jpeg_norm=None, interp=False, degradation_scale=None, ycbcr=False, y_only=True, **unused):
+        self.interp, self.ycbcr, self.y_only = bool(interp), bool(ycbcr), bool(y_only)
+        if degradation_scale is not None:
+            if isinstance(degradation_scale, bool) or int(degradation_scale) != degradation_scale or degradation_scale < 1:
+                raise ValueError(f"degradation_scale must be a positive integer; got {degradation_scale!r}")
+            if not self.interp and int(degradation_scale) != int(scale):
+                raise ValueError(f"degradation_scale = {degradation_scale} differs from scale = {scale}: LR and HR crops are "
+                                 "paired by `scale`, so only input = 'interp' can degrade by another factor")
+            scale = int(degradation_scale)
+        elif self.interp and int(scale) <= 1:
+            raise ValueError("online degradations with input = 'interp' and scale = 1 need the down- and up-sampling factor: "
+                             "online_degradation_params = { degradation_scale = s }")
         self.jpeg = bool(jpeg)
         if self.jpeg:
             lo, hi = (jpeg_quality, jpeg_quality) if np.isscalar(jpeg_quality) else jpeg_quality
@@ -581,7 +697,8 @@ class OnlineDegrader:
         return DegraderDraw(kernel, code, level, seed, field, quality)
 
     def apply(self, hr, d):
-        """The pixel work of the whole-image path for the draws `d` (of draw(field_shape=hr.shape)) -> (lr, box)."""
+        """The pixel work of the whole-image path for the draws `d` (of draw(field_shape=hr.shape)) -> (lr, box); lr in its
+        final form (finish)."""
         if self.noise:
             _, blurred = blur_quant(hr, d.kernel, want_float=True, want_u8=False)
             u8 = noise_quant(blurred, d.level, field=d.field)
@@ -591,12 +708,30 @@ class OnlineDegrader:
         if (rh, rw) != (hr.shape[1], hr.shape[2]):
             u8 = u8[:, top:top + rh, left:left + rw].contiguous()
         if not self.jpeg:
-            return pil_bicubic_downsample(u8, self.scale), (top, left, rh, rw)
-        return jpeg_roundtrip(pil_bicubic_downsample(u8, self.scale, to_float=False), d.quality), (top, left, rh, rw)
+            lr = pil_bicubic_downsample(u8, self.scale)
+        else:
+            lr = jpeg_roundtrip(pil_bicubic_downsample(u8, self.scale, to_float=False), d.quality)
+        return self.finish(lr), (top, left, rh, rw)
+
+    def lr_form(self):
+        """What finish() and upsample_tiles write: 'rgb', 'ycbcr' or 'y'."""
+        return ("y" if self.y_only else "ycbcr") if self.ycbcr else "rgb"
+
+    def finish(self, lr):
+        """The fp32 LR image (C, h, w) -> the sample's 'lr' before flips and crops: up-sampled with `interp`, colour-converted
+        with `ycbcr`.  float32(b / 255) * 255 truncates back to b for every byte b, so pil_bicubic_upsample's ToPILImage gives
+        the LR bytes back and its result is Pillow's resize of them."""
+        if self.ycbcr and lr.shape[0] != 3:
+            raise ValueError(f"colorspace = 'ycbcr' needs RGB images; got {lr.shape[0]} channel(s)")
+        if self.interp:
+            out = pil_bicubic_upsample(lr[None], self.scale, rgb=not self.ycbcr, ycbcr=self.ycbcr)[0]
+            return out[:1].contiguous() if self.ycbcr and self.y_only else out
+        return rgb_to_ycbcr(lr, self.y_only) if self.ycbcr else lr
 
     def __call__(self, hr):
-        """hr: (3, H, W) fp32 in [0, 1] on the device -> (lr (3, h, w) fp32 device, code (k,) float32 CPU tensor,
-        kernel (l, l) float32 CPU tensor, (top, left, rh, rw) the HR centre crop that matches lr)."""
+        """hr: (3, H, W) fp32 in [0, 1] on the device -> (lr (3, h, w) fp32 device -- (3 or 1, rh, rw) with `interp`, 1 plane
+        with `ycbcr` and `y_only` --, code (k,) float32 CPU tensor, kernel (l, l) float32 CPU tensor, (top, left, rh, rw) the HR
+        centre crop that matches lr)."""
         d = self.draw(field_shape=tuple(hr.shape))
         lr, box = self.apply(hr, d)
         return lr, d.code, d.kernel, box

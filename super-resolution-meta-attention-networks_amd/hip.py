@@ -254,7 +254,19 @@ _SIGS.update({  # multi-scale SSIM: per-plane values, their mean and its gradien
     "sisr_luma_clip": (c_int, [P, c_int, c_int, c_int, P, P]),
 })
 
+_SIGS.update({  # tile-level degradation for interpolated-input and Y-channel models (csrc/interp_tiles.hip)
+    "sisr_upsample_tile_bytes": (c_size_t, []),
+    "sisr_upsample_tiles": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "sisr_rgb_to_ycbcr": (c_int, [P, P, c_int, c_long, c_int, P]),
+})
+
 GM_MAXL = 4
+
+
+class UpsampleTile(ctypes.Structure):
+    """Host mirror of sisr_upsample_tile (include/sisr_hip.h)."""
+    _fields_ = [(n, c_void_p) for n in ("bounds_h", "coef_h", "bounds_v", "coef_v")] + \
+               [(n, c_int) for n in ("h", "w", "H", "W", "wy", "wx", "ty", "tx", "flips", "pad")]
 
 
 class DegradeTile(ctypes.Structure):
