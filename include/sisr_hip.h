@@ -867,6 +867,29 @@ int sisr_upsample_tiles(const void* tiles_host, const void* tiles_dev, const uns
  * pointers, rgb == out, B or n < 1, y_only other than 0 or 1;  -4: B > 65535. */
 int sisr_rgb_to_ycbcr(const float* rgb, float* out, int B, long n, int y_only, void* stream);
 
+/* ---- the output stage of evaluation / validation (csrc/eval_output.hip): Y-MSE against the HR batch and 8-bit RGB bytes -------
+ * One streaming pass over n network outputs on the device, either result or both:
+ *   mse[i]   the mean over shave <= row < h - shave, shave <= col < w - shave of (Ys - Yh)^2, the difference in fp32, its square
+ *            and the sum in float64.  Ys: sr_planes == 3, the Y of the clipped RGB output as metrics.batch_rgb_to_ycbcr forms it
+ *            in fp32 ((0.299 R + 0.587 G) + 0.114 B, every operation rounded); sr_planes == 1, the plane itself clipped to [0, 1].
+ *            Yh: hr_form 0, the same of hr (n, hr_planes >= 3, h, w) RGB, planes 0 .. 2; hr_form 1, plane 0 of hr (n, hr_planes, h, w)
+ *            clipped.  Y-PSNR is 20 log10(max / sqrt(mse)) on the host (metrics.batch_psnr).
+ *   rgb8     n x h x w x 3 bytes, HWC.  sr_planes == 3: rint(clip(c) * 255), ties to even as np.round, byte for byte
+ *            `(clip(x) * 255).round().astype(uint8)`.  sr_planes == 1: (Y, Cb, Cr) = the clipped (sr, plane 1 of chroma, plane 2 of
+ *            chroma), chroma (n, 3, h, w); metrics.ycbcr_to_rgb_jpg in its fp32 operation order; rint(v * 255) CLAMPED to 0 .. 255.
+ *            Where the host's rounded value lies in 0 .. 255 the byte equals the host's `(rgb * 255).round().astype(uint8)`;
+ *            elsewhere it saturates at 0 or 255 where the host's cast wraps (253 for -0.01, 2 for 1.01).  NaN gives 0.
+ * The sum is ordered in two stages (per-block partials in the workspace in block order, then one block per image): no atomics, a
+ * repeat call is bit-identical.  Two launches with mse, one without; no allocation, no host synchronisation: capturable.
+ * workspace: sisr_eval_output_workspace_bytes(n, h, w) bytes, 16-byte aligned, needed with mse only; 0 for a shape that is refused.
+ * -1: null sr; neither mse nor rgb8; mse without hr; sr_planes not 1 or 3; sr_planes == 1 with rgb8 and no chroma; with hr,
+ *     hr_form not 0 or 1, hr_planes < 1 (< 3 with hr_form 0); n, h or w <= 0; shave < 0 or 2 shave >= min(h, w); with mse, a null
+ *     or too small workspace;  -2: a float pointer not 4-byte aligned, mse not 8-byte or (with mse) the workspace not 16-byte
+ *     aligned;  -4: h * w above 2^31 - 2049. */
+size_t sisr_eval_output_workspace_bytes(int n, int h, int w);
+int sisr_eval_output(const float* sr, int sr_planes, const float* chroma, const float* hr, int hr_form, int hr_planes, int n, int h,
+                     int w, int shave, double* mse, unsigned char* rgb8, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,7 +57,15 @@ def _dump_toml(d, path):
 class TrainingHandler:
     def __init__(self, experiment_name, save_loc, model_params, data_params, gpu='off', sp_gpu=0, num_epochs=None,
                  continue_from_epoch=None, max_im_val=1.0, metrics=None, seed=8, epoch_cutoff=None,
-                 early_stopping_patience=None, overwrite_data=False, **kwargs):
+                 early_stopping_patience=None, overwrite_data=False, device_metrics=False, psnr_shave=None, **kwargs):
+        """device_metrics: validation through ModelInterface.net_run_and_measure -- the output stays on the model's device, PSNR
+        comes from the device output stage (metrics.eval_output) and only the per-image values cross to the host; on a CPU
+        model the host forms of the same functions.  psnr_shave: pixels cropped from every border before PSNR (the papers'
+        protocol, typically the scale); needs device_metrics."""
+        self.device_metrics = bool(device_metrics)
+        if psnr_shave is not None and not self.device_metrics:
+            raise ValueError("[training] psnr_shave is honoured by the device output stage only: set device_metrics = true with it")
+        self.psnr_shave = int(psnr_shave or 0)
         self.rank, self.world, local = parallel.init_distributed()
         self.num_epochs, self.stop_patience, self.overwrite = num_epochs, early_stopping_patience, bool(overwrite_data)
         torch.manual_seed(seed)
@@ -117,6 +125,14 @@ class TrainingHandler:
         wanted = list(dict.fromkeys(self.metrics or ()))  # columns follow the order the metrics are listed in
         for batch in self.val_data:
             y = batch['hr']
+            if self.device_metrics:
+                measured, loss, _, _ = self.model.net_run_and_measure(**batch, metrics=wanted, max_value=self.max_im_val,
+                                                                      shave=self.psnr_shave, request_loss=True)
+                losses['val-loss'].append(loss)
+                for metric in wanted:
+                    if metric in measured:
+                        losses['val-' + metric].extend(measured[metric])
+                continue
             if 'SSIM' in wanted or 'MS-SSIM' in wanted:  # measured on the device output, before it is copied back
                 rgb_out, ycbcr_out, loss, _, measured = self.model.net_run_process_and_measure(
                     **batch, metrics=wanted, max_value=self.max_im_val, request_loss=True)
@@ -249,7 +265,12 @@ def eval_sisr(config=None, **kw):
     every model with the geometric self-ensemble (run_eval(self_ensemble=True), the papers' "+" rows): its rows and its image
     folder carry the name '<experiment>+'; the LR rows are unaffected.  `use_ema = true` loads every listed model from the
     averaged weights of its checkpoint ('network_ema', stored by a run with ema_decay; a checkpoint without them is an
-    error): its rows and image folder carry '<experiment>@ema' (before the '+', if both are set)."""
+    error): its rows and image folder carry '<experiment>@ema' (before the '+', if both are set).  `device_outputs = true`
+    routes every model through ModelInterface.net_run_and_measure: the HR batch is sent to the device once per batch for all
+    models, PSNR and the listed metrics are measured on the device output, and with `save_im` the PNGs are written from the
+    bytes the same launch makes (metrics.eval_output); no fp32 image crosses to the host.  Models on the CPU take the host
+    forms of the same functions.  `psnr_shave = k` crops k pixels from every border before PSNR (the papers' protocol,
+    typically k = scale; the model rows only); it needs device_outputs."""
     import pandas as pd
     cfg = dict(_load_toml(config)) if config is not None else {}
     cfg.update({k: v for k, v in kw.items() if v is not None})
@@ -287,6 +308,10 @@ def eval_sisr(config=None, **kw):
     need_interp = baseline or bool(y_models) or any(m.configuration['input'] != 'unmodified' for m in models)
     need_ycbcr = baseline or bool(y_models)
     device = next((torch.device('cuda', m.device) for m in models if m.device != torch.device('cpu')), None)
+    device_outputs = bool(cfg.get('device_outputs'))
+    if cfg.get('psnr_shave') is not None and not device_outputs:
+        raise ValueError("psnr_shave is honoured by the device output stage only: set device_outputs = true with it")
+    shave = int(cfg.get('psnr_shave') or 0)
     stored = None
     if need_interp and cfg.get('lr_dir_interp'):  # ready-made interpolated images, in step with the LR loader
         stored = iter(torch.utils.data.DataLoader(
@@ -295,7 +320,11 @@ def eval_sisr(config=None, **kw):
             batch_size=cfg.get('batch_size', 1)))
     rows = []
     for batch in loader:
-        y_proc = ModelInterface.colorspace_convert(batch['hr'], colorspace='rgb')
+        if baseline or not device_outputs:
+            y_proc = ModelInterface.colorspace_convert(batch['hr'], colorspace='rgb')
+        hr_there = hr_y_there = None  # the HR batch where the models run (RGB; YCbCr for the Y-channel models): sent once
+        if device_outputs:
+            hr_there = batch['hr'].to(device) if device is not None else batch['hr']
         interp = interp_ycbcr = None
         if stored is not None:
             interp, up_secs = next(stored)['lr'], None
@@ -327,6 +356,28 @@ def eval_sisr(config=None, **kw):
                         'hr': torch.stack([rgb_to_ycbcr(im, y_only=False) for im in batch['hr']])}
             elif m.configuration['input'] != 'unmodified':
                 feed = {**batch, 'lr': interp}
+            if device_outputs:
+                if m in y_models:
+                    if hr_y_there is None:
+                        hr_y_there = feed['hr'].to(device) if device is not None else feed['hr']
+                    feed = {**feed, 'hr': hr_y_there}
+                else:
+                    feed = {**feed, 'hr': hr_there}
+                measured, _, secs, rgb8 = m.net_run_and_measure(**feed, metrics=['PSNR'] + on_device, max_value=1, shave=shave,
+                                                                want_images=bool(cfg.get('save_im')), timing=timing, **plus)
+                for i, tag in enumerate(batch['tag']):
+                    row = {'Image_Name': tag, 'Model': label(m), 'PSNR': measured['PSNR'][i]}
+                    for name in on_device:
+                        row[name] = measured[name][i]
+                    row['runtime'] = secs
+                    rows.append(row)
+                if cfg.get('save_im'):
+                    from PIL import Image
+                    d = os.path.join(out_dir, label(m))
+                    os.makedirs(d, exist_ok=True)
+                    for i, tag in enumerate(batch['tag']):
+                        Image.fromarray(rgb8[i]).save(os.path.join(d, os.path.basename(tag)))
+                continue
             if on_device:  # SSIM / MS-SSIM on the device output (data_range 1), outside the timed window
                 rgb, ycbcr, _, secs, measured = m.net_run_process_and_measure(**feed, metrics=on_device, max_value=1,
                                                                               timing=timing, **plus)

@@ -24,7 +24,7 @@ from torch import nn, optim
 
 from . import architectures as A
 from . import ensemble, metrics, ops
-from .metrics import batch_ms_ssim, batch_ssim
+from .metrics import batch_ms_ssim, batch_ssim, eval_output
 
 
 class L1Loss(nn.Module):
@@ -823,6 +823,45 @@ class ModelInterface:
         out_ycbcr = self.colorspace_convert(out_rgb, colorspace='rgb')
         out_rgb = self._standard_image_formatting(out_rgb.numpy())
         return out_rgb, out_ycbcr, loss, timing, measured
+
+    def net_run_and_measure(self, lr=None, hr=None, metrics=(), max_value=1, shave=0, want_images=False, **kwargs):
+        """The device output stage: the network's output stays where the model runs and only what is asked for leaves it.
+        -> ({metric: [one value per image]}, loss, timing, rgb8 or None).
+        metrics: any of 'PSNR' (Y-PSNR with `shave` pixels cropped from every border, metrics.eval_output), 'SSIM', 'MS-SSIM'
+        (batch_ssim / batch_ms_ssim), all against `hr`, which is sent to the model's device once (a tensor already there is
+        used as it is) and also serves the loss.  want_images: the (N, H, W, 3) uint8 numpy images a PNG is written from,
+        made by the launch that measures PSNR.  A Y-channel model follows _run_y / _y_to_images: its one output plane against
+        plane 0 of `hr`, the bytes from that plane with the Cb / Cr of `lr`, saturated where the host cast of
+        net_run_and_process's RGB would wrap.  On a CPU handler everything takes the host forms of metrics.py."""
+        y_model = 'rgb' not in self.configuration['colorspace']
+        device = self.model.device
+        on_device = device != torch.device('cpu')
+        need_ref = [m for m in ('PSNR', 'SSIM', 'MS-SSIM') if m in metrics]
+        if need_ref and hr is None:
+            raise RuntimeError('Need a reference to calculate %s.' % need_ref[0])
+        ref = hr.to(device=device) if (hr is not None and on_device) else hr
+        if y_model:
+            f_ref = None if ref is None else ref[:, :1].contiguous()
+            out, loss, timing = self.model.run_eval(lr[:, :1].contiguous(), y=f_ref, keep_on_device=True, **kwargs)
+        else:
+            out, loss, timing = self.model.run_eval(x=lr, y=ref, keep_on_device=True, **kwargs)
+        chroma = None
+        if y_model and want_images:
+            chroma = lr.to(device=out.device)
+        values, rgb8 = eval_output(out, ref, chroma=chroma, max_value=max_value, shave=shave,
+                                   want_psnr='PSNR' in metrics, want_rgb8=want_images, hr_form=1 if y_model else 0)
+        measured = {}
+        if values is not None:
+            measured['PSNR'] = values
+        if 'SSIM' in metrics or 'MS-SSIM' in metrics:
+            a, b = (out.clamp(0, 1), f_ref.clamp(0, 1)) if y_model else (out, ref)
+            if 'SSIM' in metrics:
+                measured['SSIM'] = batch_ssim(a, b, max_value=max_value)
+            if 'MS-SSIM' in metrics:
+                measured['MS-SSIM'] = batch_ms_ssim(a, b, max_value=max_value)
+        if isinstance(rgb8, torch.Tensor):
+            rgb8 = rgb8.cpu().numpy()
+        return measured, loss, timing, rgb8
 
     @staticmethod
     def colorspace_convert(image, colorspace='rgb'):

@@ -260,6 +260,11 @@ _SIGS.update({  # tile-level degradation for interpolated-input and Y-channel mo
     "sisr_rgb_to_ycbcr": (c_int, [P, P, c_int, c_long, c_int, P]),
 })
 
+_SIGS.update({  # output stage of evaluation: Y-MSE against the HR batch and 8-bit HWC bytes in one pass (csrc/eval_output.hip)
+    "sisr_eval_output_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "sisr_eval_output": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+})
+
 GM_MAXL = 4
 
 

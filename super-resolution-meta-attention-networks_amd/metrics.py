@@ -1,7 +1,11 @@
 """PSNR and SSIM on the BT.601 'jpg' luma, the reference's validation / evaluation metrics.
 
-PSNR is host-side numpy.  SSIM has a host float64 form (`ssim`, numpy only) and a device form (csrc/metrics.hip,
-`sisr_ssim`) that `batch_ssim` uses for tensors on a HIP device.
+`psnr` is host-side numpy.  SSIM has a host float64 form (`ssim`, numpy only) and a device form (csrc/metrics.hip,
+`sisr_ssim`) that `batch_ssim` uses for tensors on a HIP device.  The output stage of evaluation -- Y-PSNR of a batch
+against its HR batch, with the papers' border crop (`shave`), and the 8-bit HWC image a PNG is written from -- has a device
+form too (csrc/eval_output.hip, `sisr_eval_output`: one streaming pass for either or both): `batch_psnr`, `batch_rgb8` and
+`eval_output` use it for tensors on a HIP device and the host expressions of this file otherwise.  The device bytes of a
+Y-channel output saturate (0 / 255) where the host's `astype(uint8)` of an out-of-gamut value wraps.
 
 ref: Code/sr_tools/metrics.py:6-17 (psnr), :64-91 (ssim: skimage.metrics.structural_similarity with gaussian_weights=True,
      sigma=1.5, use_sample_covariance=False, on Y planes one image at a time), Code/sr_tools/image_manipulation.py:65-89
@@ -261,3 +265,113 @@ def batch_ms_ssim(sr, hr, max_value=1, weights=MS_SSIM_WEIGHTS):
         hip.check(L.sisr_ms_ssim(hip.ptr(a), hip.ptr(b), n, h, w, float(max_value), wv, len(weights), out.data_ptr(), None,
                                  None, ws.data_ptr(), nbytes, hip.stream()), "sisr_ms_ssim")
     return out.cpu().tolist()
+
+
+def _host(t):
+    import torch
+    return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+
+
+def eval_output(sr, hr=None, chroma=None, max_value=1, shave=0, want_psnr=True, want_rgb8=False, hr_form=None):
+    """The output stage of evaluation in one pass -> (psnr, rgb8), each None when not asked for.
+    sr: (N, 3, H, W) RGB, or (N, 1, H, W) Y planes with `chroma` (N, 3, H, W) YCbCr when bytes are wanted (planes 1 and 2 used).
+    hr: (N, C, H, W); hr_form 0: RGB, compared on the Y of its clip; hr_form 1: plane 0 is Y (clipped).  None: 0 when sr and hr
+    both have three planes and sr is RGB, otherwise 1.
+    psnr: N floats, 100 if mse == 0 else 20 log10(max_value / sqrt(mse)) in float64; mse the mean over the pixels at least
+    `shave` away from every border of the squared fp32 difference of the Y planes, squared and summed in float64.
+    rgb8: (N, H, W, 3) uint8.  Three planes: (clip(x) * 255).round().  One plane: batch_ycbcr_to_rgb of (sr, chroma[:, 1:]), times
+    255, rounded and SATURATED to 0 .. 255 (the existing host path's astype(uint8) wraps there).
+    If any of the three is a tensor on a HIP device, all go to it and one sisr_eval_output call makes both results (rgb8 is then
+    a tensor on that device); anything else takes the host forms (rgb8 a numpy array)."""
+    import torch
+    if not (want_psnr or want_rgb8):
+        return None, None
+    if want_psnr and hr is None:
+        raise RuntimeError('Need a reference to calculate PSNR.')
+    shape = tuple(sr.shape)
+    if len(shape) != 4 or shape[1] not in (1, 3):
+        raise ValueError(f"eval_output takes an (N, 1|3, H, W) batch; got {shape}")
+    n, c, h, w = shape
+    if want_psnr:
+        hs = tuple(hr.shape)
+        if len(hs) != 4 or hs[0] != n or hs[2:] != (h, w) or hs[1] < 1:
+            raise ValueError(f"eval_output: hr must be (N, C, H, W) with the batch's N, H, W; got {hs} for {shape}")
+        if hr_form is None:
+            hr_form = 0 if (c == 3 and hs[1] == 3) else 1
+        if hr_form not in (0, 1) or (hr_form == 0 and hs[1] < 3):
+            raise ValueError(f"eval_output: hr_form {hr_form!r} does not fit an HR batch of {hs[1]} planes")
+        shave = int(shave)
+        if shave < 0 or 2 * shave >= min(h, w):
+            raise ValueError(f"psnr_shave = {shave} leaves nothing of a {h} x {w} image")
+    if want_rgb8 and c == 1:
+        if chroma is None or tuple(chroma.shape) != (n, 3, h, w):
+            raise ValueError("eval_output: bytes of a one-plane batch need `chroma`, an (N, 3, H, W) YCbCr batch of its size")
+    dev = next((t.device for t in (sr, hr, chroma) if isinstance(t, torch.Tensor) and t.is_cuda), None)
+    if dev is None:
+        values = rgb8 = None
+        a = _host(sr).astype(np.float32, copy=False)
+        if want_psnr:
+            b = _host(hr).astype(np.float32, copy=False)
+            ya = batch_rgb_to_ycbcr(a)[:, 0] if c == 3 else standard_image_formatting(a[:, 0])
+            yb = batch_rgb_to_ycbcr(b[:, :3])[:, 0] if hr_form == 0 else standard_image_formatting(b[:, 0])
+            values = [psnr(ya[i, shave:h - shave, shave:w - shave], yb[i, shave:h - shave, shave:w - shave],
+                           max_value=max_value) for i in range(n)]
+        if want_rgb8:
+            if c == 3:
+                v = (standard_image_formatting(a) * 255).round()
+            else:
+                ch = _host(chroma).astype(np.float32, copy=False)
+                v = (batch_ycbcr_to_rgb(np.stack([a[:, 0], ch[:, 1], ch[:, 2]], 1)) * 255).round()
+            rgb8 = np.ascontiguousarray(np.clip(np.nan_to_num(v, nan=0.0), 0, 255).astype(np.uint8).transpose(0, 2, 3, 1))
+        return values, rgb8
+    from . import hip
+    L = hip.lib()
+    to_dev = lambda t: torch.as_tensor(t).to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+    a = to_dev(sr)
+    b = to_dev(hr) if want_psnr else None
+    ch = to_dev(chroma) if want_rgb8 and c == 1 else None
+    if n == 0:
+        return ([] if want_psnr else None), (torch.empty((0, h, w, 3), dtype=torch.uint8, device=dev) if want_rgb8 else None)
+    with torch.cuda.device(dev):
+        mse = ws = rgb8 = None
+        nbytes = 0
+        if want_psnr:
+            nbytes = L.sisr_eval_output_workspace_bytes(n, h, w)
+            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+            mse = torch.empty(n, dtype=torch.float64, device=dev)
+        if want_rgb8:
+            rgb8 = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+        hip.check(L.sisr_eval_output(hip.ptr(a), c, hip.ptr(ch), hip.ptr(b), int(hr_form or 0), b.shape[1] if want_psnr else 1,
+                                     n, h, w, shave if want_psnr else 0, None if mse is None else mse.data_ptr(),
+                                     None if rgb8 is None else rgb8.data_ptr(), None if ws is None else ws.data_ptr(), nbytes,
+                                     hip.stream()), "sisr_eval_output")
+    values = None
+    if want_psnr:
+        values = [100 if m == 0 else float(20 * np.log10(max_value / np.sqrt(m))) for m in mse.cpu().tolist()]
+    return values, rgb8
+
+
+def batch_psnr(sr, hr, max_value=1, shave=0):
+    """Per-image Y-PSNR of two (N, C, H, W) batches -> list of N floats, with the argument forms of batch_ssim: C == 3 is clipped
+    RGB compared on Y (as y_psnr), C == 1 Y planes (clipped).  `shave` crops that many pixels from every border first (the
+    papers' protocol, typically the scale).  If either batch is a tensor on a HIP device both go to the device kernel
+    (sisr_eval_output: the squares and their sum in float64); anything else takes the host `psnr` on the cropped Y planes."""
+    dev, a, b = _batch_pair("batch_psnr", sr, hr)
+    if dev is None:
+        n, _, h, w = a.shape
+        shave = int(shave)
+        if shave < 0 or 2 * shave >= min(h, w):
+            raise ValueError(f"psnr_shave = {shave} leaves nothing of a {h} x {w} image")
+        if a.shape[1] == 1:  # Y planes as given are clipped, as the device form clips them; C == 3 arrives as the Y of the clip
+            a, b = standard_image_formatting(a), standard_image_formatting(b)
+        a, b = a[:, 0], b[:, 0]
+        return [psnr(a[i, shave:h - shave, shave:w - shave], b[i, shave:h - shave, shave:w - shave], max_value=max_value)
+                for i in range(n)]
+    return eval_output(a, b, max_value=max_value, shave=shave, hr_form=0 if a.shape[1] == 3 else 1)[0]
+
+
+def batch_rgb8(sr, chroma=None):
+    """The 8-bit image of a batch -> (N, H, W, 3) uint8: `(clip(x) * 255).round()` of an (N, 3, H, W) RGB batch, or of an
+    (N, 1, H, W) Y batch with `chroma` (N, 3, H, W; its Cb and Cr) the clipped YCbCr through batch_ycbcr_to_rgb, times 255,
+    rounded and saturated to 0 .. 255.  A tensor on the HIP device when an input is one (sisr_eval_output), else numpy."""
+    return eval_output(sr, chroma=chroma, want_psnr=False, want_rgb8=True)[1]
