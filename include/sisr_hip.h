@@ -727,6 +727,28 @@ int sisr_wgradk_mfma(const float* x, const float* dy, const float* dymask, float
 size_t sisr_mse_loss_workspace_bytes(void);
 int sisr_mse_loss(const float* a, const float* b, long n, float* loss, float* grad, float* workspace, void* stream);
 
+/* ---- degradation-predictor building blocks (csrc/basic.hip) -----------------------------------------------------------
+ * LeakyReLU forms of the K x K MFMA conv and its gradients (same tiles, same packing, same refusals as the forms above; a
+ * NaN or infinite slope is refused with -1), and the global mean of a map.  The slope is a per-call argument.
+ * sisr_convk_mfma_leaky: y = conv(x', packed) + bias[< nbias], then with act != 0  y = y > 0 ? y : slope * y (one fp32
+ *   rounding).  x' = x, or with in_mask (the input-gradient form: x is dy, in_mask the saved output of the layer whose
+ *   gradient is taken)  x' = in_mask > 0 ? x : slope * x.
+ * sisr_wgradk_mfma_leaky: sisr_wgradk_mfma with dy read as dymask > 0 ? dy : slope * dy (dymask required); the workspace is
+ *   that of sisr_wgradk_mfma_workspace_bytes.
+ * sisr_map_mean: out[b][ch] = (sum_pix x[b][pix][ch]) / (H W), ch < c, of a channels-last map of cp = 32 / 64 channels
+ *   (H W <= 2^24).  Ordered two-stage float64 sum: fixed pixel ranges per partial, then the partials in order; the result is
+ *   the correctly rounded mean and a repeat is bit-identical.  workspace: 8-byte aligned, sisr_map_mean_workspace_bytes.
+ * sisr_map_mean_bwd: dx[b][pix][ch] = g[b][ch] / (H W) for ch < c and 0 for c <= ch < cp. */
+int sisr_convk_mfma_leaky(const float* x, const float* in_mask, const float* packed, const float* bias, int nbias, float* y,
+                          int B, int H, int W, int K, int cin_p, int cout_p, int act, float slope, void* stream);
+int sisr_wgradk_mfma_leaky(const float* x, const float* dy, const float* dymask, float* dw, float* db, int B, int H, int W,
+                           int K, int cout, int cin, int cop, int cip, float* workspace, size_t workspace_bytes, float slope,
+                           void* stream);
+size_t sisr_map_mean_workspace_bytes(int B, int H, int W, int cp);
+int sisr_map_mean(const float* x, float* out, int B, int H, int W, int c, int cp, void* workspace, size_t workspace_bytes,
+                  void* stream);
+int sisr_map_mean_bwd(const float* g, float* dx, int B, int H, int W, int c, int cp, void* stream);
+
 /* ---- geometric self-ensemble around a network (csrc/ensemble.hip) -----------------------------------------------------
  * The eight flips / transposes of an image batch as two batches a network runs as they are, and the mean of its eight
  * outputs with each mapped back (the "+" protocol of the EDSR / RCAN / HAN / SAN papers).  All maps contiguous NCHW fp32;

@@ -5,7 +5,7 @@ Import with ``importlib.import_module("super-resolution-meta-attention-networks_
 architectures (drop-in nn.Modules), handlers (model-handler API), parallel (RCCL data parallelism),
 metrics (PSNR), basic (SRCNN / VDSR), ensemble (x8 geometric self-ensemble for evaluation),
 perceptual (VGG19 feature loss), structural (SSIM loss term), multiscale (MS-SSIM loss term),
-frequency (FFT L1 loss term).
+frequency (FFT L1 loss term), predictor (degradation code from an LR image), pool (global mean of a map).
 """
-from . import hip, ops, optim, architectures, metrics, handlers, parallel, han, san, srmd, sftmd, sparnet, basic, degrade, data, ensemble, perceptual, structural, multiscale, frequency, cli  # noqa: F401
+from . import hip, ops, optim, architectures, metrics, handlers, parallel, han, san, srmd, sftmd, sparnet, basic, degrade, data, ensemble, perceptual, structural, multiscale, frequency, pool, predictor, cli  # noqa: F401
 from .handlers import ModelInterface, available_models  # noqa: F401

@@ -20,7 +20,7 @@ import torch
 from . import metrics as M
 from . import parallel
 from .data import SuperResImages, rgb_to_ycbcr, sisr_data_setup
-from .handlers import ModelInterface, create_dir_if_empty
+from .handlers import ModelInterface, QModel, create_dir_if_empty
 
 
 def _load_toml(path):
@@ -73,6 +73,7 @@ class TrainingHandler:
         np.random.seed(seed)
         random.seed(seed)
         self.best_val_model_idx, self.best_val_model_psnr = 0, 0
+        self.best_val_model_loss = None  # (models that predict the degradation code are ranked by val-loss)
         self.max_im_val = max_im_val
         self.metrics = list(metrics) if metrics is not None else None
         if self.world > 1:
@@ -120,7 +121,22 @@ class TrainingHandler:
                 return self._eval(epoch_idx)
         return self._eval(epoch_idx)
 
+    def _eval_codes(self):
+        """validation of a model that predicts the degradation code (handler.predicts_metadata): per batch the loss against
+        the batch's code and per image the mean absolute code error; no image is made, the `metrics` list is not read"""
+        handler = self.model.model
+        losses = defaultdict(list)
+        for batch in self.val_data:
+            codes, loss, _ = handler.run_eval(batch['lr'], metadata=batch['metadata'], metadata_keys=batch['metadata_keys'],
+                                              request_loss=True)
+            target = handler.target_codes(batch['lr'], batch['metadata'], batch['metadata_keys']).cpu()
+            losses['val-loss'].append(loss)
+            losses['val-MAE'].extend((codes.double() - target.double()).abs().mean(dim=1).tolist())
+        return losses
+
     def _eval(self, epoch_idx):
+        if getattr(self.model.model, 'predicts_metadata', False):
+            return self._eval_codes()
         losses = defaultdict(list)
         wanted = list(dict.fromkeys(self.metrics or ()))  # columns follow the order the metrics are listed in
         for batch in self.val_data:
@@ -174,9 +190,18 @@ class TrainingHandler:
                 #                      every rank's stream -- hence next epoch's shuffle -- identical
             if self.rank == 0:
                 cur.update(self.eval(epoch_idx))
-                val_psnr = np.mean(cur['val-PSNR']) if 'val-PSNR' in cur else float('nan')
-                if val_psnr > self.best_val_model_psnr:
-                    self.best_val_model_psnr, self.best_val_model_idx, stale = val_psnr, epoch_idx, 0
+                if getattr(self.model.model, 'predicts_metadata', False):  # no image, no PSNR: the lowest val-loss is best
+                    val_loss = float(np.mean(cur['val-loss']))
+                    improved = self.best_val_model_loss is None or val_loss < self.best_val_model_loss
+                    if improved:
+                        self.best_val_model_loss = val_loss
+                else:
+                    val_psnr = np.mean(cur['val-PSNR']) if 'val-PSNR' in cur else float('nan')
+                    improved = val_psnr > self.best_val_model_psnr
+                    if improved:
+                        self.best_val_model_psnr = val_psnr
+                if improved:
+                    self.best_val_model_idx, stale = epoch_idx, 0
                 else:
                     stale += 1
                 for k, v in cur.items():
@@ -254,6 +279,74 @@ def _interpolated(lr, scale, device, want_ycbcr, timing):
     return rgb, ycbcr, time.perf_counter() - tic if timing else None
 
 
+def _load_predictor(cfg, models):
+    """The `metadata_predictor = [experiment, epoch]` model of an evaluation (None without the key), loaded once next to the
+    listed models.  Every listed Q-model must take exactly the code it predicts: a different `metadata` list, in order or
+    content, is refused here, before any image is read."""
+    key = cfg.get('metadata_predictor')
+    if not key:
+        return None
+    name, ep = key
+    use_ema = bool(cfg.get('use_ema'))
+    if use_ema:  # the averaged weights when the predictor's run kept an average; its trained ones otherwise
+        stored = _load_toml(os.path.join(cfg['model_loc'], name, 'config.toml'))['model']['internal_params']
+        use_ema = stored.get('ema_decay') is not None
+    predictor = ModelInterface(cfg['model_loc'], name, gpu='single' if cfg.get('gpu') else 'off', sp_gpu=cfg.get('sp_gpu', 0),
+                               mode='eval', load_epoch=ep if ep in ('best', 'last') else int(ep), ema=use_ema)
+    if not getattr(predictor.model, 'predicts_metadata', False):
+        raise ValueError("metadata_predictor: experiment %r holds a %r model, which predicts no degradation code"
+                         % (name, predictor.name))
+    for m in models:
+        if isinstance(m.model, QModel) and list(m.model.metadata) != list(predictor.model.metadata):
+            raise ValueError("metadata_predictor: model %r reads the metadata %s, the predictor %r estimates %s; the two lists "
+                             "must be the same, in the same order"
+                             % (m.experiment, list(m.model.metadata), name, list(predictor.model.metadata)))
+    return predictor
+
+
+def _code_columns(handler):
+    """one column name per entry of a handler's code: the key itself, or key_<i> for a key of several entries"""
+    names = []
+    for key in handler.metadata:
+        width = {'all': 40, 'blur_kernel': 10, 'unmodified_blur_kernel': 441}.get(key, 1)
+        names += [key] if width == 1 else ['%s_%d' % (key, i) for i in range(width)]
+    return names
+
+
+def _code_rows(handler, batch, codes, have_file):
+    """rows of predicted_metadata.csv for a batch: the code entries and, next to a metadata file, the mean absolute
+    difference from the file's code"""
+    host = codes.detach().cpu()
+    names = _code_columns(handler)
+    mae = None
+    if have_file:
+        want = handler.generate_channels(batch['lr'], batch['metadata'], batch['metadata_keys'])[:, :, 0, 0]
+        mae = (host.double() - want.double()).abs().mean(dim=1).tolist()
+    rows = []
+    for i, tag in enumerate(batch['tag']):
+        row = {'Image_Name': tag, **{n: float(v) for n, v in zip(names, host[i].tolist())}}
+        if mae is not None:
+            row['code_MAE'] = mae[i]
+        rows.append(row)
+    return rows
+
+
+def _with_predicted_codes(handler, predictor, batch, codes):
+    """The batch a Q-model is given when its code comes from the predictor: the file's metadata is taken out and the
+    predicted code goes in as `extra_channels` (QModel.channels_from_codes), on the model's device.  Handlers that build their
+    own metadata maps in run_eval (SRMD, SFTMD) get the code as the batch's metadata instead, keyed entry by entry."""
+    feed = {k: v for k, v in batch.items() if k not in ('metadata', 'metadata_keys')}
+    if type(handler).run_eval is QModel.run_eval:
+        extra = handler.channels_from_codes(codes)
+        feed['extra_channels'] = extra if handler.device == torch.device('cpu') else extra.to(handler.device)
+        return feed
+    B = codes.shape[0]
+    keys = [k for key in predictor.metadata
+            for k in [key] * {'all': 40, 'blur_kernel': 10, 'unmodified_blur_kernel': 441}.get(key, 1)]
+    feed['metadata'], feed['metadata_keys'] = codes.detach().cpu(), [tuple(k for _ in range(B)) for k in keys]
+    return feed
+
+
 def eval_sisr(config=None, **kw):
     """ref: net_eval.py:64-74 / standard_eval.py full_image_protocol: per-image and average Y-PSNR CSVs, plus Y-SSIM
     columns when the config's `metrics` lists 'SSIM' (ref: standard_eval.py:268-271) and Y-MS-SSIM columns when it lists
@@ -287,6 +380,8 @@ def eval_sisr(config=None, **kw):
         if m.configuration['input'] == 'unmodified' and scale != m.metadata['internal_params']['scale']:
             raise Exception('The model loaded has been trained for a different scale, '
                             'and cannot produce the requested images.')
+    predictor = _load_predictor(cfg, models)
+    code_rows = []
     lr_dir = cfg['lr_dir']
     meta = cfg.get('metadata_file') or os.path.join(lr_dir, 'degradation_metadata.csv')
     if not os.path.isfile(meta):
@@ -347,15 +442,21 @@ def eval_sisr(config=None, **kw):
                     row['MS-SSIM'] = lr_ms[i]
                 row['runtime'] = up_secs
                 rows.append(row)
+        codes = None
+        if predictor is not None:  # on the LR batch as read: RGB, before any interpolation
+            codes, _, _ = predictor.model.run_eval(batch['lr'], keep_on_device=True)
+            code_rows.extend(_code_rows(predictor.model, batch, codes, have_file=meta is not None))
         for m in models:
             feed = batch
+            if codes is not None and isinstance(m.model, QModel):
+                feed = _with_predicted_codes(m.model, predictor.model, batch, codes)
             if m in y_models:
                 # the Y-channel branch reads the reference's Y from channel 0 of `hr` (loss, SSIM): hand it the HR image as
                 # the validation set of such a model does, in YCbCr (data.SuperResImages, colorspace = 'ycbcr')
-                feed = {**batch, 'lr': interp_ycbcr,
+                feed = {**feed, 'lr': interp_ycbcr,
                         'hr': torch.stack([rgb_to_ycbcr(im, y_only=False) for im in batch['hr']])}
             elif m.configuration['input'] != 'unmodified':
-                feed = {**batch, 'lr': interp}
+                feed = {**feed, 'lr': interp}
             if device_outputs:
                 if m in y_models:
                     if hr_y_there is None:
@@ -402,6 +503,8 @@ def eval_sisr(config=None, **kw):
     mdir = os.path.join(out_dir, 'standard_metrics')
     create_dir_if_empty(mdir)
     df.to_csv(os.path.join(mdir, 'individual_metrics.csv'), index=False)
+    if predictor is not None:
+        pd.DataFrame(code_rows).to_csv(os.path.join(mdir, 'predicted_metadata.csv'), index=False)
     avg = df.groupby('Model')[['PSNR'] + on_device + ['runtime']].mean().reset_index()
     avg.to_csv(os.path.join(mdir, 'average_metrics.csv'), index=False)
     return df, avg

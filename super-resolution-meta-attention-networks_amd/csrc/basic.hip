@@ -16,6 +16,11 @@
 //   sisr_wgradk_mfma   its weight gradient: per (tap, 32 input channels, pixel slice) workgroup, M = Cout, N = 32 input
 //                      channels, contraction over pixels; slices are summed in order by a second pass.
 //   sisr_mse_loss      mean squared difference and its gradient 2 (a - b) / n in the same launch (ordered two-stage sum).
+//   sisr_convk_mfma_leaky, sisr_wgradk_mfma_leaky   the two MFMA kernels with LeakyReLU(slope) in place of ReLU: the forward
+//                      epilogue selects v > 0 ? v : slope * v, the gradient forms read dy as m > 0 ? dy : slope * dy through
+//                      the layer's saved output m (one more template flag; the ReLU forms keep their own selects).
+//   sisr_map_mean, sisr_map_mean_bwd   global mean of a map's real channels (ordered two-stage float64 sum) and its gradient:
+//                      the degradation predictor's head (predictor.py).
 //
 // Within a lane the contraction index of the 32x32x2 MFMA is permuted (lane half h takes channels 16 h + kk at step kk), so
 // both operands are read 16 bytes at a time; A and B use the same permutation, so the sum is over the same products.
@@ -315,11 +320,13 @@ extern "C" int sisr_pack_convk(const float* w, float* fwd, float* dgrad, int K, 
 }
 
 // Wave v of the 4 computes rows 2v, 2v+1 of the 8 x 32 pixel tile: MT = 2 M-tiles of 32 pixels x NT N-tiles of 32 channels.
-template <int NT>
+// LEAKY: the LeakyReLU forms -- in_mask scales by `slope` where the map is <= 0 instead of zeroing (dy read through the saved
+// output of a leaky layer), and `relu` selects v > 0 ? v : slope * v.  The ReLU forms keep their selects (slope unused).
+template <int NT, bool LEAKY>
 __global__ __launch_bounds__(256) void bk_convk_mfma_kernel(const float* __restrict__ x, const float* __restrict__ in_mask,
                                                             const float* __restrict__ wp, const float* __restrict__ bias,
                                                             int nbias, const float* __restrict__ mask, float* __restrict__ y,
-                                                            int H, int W, int K, int cin_p, int relu) {
+                                                            int H, int W, int K, int cin_p, int relu, float slope) {
   extern __shared__ __attribute__((aligned(16))) float lds[];  // [LH * LW][BK_XS]
   constexpr int cout_p = NT * 32;
   const int p = K / 2, LW = BK_TW + K - 1, LH = BK_TH + K - 1;
@@ -344,7 +351,12 @@ __global__ __launch_bounds__(256) void bk_convk_mfma_kernel(const float* __restr
         v = *reinterpret_cast<const f32x4*>(x + o);
         if (in_mask) {
           const f32x4 m = *reinterpret_cast<const f32x4*>(in_mask + o);
-          v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
+          if constexpr (LEAKY) {
+            v.x = m.x > 0.f ? v.x : slope * v.x; v.y = m.y > 0.f ? v.y : slope * v.y;
+            v.z = m.z > 0.f ? v.z : slope * v.z; v.w = m.w > 0.f ? v.w : slope * v.w;
+          } else {
+            v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
+          }
         }
       }
       *reinterpret_cast<f32x4*>(lds + pix * BK_XS + q * 4) = v;
@@ -392,7 +404,11 @@ __global__ __launch_bounds__(256) void bk_convk_mfma_kernel(const float* __restr
         if (ww >= W) continue;
         const long o = (((long)b * H + hh) * W + ww) * cout_p + co;
         float v = acc[mt][nt][r] + bv;
-        if (relu) v = fmaxf(v, 0.f);
+        if constexpr (LEAKY) {
+          if (relu) v = v > 0.f ? v : slope * v;
+        } else {
+          if (relu) v = fmaxf(v, 0.f);
+        }
         if (mask) v = mask[o] > 0.f ? v : 0.f;
         y[o] = v;
       }
@@ -402,34 +418,49 @@ __global__ __launch_bounds__(256) void bk_convk_mfma_kernel(const float* __restr
 
 static size_t bk_mfma_lds(int K) { return sizeof(float) * (size_t)(BK_TH + K - 1) * (BK_TW + K - 1) * BK_XS; }
 
-extern "C" int sisr_convk_mfma(const float* x, const float* in_mask, const float* packed, const float* bias, int nbias,
-                               const float* mask, float* y, int B, int H, int W, int K, int cin_p, int cout_p, int relu,
-                               void* stream) {
+template <bool LEAKY>
+static int bk_convk_mfma(const float* x, const float* in_mask, const float* packed, const float* bias, int nbias,
+                         const float* mask, float* y, int B, int H, int W, int K, int cin_p, int cout_p, int relu, float slope,
+                         void* stream) {
   if (!x || !packed || !y || !bk_dims_ok(B, H, W) || nbias < 0) return SISR_ERR_ARG;
   if (!bk_k_ok(K) || !bk_cp_ok(cin_p) || !bk_cp_ok(cout_p) || nbias > cout_p) return SISR_ERR_UNSUPPORTED;
   if (!sisr_aligned16(x) || !sisr_aligned16(in_mask) || !sisr_aligned16(packed)) return SISR_ERR_ALIGN;
   const dim3 grid((W + BK_TW - 1) / BK_TW, (H + BK_TH - 1) / BK_TH, B);
   const size_t lds = bk_mfma_lds(K);  // 9 x 9: 90 KB
   if (cout_p == 64) {
-    SISR_ALLOW_LDS(bk_convk_mfma_kernel<2>, bk_mfma_lds(BK_MAXK));
-    hipLaunchKernelGGL(bk_convk_mfma_kernel<2>, grid, dim3(256), lds, (hipStream_t)stream, x, in_mask, packed, bias, nbias,
-                       mask, y, H, W, K, cin_p, relu);
+    SISR_ALLOW_LDS((bk_convk_mfma_kernel<2, LEAKY>), bk_mfma_lds(BK_MAXK));
+    hipLaunchKernelGGL((bk_convk_mfma_kernel<2, LEAKY>), grid, dim3(256), lds, (hipStream_t)stream, x, in_mask, packed, bias,
+                       nbias, mask, y, H, W, K, cin_p, relu, slope);
   } else {
-    SISR_ALLOW_LDS(bk_convk_mfma_kernel<1>, bk_mfma_lds(BK_MAXK));
-    hipLaunchKernelGGL(bk_convk_mfma_kernel<1>, grid, dim3(256), lds, (hipStream_t)stream, x, in_mask, packed, bias, nbias,
-                       mask, y, H, W, K, cin_p, relu);
+    SISR_ALLOW_LDS((bk_convk_mfma_kernel<1, LEAKY>), bk_mfma_lds(BK_MAXK));
+    hipLaunchKernelGGL((bk_convk_mfma_kernel<1, LEAKY>), grid, dim3(256), lds, (hipStream_t)stream, x, in_mask, packed, bias,
+                       nbias, mask, y, H, W, K, cin_p, relu, slope);
   }
   return sisr_check_launch();
+}
+
+extern "C" int sisr_convk_mfma(const float* x, const float* in_mask, const float* packed, const float* bias, int nbias,
+                               const float* mask, float* y, int B, int H, int W, int K, int cin_p, int cout_p, int relu,
+                               void* stream) {
+  return bk_convk_mfma<false>(x, in_mask, packed, bias, nbias, mask, y, B, H, W, K, cin_p, cout_p, relu, 0.f, stream);
+}
+
+extern "C" int sisr_convk_mfma_leaky(const float* x, const float* in_mask, const float* packed, const float* bias, int nbias,
+                                     float* y, int B, int H, int W, int K, int cin_p, int cout_p, int act, float slope,
+                                     void* stream) {
+  if (!(slope == slope) || slope - slope != 0.f) return SISR_ERR_ARG;  // NaN / infinite slope
+  return bk_convk_mfma<true>(x, in_mask, packed, bias, nbias, nullptr, y, B, H, W, K, cin_p, cout_p, act, slope, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ its weight gradient
 // Workgroup (tap, 32-channel chunk of Cin, slice s of the B*H image rows): D[co][ci] += sum_pixels dy[pix][co] x[pix + tap][ci],
 // two pixels per MFMA (lane half h takes pixel w0 + h).  The 4 waves take every 4th row of the slice; their tiles are summed
 // in wave order through LDS and written as slice s's partial.
-template <int MT>
+// LEAKY: dy is scaled by `slope` where dymask <= 0 instead of zeroed (the layer's activation was a LeakyReLU).
+template <int MT, bool LEAKY>
 __global__ __launch_bounds__(256) void bk_wgradk_mfma_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                              const float* __restrict__ dymask, float* __restrict__ part,
-                                                             int B, int H, int W, int K, int cip, int S) {
+                                                             int B, int H, int W, int K, int cip, int S, float slope) {
   __shared__ float red[4][MT][16 * 64];
   constexpr int cop = MT * 32;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, h = lane >> 5, i = lane & 31;
@@ -458,7 +489,11 @@ __global__ __launch_bounds__(256) void bk_wgradk_mfma_kernel(const float* __rest
         for (int mt = 0; mt < MT; ++mt) {
           const long o = (long)(okd ? wd : 0) * cop + mt * 32 + i;
           float a = dyr[o];
-          if (mr) a = mr[o] > 0.f ? a : 0.f;
+          if constexpr (LEAKY) {
+            if (mr) a = mr[o] > 0.f ? a : slope * a;
+          } else {
+            if (mr) a = mr[o] > 0.f ? a : 0.f;
+          }
           av[u][mt] = okd ? a : 0.f;
         }
       }
@@ -494,16 +529,20 @@ __global__ __launch_bounds__(256) void bk_wgradk_final_kernel(const float* __res
 }
 
 // per-channel sum of a (masked) channels-last map: ordered partials per workgroup, then one ordered pass
-template <int CP>
+template <int CP, bool LEAKY>
 __global__ __launch_bounds__(256) void bk_colsum_kernel(const float* __restrict__ dy, const float* __restrict__ dymask,
-                                                        long npix, float* __restrict__ part) {
+                                                        long npix, float* __restrict__ part, float slope) {
   constexpr int G = 256 / CP;
   __shared__ float red[256];
   const int c = threadIdx.x % CP, g = threadIdx.x / CP;
   float s = 0.f;
   for (long pix = (long)blockIdx.x * G + g; pix < npix; pix += (long)gridDim.x * G) {
     float v = dy[pix * CP + c];
-    if (dymask) v = dymask[pix * CP + c] > 0.f ? v : 0.f;
+    if constexpr (LEAKY) {
+      if (dymask) v = dymask[pix * CP + c] > 0.f ? v : slope * v;
+    } else {
+      if (dymask) v = dymask[pix * CP + c] > 0.f ? v : 0.f;
+    }
     s += v;
   }
   red[threadIdx.x] = s;
@@ -543,9 +582,10 @@ extern "C" size_t sisr_wgradk_mfma_workspace_bytes(int B, int H, int W, int K, i
   return sizeof(float) * ((size_t)bk_wgrad_slices(B, H, K, cin_p) * cout_p * cin_p * K * K + (size_t)BK_PARTS * cout_p);
 }
 
-extern "C" int sisr_wgradk_mfma(const float* x, const float* dy, const float* dymask, float* dw, float* db, int B, int H,
-                                int W, int K, int cout, int cin, int cop, int cip, float* workspace, size_t workspace_bytes,
-                                void* stream) {
+template <bool LEAKY>
+static int bk_wgradk_mfma(const float* x, const float* dy, const float* dymask, float* dw, float* db, int B, int H, int W,
+                          int K, int cout, int cin, int cop, int cip, float* workspace, size_t workspace_bytes, float slope,
+                          void* stream) {
   if (!x || !dy || !dw || !workspace || !bk_dims_ok(B, H, W) || cout < 1 || cin < 1) return SISR_ERR_ARG;
   if (!bk_k_ok(K) || !bk_cp_ok(cop) || !bk_cp_ok(cip) || cout > cop || cin > cip) return SISR_ERR_UNSUPPORTED;
   if (workspace_bytes < sisr_wgradk_mfma_workspace_bytes(B, H, W, K, cip, cop)) return SISR_ERR_ARG;
@@ -553,9 +593,11 @@ extern "C" int sisr_wgradk_mfma(const float* x, const float* dy, const float* dy
   const int S = bk_wgrad_slices(B, H, K, cip), KK = K * K;
   const dim3 grid(KK, cip / 32, S);
   if (cop == 64)
-    hipLaunchKernelGGL(bk_wgradk_mfma_kernel<2>, grid, dim3(256), 0, s, x, dy, dymask, workspace, B, H, W, K, cip, S);
+    hipLaunchKernelGGL((bk_wgradk_mfma_kernel<2, LEAKY>), grid, dim3(256), 0, s, x, dy, dymask, workspace, B, H, W, K, cip, S,
+                       slope);
   else
-    hipLaunchKernelGGL(bk_wgradk_mfma_kernel<1>, grid, dim3(256), 0, s, x, dy, dymask, workspace, B, H, W, K, cip, S);
+    hipLaunchKernelGGL((bk_wgradk_mfma_kernel<1, LEAKY>), grid, dim3(256), 0, s, x, dy, dymask, workspace, B, H, W, K, cip, S,
+                       slope);
   int rc = sisr_check_launch();
   if (rc) return rc;
   const long n = (long)cout * cin * KK;
@@ -567,12 +609,126 @@ extern "C" int sisr_wgradk_mfma(const float* x, const float* dy, const float* dy
   const long npix = (long)B * H * W;
   const int parts = bk_colsum_parts(npix, cop);
   if (cop == 64)
-    hipLaunchKernelGGL(bk_colsum_kernel<64>, dim3(parts), dim3(256), 0, s, dy, dymask, npix, bpart);
+    hipLaunchKernelGGL((bk_colsum_kernel<64, LEAKY>), dim3(parts), dim3(256), 0, s, dy, dymask, npix, bpart, slope);
   else
-    hipLaunchKernelGGL(bk_colsum_kernel<32>, dim3(parts), dim3(256), 0, s, dy, dymask, npix, bpart);
+    hipLaunchKernelGGL((bk_colsum_kernel<32, LEAKY>), dim3(parts), dim3(256), 0, s, dy, dymask, npix, bpart, slope);
   rc = sisr_check_launch();
   if (rc) return rc;
   hipLaunchKernelGGL(bk_colsum_final_kernel, dim3(1), dim3(64), 0, s, bpart, parts, cop, cout, db);
+  return sisr_check_launch();
+}
+
+extern "C" int sisr_wgradk_mfma(const float* x, const float* dy, const float* dymask, float* dw, float* db, int B, int H,
+                                int W, int K, int cout, int cin, int cop, int cip, float* workspace, size_t workspace_bytes,
+                                void* stream) {
+  return bk_wgradk_mfma<false>(x, dy, dymask, dw, db, B, H, W, K, cout, cin, cop, cip, workspace, workspace_bytes, 0.f, stream);
+}
+
+// dymask is the layer's saved output and is required: without it there is no activation to differentiate
+extern "C" int sisr_wgradk_mfma_leaky(const float* x, const float* dy, const float* dymask, float* dw, float* db, int B, int H,
+                                      int W, int K, int cout, int cin, int cop, int cip, float* workspace,
+                                      size_t workspace_bytes, float slope, void* stream) {
+  if (!dymask || !(slope == slope) || slope - slope != 0.f) return SISR_ERR_ARG;
+  return bk_wgradk_mfma<true>(x, dy, dymask, dw, db, B, H, W, K, cout, cin, cop, cip, workspace, workspace_bytes, slope, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ global mean of a map
+// out[b][c] = (sum_pix x[b][pix][c]) / (H W) for the real channels of a channels-last map, and its gradient.  Two ordered
+// stages in float64: part p of image b sums the fixed pixel range [p per, (p + 1) per) (thread group g takes every G-th pixel
+// of it, the groups are summed in order through LDS), then one thread per channel sums the parts in order.  The float64 sum
+// of fp32 values is exact far beyond the fp32 budget, so the result is the correctly rounded mean and repeats bit for bit.
+#define MM_PIX 512   // pixels per part
+#define MM_PARTS 128 // at most this many parts per image
+
+static int mm_parts(int H, int W) {
+  const long n = ((long)H * W + MM_PIX - 1) / MM_PIX;
+  return (int)(n < MM_PARTS ? n : MM_PARTS);
+}
+
+template <int CP>
+__global__ __launch_bounds__(256) void bk_map_mean_partial_kernel(const float* __restrict__ x, long HW, int per,
+                                                                  double* __restrict__ part) {
+  constexpr int Q = CP / 4, G = 256 / Q;  // Q lanes of 4 channels per pixel, G pixels per pass
+  __shared__ double red[G][CP];
+  const int q = threadIdx.x % Q, g = threadIdx.x / Q, b = blockIdx.y;
+  const long begin = (long)blockIdx.x * per, end = begin + per < HW ? begin + per : HW;
+  double s0 = 0., s1 = 0., s2 = 0., s3 = 0.;
+  const float* xb = x + (long)b * HW * CP + q * 4;
+  for (long pix = begin + g; pix < end; pix += G) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(xb + pix * CP);
+    s0 += v.x; s1 += v.y; s2 += v.z; s3 += v.w;
+  }
+  red[g][q * 4 + 0] = s0; red[g][q * 4 + 1] = s1; red[g][q * 4 + 2] = s2; red[g][q * 4 + 3] = s3;
+  __syncthreads();
+  if (threadIdx.x < CP) {
+    double t = red[0][threadIdx.x];
+    for (int k = 1; k < G; ++k) t += red[k][threadIdx.x];
+    part[((long)b * gridDim.x + blockIdx.x) * CP + threadIdx.x] = t;
+  }
+}
+
+__global__ __launch_bounds__(64) void bk_map_mean_final_kernel(const double* __restrict__ part, int nparts, int cp, int c,
+                                                               double hw, float* __restrict__ out) {
+  const int ch = threadIdx.x, b = blockIdx.x;
+  if (ch >= c) return;
+  double s = 0.;
+  for (int k = 0; k < nparts; ++k) s += part[((long)b * nparts + k) * cp + ch];
+  out[(long)b * c + ch] = (float)(s / hw);
+}
+
+template <int CP>
+__global__ __launch_bounds__(256) void bk_map_mean_bwd_kernel(const float* __restrict__ g, long HW, int c, float hw,
+                                                              float* __restrict__ dx) {
+  constexpr int Q = CP / 4;
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;  // one 4-channel group of one pixel of image blockIdx.y
+  if (e >= HW * Q) return;
+  const int q = (int)(e % Q), b = blockIdx.y;
+  f32x4 v;
+  v.x = q * 4 + 0 < c ? g[(long)b * c + q * 4 + 0] / hw : 0.f;
+  v.y = q * 4 + 1 < c ? g[(long)b * c + q * 4 + 1] / hw : 0.f;
+  v.z = q * 4 + 2 < c ? g[(long)b * c + q * 4 + 2] / hw : 0.f;
+  v.w = q * 4 + 3 < c ? g[(long)b * c + q * 4 + 3] / hw : 0.f;
+  reinterpret_cast<f32x4*>(dx + (long)b * HW * CP)[e] = v;
+}
+
+// (H W <= 2^24 keeps float(H W) exact in the backward's division)
+static inline bool mm_dims_ok(int B, int H, int W) { return bk_dims_ok(B, H, W) && (long)H * W <= (1L << 24); }
+
+extern "C" size_t sisr_map_mean_workspace_bytes(int B, int H, int W, int cp) {
+  if (!mm_dims_ok(B, H, W) || !bk_cp_ok(cp)) return 0;
+  return sizeof(double) * (size_t)B * mm_parts(H, W) * cp;
+}
+
+extern "C" int sisr_map_mean(const float* x, float* out, int B, int H, int W, int c, int cp, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  if (!x || !out || !workspace || !mm_dims_ok(B, H, W) || c < 1) return SISR_ERR_ARG;
+  if (!bk_cp_ok(cp) || c > cp) return SISR_ERR_UNSUPPORTED;
+  if (!sisr_aligned16(x) || ((uintptr_t)workspace & 7)) return SISR_ERR_ALIGN;
+  if (workspace_bytes < sisr_map_mean_workspace_bytes(B, H, W, cp)) return SISR_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const long HW = (long)H * W;
+  const int parts = mm_parts(H, W), per = (int)((HW + parts - 1) / parts);
+  double* part = (double*)workspace;
+  if (cp == 64)
+    hipLaunchKernelGGL(bk_map_mean_partial_kernel<64>, dim3(parts, B), dim3(256), 0, s, x, HW, per, part);
+  else
+    hipLaunchKernelGGL(bk_map_mean_partial_kernel<32>, dim3(parts, B), dim3(256), 0, s, x, HW, per, part);
+  int rc = sisr_check_launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL(bk_map_mean_final_kernel, dim3(B), dim3(64), 0, s, part, parts, cp, c, (double)HW, out);
+  return sisr_check_launch();
+}
+
+extern "C" int sisr_map_mean_bwd(const float* g, float* dx, int B, int H, int W, int c, int cp, void* stream) {
+  if (!g || !dx || !mm_dims_ok(B, H, W) || c < 1) return SISR_ERR_ARG;
+  if (!bk_cp_ok(cp) || c > cp) return SISR_ERR_UNSUPPORTED;
+  if (!sisr_aligned16(dx)) return SISR_ERR_ALIGN;
+  const long HW = (long)H * W, n = HW * (cp / 4);
+  const dim3 grid((unsigned)((n + 255) / 256), B);
+  if (cp == 64)
+    hipLaunchKernelGGL(bk_map_mean_bwd_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, g, HW, c, (float)HW, dx);
+  else
+    hipLaunchKernelGGL(bk_map_mean_bwd_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, g, HW, c, (float)HW, dx);
   return sisr_check_launch();
 }
 

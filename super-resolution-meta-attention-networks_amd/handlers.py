@@ -565,6 +565,18 @@ class QModel(BaseModel):
             extra = self.scale_qpi(extra)
         return extra
 
+    def channels_from_codes(self, codes):
+        """(B, num_metadata) codes as a model estimated them (predictor.PredictorHandler) -> what generate_channels makes of
+        the same values: (B, num_metadata, 1, 1) fp32, through scale_qpi for the 'modulate' style.  The tensor stays where it
+        is (the 'modulate' curve is evaluated on the host, as for file metadata)."""
+        if codes.dim() != 2 or codes.shape[1] != self.num_metadata:
+            raise ValueError("%s takes codes of %d entries per image; got %s"
+                             % (type(self).__name__, self.num_metadata, tuple(codes.shape)))
+        extra = codes.detach().to(torch.float32)[:, :, None, None]
+        if self.style == 'modulate':
+            extra = self.scale_qpi(extra.cpu())
+        return extra
+
     def channel_concat_logic(self, x, extra_channels, metadata, metadata_keys):
         if extra_channels is None:
             extra_channels = self.generate_channels(x, metadata, metadata_keys)
@@ -698,6 +710,11 @@ try:  # SRCNN / VDSR (basic.py)
     HANDLERS += [SRCNNHandler, VDSRHandler]
 except ImportError:
     pass
+try:  # degradation predictor (predictor.py)
+    from .predictor import PredictorHandler
+    HANDLERS += [PredictorHandler]
+except ImportError:
+    pass
 # registry key = class name minus 'Handler', lower-cased (ref: models/__init__.py:26-30)
 available_models = {h.__name__.split('Handler')[0].lower(): h for h in HANDLERS}
 
@@ -759,7 +776,11 @@ class ModelInterface:
         if load_epoch not in ('best', 'last'):
             return load_epoch
         import pandas as pd
-        psnr = pd.read_csv(os.path.join(self.logs, 'summary.csv'))['val-PSNR']
+        summary = pd.read_csv(os.path.join(self.logs, 'summary.csv'))
+        if getattr(self.model, 'predicts_metadata', False):  # no images, no PSNR: the lowest val-loss
+            loss = summary['val-loss']
+            return loss.idxmin() if load_epoch == 'best' else len(loss) - 1
+        psnr = summary['val-PSNR']
         return psnr.idxmax() if load_epoch == 'best' else len(psnr) - 1
 
     def train_batch(self, lr, hr, **kwargs):

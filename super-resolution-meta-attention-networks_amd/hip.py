@@ -202,6 +202,15 @@ _SIGS.update({  # SRCNN / VDSR building blocks: K x K convs, the Y-channel ends,
     "sisr_mse_loss": (c_int, [P, P, c_long, P, P, P, P]),
 })
 
+_SIGS.update({  # degradation predictor: LeakyReLU forms of the K x K conv and its gradients, global mean of a map (csrc/basic.hip)
+    "sisr_convk_mfma_leaky": (c_int, [P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
+    "sisr_wgradk_mfma_leaky": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t,
+                                       c_float, P]),
+    "sisr_map_mean_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "sisr_map_mean": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    "sisr_map_mean_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
+})
+
 _SIGS.update({  # geometric self-ensemble: the eight flips / transposes of a batch and the mean of eight outputs (csrc/ensemble.hip)
     "sisr_dihedral_fan": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
     "sisr_dihedral_merge": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P]),

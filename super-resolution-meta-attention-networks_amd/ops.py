@@ -3789,12 +3789,12 @@ def convk_mfma(x, packed, bias, nbias, y, B, H, W, K, cin_p, cout_p, relu=False,
 
 
 class _ConvKxK(Function):
-    """K x K conv + bias (+ ReLU) between channels-last maps of 32 / 64 (padded) channels on the fp32 matrix cores
-    (ref: basic/architectures.py:45-52, the inner layers).  Backward: the input gradient is the same kernel on the flipped /
-    transposed packing; both gradient kernels read dy through the ReLU mask."""
+    """K x K conv + bias (+ ReLU, or LeakyReLU(slope)) between channels-last maps of 32 / 64 (padded) channels on the fp32
+    matrix cores (ref: basic/architectures.py:45-52, the inner layers).  Backward: the input gradient is the same kernel on
+    the flipped / transposed packing; both gradient kernels read dy through the activation's mask (the saved output)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, relu):
+    def forward(ctx, x, weight, bias, relu, slope):
         _fp32_only("conv_kxk")
         B, cip, H, W = x.shape
         co, ci = weight.shape[0], weight.shape[1]
@@ -3804,10 +3804,13 @@ class _ConvKxK(Function):
             raise RuntimeError(f"conv_kxk: weight takes {ci} channels, the map has {cip}")
         pf, pd = pack_convk(weight, need_dgrad=ctx.needs_input_grad[0])
         y = _empty_cl(B, cop, H, W, x.device)
-        convk_mfma(x, pf, bias, co if bias is not None else 0, y, B, H, W, K, cip, cop, relu=relu)
-        ctx.save_for_backward(x, y if relu else None, weight, pd)
+        if slope is None:
+            convk_mfma(x, pf, bias, co if bias is not None else 0, y, B, H, W, K, cip, cop, relu=relu)
+        else:
+            convk_mfma_leaky(x, pf, bias, co if bias is not None else 0, y, B, H, W, K, cip, cop, slope, act=True)
+        ctx.save_for_backward(x, y if (relu or slope is not None) else None, weight, pd)
         ctx.cfg = (B, H, W, K, co, ci, cop, cip)
-        ctx.bias = bias
+        ctx.bias, ctx.slope = bias, slope
         return y
 
     @staticmethod
@@ -3817,6 +3820,7 @@ class _ConvKxK(Function):
         try:
             x, y, weight, pd = ctx.saved_tensors
             B, H, W, K, co, ci, cop, cip = ctx.cfg
+            slope = ctx.slope
             dy = _cl(dy)
             L = hip.lib()
             dx = dw = db = None
@@ -3826,19 +3830,44 @@ class _ConvKxK(Function):
                 db = _grad_buf(ctx.bias) if want_db else None
                 nb = L.sisr_wgradk_mfma_workspace_bytes(B, H, W, K, cip, cop)
                 ws = hip.workspace(dy.device, nb)
-                hip.check(L.sisr_wgradk_mfma(hip.ptr(x), hip.ptr(dy), hip.ptr(y), hip.ptr(dwb), hip.ptr(db), B, H, W, K, co, ci,
-                                             cop, cip, hip.ptr(ws), nb, hip.stream()), "sisr_wgradk_mfma")
+                if slope is None:
+                    hip.check(L.sisr_wgradk_mfma(hip.ptr(x), hip.ptr(dy), hip.ptr(y), hip.ptr(dwb), hip.ptr(db), B, H, W, K, co,
+                                                 ci, cop, cip, hip.ptr(ws), nb, hip.stream()), "sisr_wgradk_mfma")
+                else:
+                    hip.check(L.sisr_wgradk_mfma_leaky(hip.ptr(x), hip.ptr(dy), hip.ptr(y), hip.ptr(dwb), hip.ptr(db), B, H, W,
+                                                       K, co, ci, cop, cip, hip.ptr(ws), nb, slope, hip.stream()),
+                              "sisr_wgradk_mfma_leaky")
                 dw = dwb if ctx.needs_input_grad[1] else None
             if ctx.needs_input_grad[0]:
                 dx = _empty_cl(B, cip, H, W, dy.device)
-                convk_mfma(dy, pd, None, 0, dx, B, H, W, K, cop, cip, in_mask=y)
-            return dx, dw, db, None
+                if slope is None:
+                    convk_mfma(dy, pd, None, 0, dx, B, H, W, K, cop, cip, in_mask=y)
+                else:
+                    convk_mfma_leaky(dy, pd, None, 0, dx, B, H, W, K, cop, cip, slope, in_mask=y)
+            return dx, dw, db, None, None
         finally:
             IN_BACKWARD = False
 
 
-def conv_kxk(x, weight, bias=None, relu=False):
-    return _ConvKxK.apply(x, weight, bias, bool(relu))
+def convk_mfma_leaky(x, packed, bias, nbias, y, B, H, W, K, cin_p, cout_p, slope, act=False, in_mask=None):
+    hip.check(hip.lib().sisr_convk_mfma_leaky(hip.ptr(x), hip.ptr(in_mask), hip.ptr(packed), hip.ptr(bias), int(nbias),
+                                              hip.ptr(y), B, H, W, K, cin_p, cout_p, int(act), float(slope), hip.stream()),
+              "sisr_convk_mfma_leaky")
+
+
+def conv_kxk(x, weight, bias=None, relu=False, slope=None):
+    """slope: LeakyReLU(slope) after the conv, through the leaky entry points (the ReLU path keeps its own selects)."""
+    if slope is not None:
+        if relu:
+            raise ValueError("conv_kxk: relu and slope are two activations; give one of them")
+        slope = float(slope)
+        if not (math.isfinite(slope) and slope >= 0):  # (the backward reads the sign of the pre-activation off the saved output)
+            raise ValueError(f"conv_kxk: the LeakyReLU slope must be finite and >= 0, got {slope}")
+    return _ConvKxK.apply(x, weight, bias, bool(relu), slope)
+
+
+# ----------------------------------------------------------------------------- global mean of a map (csrc/basic.hip)
+from .pool import map_mean  # noqa: E402,F401  (pool.py: the operator and its autograd node)
 
 
 # ----------------------------------------------------------------------------- MSE loss
