@@ -125,14 +125,19 @@ __device__ __forceinline__ TileCoord sisr_tile_decode_by_image(int tile, int til
 // conv3x3_c64_p4_kernel and conv3x3_c64_w4_kernel request the 6 x 34 pixel halo of the NEXT tile before / inside the K loop
 // of the current one (halo_issue: global -> registers) and write it to LDS after that loop (halo_commit).  Staging thread
 // map: tid -> (16-B piece c4 = tid & 15 of a pixel, halo columns pcol + {0, 16, 32} with pcol = tid >> 4), rows 0..5: 18
-// float4 per thread.  Every load is unconditional (clamped address); padding is zeroed by a mask when the halo is committed.
+// float4 per thread.  Every load is unconditional (clamped address); padding is zeroed when the halo is committed, by
+// decisions of the tile (halo_commit).
 typedef f32x4 halo_regs_t[HALO_H][3];
 // What every staging call of a kernel shares, built once at its top and passed in: with p.H and threadIdx.x read inside the
-// calls hipcc orders the commit's masks differently (18 more s_and_b64 -> vcc -> v_cndmask chains per commit), which costs
+// calls hipcc ordered the commit's masks differently (18 more s_and_b64 -> vcc -> v_cndmask chains per commit), which cost
 // p4's mask + affine form 0.25 % (profiles/README.md, round 12).
 struct HaloLane {
   int H, W, c4, pcol;
-  __device__ __forceinline__ HaloLane(const ConvParams& p, int tid) : H(p.H), W(p.W), c4(tid & 15), pcol(tid >> 4) {}
+  // lane-constant: the thread's k = 0 piece is halo column 0, its k = 2 piece is halo column HALO_W - 1 -- the only two pieces
+  // of a full-width tile that can lie left / right of the image (halo_commit)
+  bool col_first, col_last;
+  __device__ __forceinline__ HaloLane(const ConvParams& p, int tid)
+      : H(p.H), W(p.W), c4(tid & 15), pcol(tid >> 4), col_first((tid >> 4) == 0), col_last((tid >> 4) == 1) {}
 };
 
 // rows [r0, r1) of the halo of tile t, input chunk `chunk` (CHUNKS: the maps have more than one; else chunk 0)
@@ -155,13 +160,23 @@ __device__ __forceinline__ void halo_issue(halo_regs_t& v, const ConvParams& p, 
 
 // The staged halo of tile tc -> LDS image `lds` (pixel stride 64 floats, 16-B piece k of halo column c at slot
 // k ^ (c & 15)), through the prologue: AFFINE x * in_scale[b, c] + in_shift[b, c]; GATE x * in_scale[b, c] + gate_add, whose
-// in-image value the tile that owns the pixel also writes to gate_out.  Zero padding stays zero.  One input chunk.
+// in-image value the tile that owns the pixel also writes to gate_out.  Zero padding stays zero (+0).  One input chunk.
+// Padding is decided per tile, not per element (*Padding decided per tile*): what lies outside the image
+// is a scalar fact of the tile for all but two lane groups.
+//   halo row r            inside or outside for the whole workgroup: an outside row is written as +0 (over what the
+//                         loads brought), under one scalar branch per tile and one per row inside it
+//   full-width tile       (w0 + TW <= W) halo column 0 is outside only where w0 == 0, column 33 only where w0 + TW == W:
+//                         one select on ln.col_first for the k = 0 piece / on ln.col_last for the k = 2 piece, under a
+//                         scalar branch; the k = 1 piece is never outside
+//   width-ragged tile     the per-element predicate, as before
+// A piece inside the image is written as loaded (or as the prologue left it).  The decisions must reach the ISA as scalar
+// branches: hipcc turns `if (uniform) t = keep_if(t, lane)` into a select that every tile pays, and sinks the two sides' LDS
+// writes into one fed by selects, so each rarely taken side holds an empty `asm volatile` (neither speculated nor merged).
 template <bool AFFINE, bool GATE>
 __device__ __forceinline__ void halo_commit(const halo_regs_t& v, const ConvParams& p, const HaloLane& ln, const TileCoord& tc,
                                             float* lds) {
   const int H = ln.H, W = ln.W, c4 = ln.c4, pcol = ln.pcol;
   const int b = tc.b, h0 = tc.h0, w0 = tc.w0;
-  const bool interior = h0 >= 1 && h0 + TH + 1 <= H && w0 >= 1 && w0 + TW + 1 <= W;  // scalar
   f32x4 s4 = {1.f, 1.f, 1.f, 1.f}, t4 = {0.f, 0.f, 0.f, 0.f};
   if (AFFINE || GATE) s4 = *reinterpret_cast<const f32x4*>(p.in_scale + (long)b * 64 + c4 * 4);
   if (AFFINE && p.in_shift) t4 = *reinterpret_cast<const f32x4*>(p.in_shift + (long)b * 64 + c4 * 4);
@@ -171,35 +186,94 @@ __device__ __forceinline__ void halo_commit(const halo_regs_t& v, const ConvPara
   f32x4 u[GATE ? HALO_H : 1][3];
   if (GATE) {
     const sisr_rsrc_t ru = sisr_rsrc(p.gate_add + (long)b * p.xv.sB);
-#pragma unroll
-    for (int r = 0; r < HALO_H; ++r) {
-      const unsigned ro = (unsigned)(min(max(h0 - 1 + r, 0), H - 1) * (int)p.xv.sH) * 4u;
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-        if (k < 2 || pcol < 2)
-          u[r][k] = sisr_buf_load4(ru, (unsigned)(min(max(w0 - 1 + pcol + 16 * k, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u, ro);
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < HALO_H; ++r) {
-    const int gh = h0 - 1 + r;
-    const bool rok = gh >= 0 && gh < H;               // scalar
-    const bool rown = r >= 1 && r <= TH && gh < H;    // scalar: a row this tile owns
-    const unsigned ro = (unsigned)(min(max(gh, 0), H - 1) * (int)p.xv.sH) * 4u;
+    // piece by piece, the order in which a full-width tile consumes them below
 #pragma unroll
     for (int k = 0; k < 3; ++k)
       if (k < 2 || pcol < 2) {
-        const int col = pcol + 16 * k, gw = w0 - 1 + col;
-        const bool cok = gw >= 0 && gw < W && col < HALO_W;
-        f32x4 t = v[r][k];
-        if (AFFINE) t = t * s4 + t4;
-        if (GATE) {
-          t = sisr_mul_add4(t, s4, u[r][k]);
-          if (rown && cok && col >= 1 && col <= TW)
-            sisr_buf_store4(t, ro_, (unsigned)(min(max(gw, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u, ro);
-        }
-        if (!interior) t = sisr_keep_if(t, rok && cok);
-        *reinterpret_cast<f32x4*>(lds + r * (HALO_W * 64) + col * 64 + ((c4 ^ (col & 15)) << 2)) = t;
+        const unsigned go = (unsigned)(min(max(w0 - 1 + pcol + 16 * k, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u;
+#pragma unroll
+        for (int r = 0; r < HALO_H; ++r)
+          u[r][k] = sisr_buf_load4(ru, go, (unsigned)(min(max(h0 - 1 + r, 0), H - 1) * (int)p.xv.sH) * 4u);
       }
+  }
+  if (__builtin_expect(w0 + TW > W, 0)) {  // scalar: a width-ragged tile, per-element column predicates
+#pragma unroll
+    for (int r = 0; r < HALO_H; ++r) {
+      const int gh = h0 - 1 + r;
+      const bool rok = gh >= 0 && gh < H;               // scalar
+      const bool rown = r >= 1 && r <= TH && gh < H;    // scalar: a row this tile owns
+      const unsigned ro = (unsigned)(min(max(gh, 0), H - 1) * (int)p.xv.sH) * 4u;
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        if (k < 2 || pcol < 2) {
+          const int col = pcol + 16 * k, gw = w0 - 1 + col;
+          const bool cok = gw >= 0 && gw < W && col < HALO_W;
+          f32x4 t = v[r][k];
+          if (AFFINE) t = t * s4 + t4;
+          if (GATE) {
+            t = sisr_mul_add4(t, s4, u[r][k]);
+            if (rown && cok && col >= 1 && col <= TW)
+              sisr_buf_store4(t, ro_, (unsigned)(min(max(gw, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u, ro);
+          }
+          t = sisr_keep_if(t, rok && cok);
+          *reinterpret_cast<f32x4*>(lds + r * (HALO_W * 64) + col * 64 + ((c4 ^ (col & 15)) << 2)) = t;
+        }
+    }
+    asm volatile("");
+    return;
+  }
+  // A full-width tile, piece by piece (k outer): one scalar branch per edge around the six rows of its piece, not one per
+  // row -- a branch beside the MFMA stream is not free either.  Rows outside the image are overwritten with +0 afterwards
+  // (LDS writes of one wave land in program order); they are rare, one tile row in 32 at 128 rows.
+  const bool left = w0 == 0, right = w0 + TW == W;  // scalar: halo column 0 / HALO_W - 1 is outside the image
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    if (k < 2 || pcol < 2) {
+      const int col = pcol + 16 * k;
+      float* const dst = lds + col * 64 + ((c4 ^ (col & 15)) << 2);
+      f32x4 t[HALO_H];
+#pragma unroll
+      for (int r = 0; r < HALO_H; ++r) {
+        t[r] = v[r][k];
+        if (AFFINE) t[r] = t[r] * s4 + t4;
+        if (GATE) {
+          const int gh = h0 - 1 + r;
+          t[r] = sisr_mul_add4(t[r], s4, u[r][k]);
+          // the pixels this tile owns: rows 1 .. TH inside the image (scalar), halo columns 1 .. TW -- all of k = 1, k = 0
+          // but column 0, of k = 2 column 32 only (lane-constant)
+          if (r >= 1 && r <= TH && gh < H && (k == 1 || (k == 0 ? !ln.col_first : ln.col_first)))
+            sisr_buf_store4(t[r], ro_, (unsigned)(min(max(w0 - 1 + col, 0), W - 1) * (int)p.xv.sW + c4 * 4) * 4u,
+                            (unsigned)(min(max(gh, 0), H - 1) * (int)p.xv.sH) * 4u);
+        }
+      }
+      // each side of an edge branch writes for itself: one write behind the branch would copy t on the side that leaves
+      // it alone (a value that leaves a skipped branch in other registers than a taken one)
+      if (__builtin_expect((k == 0 && left) || (k == 2 && right), 0)) {
+#pragma unroll
+        for (int r = 0; r < HALO_H; ++r)
+          *reinterpret_cast<f32x4*>(dst + r * (HALO_W * 64)) = sisr_zero_if(t[r], k == 0 ? ln.col_first : ln.col_last);
+        asm volatile("");
+      } else {
+#pragma unroll
+        for (int r = 0; r < HALO_H; ++r) *reinterpret_cast<f32x4*>(dst + r * (HALO_W * 64)) = t[r];
+      }
+    }
+  if (__builtin_expect(h0 == 0 || h0 + TH + 1 > H, 0)) {  // scalar: some halo row is outside the image
+    // the zero is made here: a zero quad the compiler knows about is hoisted out of the tile loop and held in registers
+    f32x4 z;
+    asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0\n\tv_mov_b32 %2, 0\n\tv_mov_b32 %3, 0" : "=v"(z.x), "=v"(z.y), "=v"(z.z), "=v"(z.w));
+#pragma unroll
+    for (int r = 0; r < HALO_H; ++r) {
+      const int gh = h0 - 1 + r;
+      if (gh < 0 || gh >= H) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          if (k < 2 || pcol < 2) {
+            const int col = pcol + 16 * k;
+            *reinterpret_cast<f32x4*>(lds + r * (HALO_W * 64) + col * 64 + ((c4 ^ (col & 15)) << 2)) = z;
+          }
+      }
+    }
+    asm volatile("");
   }
 }

@@ -33,6 +33,12 @@ __device__ __forceinline__ f32x4 sisr_keep_if(f32x4 t, bool ok) {
   return __builtin_bit_cast(f32x4, b);
 }
 
+// +0 where `zero` (a condition that is constant per lane, held as a lane mask: one select per component and no mask
+// quad in registers), t elsewhere
+__device__ __forceinline__ f32x4 sisr_zero_if(f32x4 t, bool zero) {
+  return (f32x4){zero ? 0.f : t.x, zero ? 0.f : t.y, zero ? 0.f : t.z, zero ? 0.f : t.w};
+}
+
 // The gated skip t * g + x, with the product rounded BEFORE the sum (no fma contraction) -- the arithmetic of the
 // reference's `x * y` followed by `res += x` on fp32 tensors.  It is formed by the stand-alone gate kernel and by the
 // GATE prologues of the conv kernels, and all of them must agree to the bit, with each other and with the reference:

@@ -600,8 +600,15 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
     int b, h0, w0;
     decode(tile, b, h0, w0);
     const bool interior = h0 >= 1 && h0 + W4_TH + 1 <= H && w0 >= 1 && w0 + WT_W + 1 <= W;  // scalar
+    // Padding is decided per tile (*Padding decided per tile*).  In a tile whose pixels are all inside
+    // the image (scalar; every tile of a map that is a multiple of 4 x 32) the staged columns and the dY rows are inside
+    // too, and all that can be outside is a whole halo row -- row 0 where h0 == 0, the last where h0 + 4 == H -- which is
+    // overwritten with +0 behind the LDS writes, and the two edge columns, which keep their per-lane mask.  Ragged tiles
+    // keep the per-element masks.
+    const bool full = h0 + W4_TH <= H && w0 + WT_W <= W;  // scalar
+    const bool ragged = !interior && !full;
     const bool okc = w0 + pcol < W;
-    if (!interior) {
+    if (ragged) {
 #pragma unroll
       for (int r = 0; r < W4_HH; ++r) {
         const int gh = h0 - 1 + r;
@@ -609,6 +616,8 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
         st.x[r][0] = sisr_keep_if(st.x[r][0], ok);
         st.x[r][1] = sisr_keep_if(st.x[r][1], ok);
       }
+    }
+    if (!interior) {
       const int gwe = eside ? w0 + WT_W : w0 - 1, ghe = h0 - 1 + er;
       const bool oke = ghe >= 0 && ghe < H && gwe >= 0 && gwe < W;
       st.xe[0] = sisr_keep_if(st.xe[0], oke);
@@ -619,6 +628,19 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
     for (int r = 0; r < W4_HH; ++r) {
       *reinterpret_cast<f32x4*>(lx + r * (WH_W * 64)) = st.x[r][0];
       *reinterpret_cast<f32x4*>(lx + r * (WH_W * 64) + 32) = st.x[r][1];
+    }
+    if (!interior && full && (h0 == 0 || h0 + W4_TH == H)) {  // scalar: a halo row outside the image (LDS writes land in order)
+      f32x4 z;  // made here: a zero quad the compiler knows about is hoisted out of the tile loop and held in registers
+      asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0\n\tv_mov_b32 %2, 0\n\tv_mov_b32 %3, 0" : "=v"(z.x), "=v"(z.y), "=v"(z.z), "=v"(z.w));
+      if (h0 == 0) {
+        *reinterpret_cast<f32x4*>(lx) = z;
+        *reinterpret_cast<f32x4*>(lx + 32) = z;
+      }
+      if (h0 + W4_TH == H) {
+        *reinterpret_cast<f32x4*>(lx + (W4_HH - 1) * (WH_W * 64)) = z;
+        *reinterpret_cast<f32x4*>(lx + (W4_HH - 1) * (WH_W * 64) + 32) = z;
+      }
+      asm volatile("");
     }
     if (tid < 96) {
       float* le = ldx + (er * WH_W + (eside ? WH_W - 1 : 0)) * 64 + ec8 * 4;
@@ -643,7 +665,7 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_c64_w4_kernel(WgradParams p) 
         st.y[r][1] = st.y[r][1] * s4b + t4b;
       }
     }
-    if (!interior) {
+    if (ragged) {
 #pragma unroll
       for (int r = 0; r < W4_TH; ++r) {
         const bool ok = okc && h0 + r < H;
