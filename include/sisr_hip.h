@@ -749,6 +749,46 @@ int sisr_map_mean(const float* x, float* out, int B, int H, int W, int c, int cp
                   void* stream);
 int sisr_map_mean_bwd(const float* g, float* dx, int B, int H, int W, int c, int cp, void* stream);
 
+/* ---- stride-2 K x K conv on the fp32 matrix cores (csrc/basic.hip) ------------------------------------------------------
+ * nn.Conv2d(cin, cout, K, stride=2, padding=K/2), K odd, 1..9, between channels-last maps of 32 / 64 (padded) channels, with
+ * the packings of sisr_pack_convk and the refusals of the stride-1 forms (-1 null operand / bad size / NaN or infinite
+ * slope, -4 K or width outside the limits, -2 misaligned map).  H x W is ALWAYS the size of the conv's input x (and of dx);
+ * the strided side is Ho x Wo = sisr_convk_s2_out_size(H) x sisr_convk_s2_out_size(W), with
+ * sisr_convk_s2_out_size(n) = (n - 1) / 2 + 1 (0 for n < 1).  LeakyReLU family only; the slope is a per-call argument.
+ * sisr_convk_s2_mfma_leaky: y[b,ho,wo,co] = bias[co < nbias] + sum x[b,2ho+kh-K/2,2wo+kw-K/2,ci] w[co][ci][kh][kw] with
+ *   `packed` the forward packing; then with act != 0  y = y > 0 ? y : slope * y.  Only the outputs' own products are formed.
+ * sisr_dgradk_s2_mfma_leaky: dx (B,H,W,cin_p) = the transposed conv of dy' (B,Ho,Wo,cout_p) with `packed_dgrad`, the 'dgrad'
+ *   packing; dy' = dy, or with dymask (the layer's saved output)  dymask > 0 ? dy : slope * dy.  Polyphase: each (row parity,
+ *   column parity) class of dx is a stride-1 correlation of dy with the taps of that parity; no zero-inserted dy exists.
+ * sisr_wgradk_s2_mfma_leaky: dw[co][ci][kh][kw] = sum dy'[b,ho,wo,co] x[b,2ho+kh-K/2,2wo+kw-K/2,ci] and db (optional) =
+ *   the ordered column sum of dy'; dymask optional as above; workspace of sisr_wgradk_s2_mfma_workspace_bytes. */
+int sisr_convk_s2_out_size(int n);
+int sisr_convk_s2_mfma_leaky(const float* x, const float* packed, const float* bias, int nbias, float* y, int B, int H, int W,
+                             int K, int cin_p, int cout_p, int act, float slope, void* stream);
+int sisr_dgradk_s2_mfma_leaky(const float* dy, const float* dymask, const float* packed_dgrad, float* dx, int B, int H, int W,
+                              int K, int cout_p, int cin_p, float slope, void* stream);
+size_t sisr_wgradk_s2_mfma_workspace_bytes(int B, int H, int W, int K, int cin_p, int cout_p);
+int sisr_wgradk_s2_mfma_leaky(const float* x, const float* dy, const float* dymask, float* dw, float* db, int B, int H, int W,
+                              int K, int cout, int cin, int cop, int cip, float* workspace, size_t workspace_bytes,
+                              float slope, void* stream);
+
+/* ---- pointwise (1 x 1) layers up to 128 channels wide, with a per-image bias (csrc/basic.hip) --------------------------
+ * Channels-last maps of cin_p, cout_p in {32, 64, 128} (padded) channels; refusals as above (a width outside the three: -4).
+ * sisr_pack_conv1: (cout,cin[,1,1]) weight -> the MFMA order, fwd (cop*cip floats) and, when given, dgrad (roles swapped).
+ * sisr_conv1_mfma_leaky: y[b,pix,co] = bias[co] + ibias[b*nbias + co] (co < nbias; either pointer may be null) +
+ *   sum_ci x'[b,pix,ci] w[co][ci], then with act != 0 the LeakyReLU(slope); x' = x, or with in_mask (the input-gradient
+ *   form on the dgrad packing: x is dy, in_mask the saved output)  in_mask > 0 ? x : slope * x.
+ * sisr_wgrad1_mfma_leaky: dw (cout,cin), and optionally db (cout) and dib (B x cout: the gradient of ibias, the per-image
+ *   column sum of dy') from x and dy' = dymask > 0 ? dy : slope * dy (dymask optional).  Every sum is ordered, without
+ *   atomics: a repeat is bit-identical.  workspace: sisr_wgrad1_mfma_workspace_bytes. */
+int sisr_pack_conv1(const float* w, float* fwd, float* dgrad, int cout, int cin, int cop, int cip, void* stream);
+int sisr_conv1_mfma_leaky(const float* x, const float* in_mask, const float* packed, const float* bias, const float* ibias,
+                          int nbias, float* y, int B, int H, int W, int cin_p, int cout_p, int act, float slope, void* stream);
+size_t sisr_wgrad1_mfma_workspace_bytes(int B, int H, int W, int cin_p, int cout_p);
+int sisr_wgrad1_mfma_leaky(const float* x, const float* dy, const float* dymask, float* dw, float* db, float* dib, int B, int H,
+                           int W, int cout, int cin, int cop, int cip, float* workspace, size_t workspace_bytes, float slope,
+                           void* stream);
+
 /* ---- geometric self-ensemble around a network (csrc/ensemble.hip) -----------------------------------------------------
  * The eight flips / transposes of an image batch as two batches a network runs as they are, and the mean of its eight
  * outputs with each mapped back (the "+" protocol of the EDSR / RCAN / HAN / SAN papers).  All maps contiguous NCHW fp32;

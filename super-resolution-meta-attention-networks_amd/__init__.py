@@ -5,7 +5,8 @@ Import with ``importlib.import_module("super-resolution-meta-attention-networks_
 architectures (drop-in nn.Modules), handlers (model-handler API), parallel (RCCL data parallelism),
 metrics (PSNR), basic (SRCNN / VDSR), ensemble (x8 geometric self-ensemble for evaluation),
 perceptual (VGG19 feature loss), structural (SSIM loss term), multiscale (MS-SSIM loss term),
-frequency (FFT L1 loss term), predictor (degradation code from an LR image), pool (global mean of a map).
+frequency (FFT L1 loss term), predictor (degradation code from an LR image), corrector (IKC's correction of that code from
+an SR image), pool (global mean of a map), convs (stride-2 K x K conv, pointwise layers up to 128 wide).
 """
-from . import hip, ops, optim, architectures, metrics, handlers, parallel, han, san, srmd, sftmd, sparnet, basic, degrade, data, ensemble, perceptual, structural, multiscale, frequency, pool, predictor, cli  # noqa: F401
+from . import hip, ops, optim, architectures, metrics, handlers, parallel, han, san, srmd, sftmd, sparnet, basic, degrade, data, ensemble, perceptual, structural, multiscale, frequency, pool, convs, predictor, corrector, cli  # noqa: F401
 from .handlers import ModelInterface, available_models  # noqa: F401

@@ -304,6 +304,35 @@ def _load_predictor(cfg, models):
     return predictor
 
 
+def _load_corrector(cfg, predictor):
+    """The `ikc = { corrector = [experiment, epoch], iterations = 7 }` model of an evaluation -> (model | None, iterations).
+    It corrects the code of `metadata_predictor`, which is required with it and must estimate the same `metadata` list (so
+    every listed Q-model, checked against the predictor, takes the corrected code as well)."""
+    key = cfg.get('ikc')
+    if not key:
+        return None, 0
+    if predictor is None:
+        raise ValueError("ikc: the loop corrects the code of metadata_predictor; set metadata_predictor = [experiment, epoch] "
+                         "with it")
+    name, ep = key['corrector']
+    iterations = int(key.get('iterations', 7))
+    if iterations < 1:
+        raise ValueError("ikc: iterations must be at least 1 (got %r)" % (iterations,))
+    use_ema = bool(cfg.get('use_ema'))
+    if use_ema:  # the averaged weights when the corrector's run kept an average; its trained ones otherwise
+        stored = _load_toml(os.path.join(cfg['model_loc'], name, 'config.toml'))['model']['internal_params']
+        use_ema = stored.get('ema_decay') is not None
+    corrector = ModelInterface(cfg['model_loc'], name, gpu='single' if cfg.get('gpu') else 'off', sp_gpu=cfg.get('sp_gpu', 0),
+                               mode='eval', load_epoch=ep if ep in ('best', 'last') else int(ep), ema=use_ema)
+    if not hasattr(corrector.model, 'correct'):
+        raise ValueError("ikc: experiment %r holds a %r model, which corrects no degradation code" % (name, corrector.name))
+    if list(corrector.model.metadata) != list(predictor.model.metadata):
+        raise ValueError("ikc: the corrector %r corrects the metadata %s, the predictor %r estimates %s; the two lists must be "
+                         "the same, in the same order" % (name, list(corrector.model.metadata), predictor.experiment,
+                                                          list(predictor.model.metadata)))
+    return corrector, iterations
+
+
 def _code_columns(handler):
     """one column name per entry of a handler's code: the key itself, or key_<i> for a key of several entries"""
     names = []
@@ -313,9 +342,9 @@ def _code_columns(handler):
     return names
 
 
-def _code_rows(handler, batch, codes, have_file):
+def _code_rows(handler, batch, codes, have_file, iteration=None):
     """rows of predicted_metadata.csv for a batch: the code entries and, next to a metadata file, the mean absolute
-    difference from the file's code"""
+    difference from the file's code; iteration (under `ikc`): the loop iteration the codes belong to, 0 = the predictor's"""
     host = codes.detach().cpu()
     names = _code_columns(handler)
     mae = None
@@ -324,7 +353,8 @@ def _code_rows(handler, batch, codes, have_file):
         mae = (host.double() - want.double()).abs().mean(dim=1).tolist()
     rows = []
     for i, tag in enumerate(batch['tag']):
-        row = {'Image_Name': tag, **{n: float(v) for n, v in zip(names, host[i].tolist())}}
+        row = {'Image_Name': tag, **({} if iteration is None else {'iteration': iteration}),
+               **{n: float(v) for n, v in zip(names, host[i].tolist())}}
         if mae is not None:
             row['code_MAE'] = mae[i]
         rows.append(row)
@@ -334,9 +364,10 @@ def _code_rows(handler, batch, codes, have_file):
 def _with_predicted_codes(handler, predictor, batch, codes):
     """The batch a Q-model is given when its code comes from the predictor: the file's metadata is taken out and the
     predicted code goes in as `extra_channels` (QModel.channels_from_codes), on the model's device.  Handlers that build their
-    own metadata maps in run_eval (SRMD, SFTMD) get the code as the batch's metadata instead, keyed entry by entry."""
+    own metadata maps, in run_eval (SRMD) or in generate_channels (SFTMD), get the code as the batch's metadata instead, keyed
+    entry by entry."""
     feed = {k: v for k, v in batch.items() if k not in ('metadata', 'metadata_keys')}
-    if type(handler).run_eval is QModel.run_eval:
+    if type(handler).run_eval is QModel.run_eval and type(handler).generate_channels is QModel.generate_channels:
         extra = handler.channels_from_codes(codes)
         feed['extra_channels'] = extra if handler.device == torch.device('cpu') else extra.to(handler.device)
         return feed
@@ -355,6 +386,9 @@ def eval_sisr(config=None, **kw):
     ('interp' models), or the up-sampled batch in YCbCr (the Y-channel models).  The up-sampled batch is made once per batch
     (on the device when the models run there), or read from `lr_dir_interp`.  `lr_baseline = true` adds 'LR' rows: the
     up-sampled image itself against the HR image (the reference always writes them).  `self_ensemble = true` evaluates
+    `ikc = { corrector = ["<experiment>", <epoch>], iterations = 7 }` (with `metadata_predictor`) runs IKC's correction loop
+    on the predictor's code (corrector.CorrectorHandler.correct) and gives every Q-model the final code; their rows carry
+    '<experiment>~ikc' and predicted_metadata.csv one row per image and iteration.  `self_ensemble = true` evaluates
     every model with the geometric self-ensemble (run_eval(self_ensemble=True), the papers' "+" rows): its rows and its image
     folder carry the name '<experiment>+'; the LR rows are unaffected.  `use_ema = true` loads every listed model from the
     averaged weights of its checkpoint ('network_ema', stored by a run with ema_decay; a checkpoint without them is an
@@ -381,6 +415,7 @@ def eval_sisr(config=None, **kw):
             raise Exception('The model loaded has been trained for a different scale, '
                             'and cannot produce the requested images.')
     predictor = _load_predictor(cfg, models)
+    corrector, ikc_iterations = _load_corrector(cfg, predictor)
     code_rows = []
     lr_dir = cfg['lr_dir']
     meta = cfg.get('metadata_file') or os.path.join(lr_dir, 'degradation_metadata.csv')
@@ -398,7 +433,8 @@ def eval_sisr(config=None, **kw):
     baseline = bool(cfg.get('lr_baseline'))
     plus = {'self_ensemble': True} if cfg.get('self_ensemble') else {}
     suffix = ('@ema' if cfg.get('use_ema') else '') + ('+' if plus else '')
-    label = lambda m: m.experiment + suffix  # noqa: E731
+    # rows and image folders of the Q-models that ran on the corrected code carry '<experiment>~ikc' (before '@ema' and '+')
+    label = lambda m: m.experiment + ('~ikc' if corrector is not None and isinstance(m.model, QModel) else '') + suffix  # noqa: E731
     y_models = [m for m in models if 'rgb' not in m.configuration['colorspace']]
     need_interp = baseline or bool(y_models) or any(m.configuration['input'] != 'unmodified' for m in models)
     need_ycbcr = baseline or bool(y_models)
@@ -445,7 +481,12 @@ def eval_sisr(config=None, **kw):
         codes = None
         if predictor is not None:  # on the LR batch as read: RGB, before any interpolation
             codes, _, _ = predictor.model.run_eval(batch['lr'], keep_on_device=True)
-            code_rows.extend(_code_rows(predictor.model, batch, codes, have_file=meta is not None))
+            if corrector is None:
+                code_rows.extend(_code_rows(predictor.model, batch, codes, have_file=meta is not None))
+            else:  # IKC's loop on the image as read (the self-ensemble's eight variants all get the final code)
+                _, codes, history = corrector.model.correct(batch['lr'], codes, ikc_iterations, want_sr=False)
+                for iteration, h in enumerate(history):
+                    code_rows.extend(_code_rows(predictor.model, batch, h, have_file=meta is not None, iteration=iteration))
         for m in models:
             feed = batch
             if codes is not None and isinstance(m.model, QModel):

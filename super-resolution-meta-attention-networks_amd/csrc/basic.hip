@@ -21,6 +21,9 @@
 //                      the layer's saved output m (one more template flag; the ReLU forms keep their own selects).
 //   sisr_map_mean, sisr_map_mean_bwd   global mean of a map's real channels (ordered two-stage float64 sum) and its gradient:
 //                      the degradation predictor's head (predictor.py).
+//   sisr_convk_s2_mfma_leaky, sisr_dgradk_s2_mfma_leaky, sisr_wgradk_s2_mfma_leaky   the stride-2 conv (padding K/2) and its
+//                      gradients: a forward kernel that forms only its own outputs' products, the transposed conv as four
+//                      stride-1 phases, and the weight-gradient kernel with a strided x index (IKC's predictor).
 //
 // Within a lane the contraction index of the 32x32x2 MFMA is permuted (lane half h takes channels 16 h + kk at step kk), so
 // both operands are read 16 bytes at a time; A and B use the same permutation, so the sum is over the same products.
@@ -38,6 +41,7 @@ static inline bool bk_cp_ok(int cp) { return cp == 32 || cp == 64; }
 static inline bool bk_dims_ok(int B, int H, int W) {
   return B > 0 && H > 0 && W > 0 && B <= 65535 && (long)B * H * W <= (1L << 28);
 }
+static inline int bk_s2_out(int n) { return (n - 1) / 2 + 1; }  // output size of a stride-2 conv with padding K / 2, K odd
 
 // ------------------------------------------------------------------------------------------------ Y -> features
 template <int CP>
@@ -457,10 +461,14 @@ extern "C" int sisr_convk_mfma_leaky(const float* x, const float* in_mask, const
 // two pixels per MFMA (lane half h takes pixel w0 + h).  The 4 waves take every 4th row of the slice; their tiles are summed
 // in wave order through LDS and written as slice s's partial.
 // LEAKY: dy is scaled by `slope` where dymask <= 0 instead of zeroed (the layer's activation was a LeakyReLU).
-template <int MT, bool LEAKY>
+// ST: the conv's stride.  dy (and dymask) is B x H x W; at ST = 2 x is B x Hx x Wx and dy pixel (h, w) meets x pixel
+// (2 h + kh - p, 2 w + kw - p); at ST = 1 the two sizes are the same.
+template <int MT, bool LEAKY, int ST = 1>
 __global__ __launch_bounds__(256) void bk_wgradk_mfma_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                              const float* __restrict__ dymask, float* __restrict__ part,
-                                                             int B, int H, int W, int K, int cip, int S, float slope) {
+                                                             int B, int H, int W, int K, int cip, int S, float slope,
+                                                             int Hx_, int Wx_) {
+  const int Hx = ST == 1 ? H : Hx_, Wx = ST == 1 ? W : Wx_;
   __shared__ float red[4][MT][16 * 64];
   constexpr int cop = MT * 32;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, h = lane >> 5, i = lane & 31;
@@ -472,17 +480,17 @@ __global__ __launch_bounds__(256) void bk_wgradk_mfma_kernel(const float* __rest
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
   for (int R = r_begin + wave; R < r_end; R += 4) {
-    const int b = R / H, hx = R % H + kh - p;
-    if (hx < 0 || hx >= H) continue;  // wave-uniform
+    const int b = R / H, hx = ST * (R % H) + kh - p;
+    if (hx < 0 || hx >= Hx) continue;  // wave-uniform
     const float* dyr = dy + (long)R * W * cop;
     const float* mr = dymask ? dymask + (long)R * W * cop : nullptr;
-    const float* xr = x + ((long)b * H + hx) * W * cip + chunk * 32 + i;
+    const float* xr = x + ((long)b * Hx + hx) * Wx * cip + chunk * 32 + i;
     for (int wq = 0; wq < W; wq += 16) {  // eight pixel pairs at a time: their loads are in flight together
       float av[8][MT], bv[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
-        const int wd = wq + 2 * u + h, wx = wd + kw - p;
-        const bool okd = wd < W, okx = okd && wx >= 0 && wx < W;
+        const int wd = wq + 2 * u + h, wx = ST * wd + kw - p;
+        const bool okd = wd < W, okx = okd && wx >= 0 && wx < Wx;
         const float xv = xr[(long)(okx ? wx : 0) * cip];
         bv[u] = okx ? xv : 0.f;
 #pragma unroll
@@ -577,27 +585,34 @@ static int bk_colsum_parts(long npix, int cp) {
   return (int)(n < BK_PARTS ? n : BK_PARTS);
 }
 
-extern "C" size_t sisr_wgradk_mfma_workspace_bytes(int B, int H, int W, int K, int cin_p, int cout_p) {
+// H x W: the size of x; dy has H x W pixels at stride 1 and bk_s2_out(H) x bk_s2_out(W) at stride 2
+static size_t bk_wgradk_ws_bytes(int B, int H, int W, int K, int cin_p, int cout_p, int stride) {
   if (!bk_dims_ok(B, H, W) || !bk_k_ok(K) || !bk_cp_ok(cin_p) || !bk_cp_ok(cout_p)) return 0;
-  return sizeof(float) * ((size_t)bk_wgrad_slices(B, H, K, cin_p) * cout_p * cin_p * K * K + (size_t)BK_PARTS * cout_p);
+  const int Hd = stride == 2 ? bk_s2_out(H) : H;
+  return sizeof(float) * ((size_t)bk_wgrad_slices(B, Hd, K, cin_p) * cout_p * cin_p * K * K + (size_t)BK_PARTS * cout_p);
 }
 
-template <bool LEAKY>
+extern "C" size_t sisr_wgradk_mfma_workspace_bytes(int B, int H, int W, int K, int cin_p, int cout_p) {
+  return bk_wgradk_ws_bytes(B, H, W, K, cin_p, cout_p, 1);
+}
+
+template <bool LEAKY, int ST = 1>
 static int bk_wgradk_mfma(const float* x, const float* dy, const float* dymask, float* dw, float* db, int B, int H, int W,
                           int K, int cout, int cin, int cop, int cip, float* workspace, size_t workspace_bytes, float slope,
                           void* stream) {
   if (!x || !dy || !dw || !workspace || !bk_dims_ok(B, H, W) || cout < 1 || cin < 1) return SISR_ERR_ARG;
   if (!bk_k_ok(K) || !bk_cp_ok(cop) || !bk_cp_ok(cip) || cout > cop || cin > cip) return SISR_ERR_UNSUPPORTED;
-  if (workspace_bytes < sisr_wgradk_mfma_workspace_bytes(B, H, W, K, cip, cop)) return SISR_ERR_ARG;
+  if (workspace_bytes < bk_wgradk_ws_bytes(B, H, W, K, cip, cop, ST)) return SISR_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int S = bk_wgrad_slices(B, H, K, cip), KK = K * K;
+  const int Hd = ST == 2 ? bk_s2_out(H) : H, Wd = ST == 2 ? bk_s2_out(W) : W;  // dy's size
+  const int S = bk_wgrad_slices(B, Hd, K, cip), KK = K * K;
   const dim3 grid(KK, cip / 32, S);
   if (cop == 64)
-    hipLaunchKernelGGL((bk_wgradk_mfma_kernel<2, LEAKY>), grid, dim3(256), 0, s, x, dy, dymask, workspace, B, H, W, K, cip, S,
-                       slope);
+    hipLaunchKernelGGL((bk_wgradk_mfma_kernel<2, LEAKY, ST>), grid, dim3(256), 0, s, x, dy, dymask, workspace, B, Hd, Wd, K,
+                       cip, S, slope, H, W);
   else
-    hipLaunchKernelGGL((bk_wgradk_mfma_kernel<1, LEAKY>), grid, dim3(256), 0, s, x, dy, dymask, workspace, B, H, W, K, cip, S,
-                       slope);
+    hipLaunchKernelGGL((bk_wgradk_mfma_kernel<1, LEAKY, ST>), grid, dim3(256), 0, s, x, dy, dymask, workspace, B, Hd, Wd, K,
+                       cip, S, slope, H, W);
   int rc = sisr_check_launch();
   if (rc) return rc;
   const long n = (long)cout * cin * KK;
@@ -606,7 +621,7 @@ static int bk_wgradk_mfma(const float* x, const float* dy, const float* dymask, 
   rc = sisr_check_launch();
   if (rc || !db) return rc;
   float* bpart = workspace + (size_t)S * cop * cip * KK;
-  const long npix = (long)B * H * W;
+  const long npix = (long)B * Hd * Wd;
   const int parts = bk_colsum_parts(npix, cop);
   if (cop == 64)
     hipLaunchKernelGGL((bk_colsum_kernel<64, LEAKY>), dim3(parts), dim3(256), 0, s, dy, dymask, npix, bpart, slope);
@@ -630,6 +645,438 @@ extern "C" int sisr_wgradk_mfma_leaky(const float* x, const float* dy, const flo
                                       size_t workspace_bytes, float slope, void* stream) {
   if (!dymask || !(slope == slope) || slope - slope != 0.f) return SISR_ERR_ARG;
   return bk_wgradk_mfma<true>(x, dy, dymask, dw, db, B, H, W, K, cout, cin, cop, cip, workspace, workspace_bytes, slope, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ stride-2 K x K conv
+// nn.Conv2d(cin, cout, K, stride=2, padding=K/2) between channels-last maps: x is B x H x W, y is B x Ho x Wo with
+// Ho = (H - 1) / 2 + 1.  Same implicit GEMM, packing and lane layout as bk_convk_mfma_kernel; LeakyReLU family only.
+//
+// Forward: output tile of 4 rows x 32 columns, one row (one M-tile) per wave.  Its input halo is (K + 6) x (2 (32 + K/2))
+// pixels, staged 32 channels at a time with the even and the odd input columns apart: [row][column parity][column / 2].
+// Lane i of a tap (kh, kw) then reads column-pair i + kw/2 of parity kw & 1, so neighbouring lanes stay BK_XS floats apart
+// as in the stride-1 kernel (interleaved, they would be 2 BK_XS apart: two lanes per bank group).  Only the outputs' own
+// products are formed.  LDS: 63 KB (K = 1), 84 KB (3), 105 KB (5), 128 KB (7), 152 KB (9): one workgroup per CU from K = 3.
+#define BK_S2_TH 4
+
+static size_t bk_s2_lds(int K) { return sizeof(float) * (size_t)(2 * BK_S2_TH + K - 2) * 2 * (BK_TW + K / 2) * BK_XS; }
+
+template <int NT>
+__global__ __launch_bounds__(256) void bk_convk_s2_kernel(const float* __restrict__ x, const float* __restrict__ wp,
+                                                          const float* __restrict__ bias, int nbias, float* __restrict__ y,
+                                                          int H, int W, int Ho, int Wo, int K, int cin_p, int act,
+                                                          float slope) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // [LH][2][LWH][BK_XS]
+  constexpr int cout_p = NT * 32;
+  const int p = K / 2, LWH = BK_TW + p, LH = 2 * BK_S2_TH + K - 2;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, h = lane >> 5, i = lane & 31;
+  const int b = blockIdx.z, h0 = blockIdx.y * BK_S2_TH, w0 = blockIdx.x * BK_TW;
+  f32x16 acc[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
+  const int groups = cin_p / 16;
+  for (int ch = 0; ch < cin_p / 32; ++ch) {
+    __syncthreads();
+    for (int idx = tid; idx < LH * 2 * LWH * 8; idx += 256) {
+      const int pix = idx >> 3, q = idx & 7;
+      const int lr = pix / (2 * LWH), par = pix % (2 * LWH) / LWH, half = pix % LWH;
+      const int hh = 2 * h0 - p + lr, ww = 2 * w0 - p + 2 * half + par;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (hh >= 0 && hh < H && ww >= 0 && ww < W)
+        v = *reinterpret_cast<const f32x4*>(x + (((long)b * H + hh) * W + ww) * cin_p + ch * 32 + q * 4);
+      *reinterpret_cast<f32x4*>(lds + pix * BK_XS + q * 4) = v;
+    }
+    __syncthreads();
+    for (int kh = 0; kh < K; ++kh)
+      for (int kw = 0; kw < K; ++kw) {
+        const int tap = kh * K + kw;
+        f32x4 bf[NT][4], af[4];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+          const f32x4* bp =
+              reinterpret_cast<const f32x4*>(wp + (((long)tap * groups + ch * 2 + h) * cout_p + nt * 32 + i) * 16);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) bf[nt][q] = bp[q];
+        }
+        const f32x4* ap = reinterpret_cast<const f32x4*>(
+            lds + (((2 * wave + kh) * 2 + (kw & 1)) * LWH + i + (kw >> 1)) * BK_XS + h * 16);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) af[q] = ap[q];
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk)
+#pragma unroll
+          for (int nt = 0; nt < NT; ++nt)
+            acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk >> 2][kk & 3], bf[nt][kk >> 2][kk & 3], acc[nt], 0, 0, 0);
+      }
+  }
+  const int ho = h0 + wave;
+  if (ho >= Ho) return;
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int co = nt * 32 + i;
+    const float bv = (bias && co < nbias) ? bias[co] : 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int wo = w0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+      if (wo >= Wo) continue;
+      float v = acc[nt][r] + bv;
+      if (act) v = v > 0.f ? v : slope * v;
+      y[(((long)b * Ho + ho) * Wo + wo) * cout_p + co] = v;
+    }
+  }
+}
+
+static inline bool bk_slope_ok(float slope) { return slope == slope && slope - slope == 0.f; }  // neither NaN nor infinite
+
+extern "C" int sisr_convk_s2_out_size(int n) { return n > 0 ? bk_s2_out(n) : 0; }
+
+extern "C" int sisr_convk_s2_mfma_leaky(const float* x, const float* packed, const float* bias, int nbias, float* y, int B,
+                                        int H, int W, int K, int cin_p, int cout_p, int act, float slope, void* stream) {
+  if (!x || !packed || !y || !bk_dims_ok(B, H, W) || nbias < 0 || !bk_slope_ok(slope)) return SISR_ERR_ARG;
+  if (!bk_k_ok(K) || !bk_cp_ok(cin_p) || !bk_cp_ok(cout_p) || nbias > cout_p) return SISR_ERR_UNSUPPORTED;
+  if (!sisr_aligned16(x) || !sisr_aligned16(packed)) return SISR_ERR_ALIGN;
+  const int Ho = bk_s2_out(H), Wo = bk_s2_out(W);
+  const dim3 grid((Wo + BK_TW - 1) / BK_TW, (Ho + BK_S2_TH - 1) / BK_S2_TH, B);
+  const size_t lds = bk_s2_lds(K);  // 9 x 9: 152 KB of the CU's 160
+  if (cout_p == 64) {
+    SISR_ALLOW_LDS(bk_convk_s2_kernel<2>, bk_s2_lds(BK_MAXK));
+    hipLaunchKernelGGL(bk_convk_s2_kernel<2>, grid, dim3(256), lds, (hipStream_t)stream, x, packed, bias, nbias, y, H, W, Ho,
+                       Wo, K, cin_p, act, slope);
+  } else {
+    SISR_ALLOW_LDS(bk_convk_s2_kernel<1>, bk_s2_lds(BK_MAXK));
+    hipLaunchKernelGGL(bk_convk_s2_kernel<1>, grid, dim3(256), lds, (hipStream_t)stream, x, packed, bias, nbias, y, H, W, Ho,
+                       Wo, K, cin_p, act, slope);
+  }
+  return sisr_check_launch();
+}
+
+// Input gradient (the transposed conv), polyphase: dx pixel (2a + rp, 2c + cq) takes only the taps kh = rp + p (mod 2),
+// kw = cq + p (mod 2), and over those it is a stride-1 correlation of dy: dx[2a + rp] += dy[a + (rp + p - kh) / 2] w[kh].
+// A workgroup takes one phase (rp, cq) and 8 x 32 of its pixels (a, c); the dy halo is at most (8 + p) x (32 + p) pixels
+// (K = 5: the sub-kernels are 3x3, 3x2, 2x3, 2x2 taps).  No zero is inserted anywhere: the MFMA count is that of the forward.
+// At K = 1 the odd phases have no tap and are written as zero.  wp: the 'dgrad' packing of sisr_pack_convk (taps flipped).
+// NT counts dx's channel tiles; cop is dy's (padded) width, the contraction.
+template <int NT>
+__global__ __launch_bounds__(256) void bk_dgradk_s2_kernel(const float* __restrict__ dy, const float* __restrict__ dymask,
+                                                           const float* __restrict__ wp, float* __restrict__ dx, int H, int W,
+                                                           int Ho, int Wo, int K, int cop, float slope) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // [LH * LW][BK_XS]
+  constexpr int cip = NT * 32;
+  const int p = K / 2, tx = gridDim.x >> 1, ty = gridDim.y >> 1;
+  const int cq = blockIdx.x >= tx, rp = blockIdx.y >= ty;
+  const int b = blockIdx.z, a0 = (blockIdx.y - rp * ty) * BK_TH, c0 = (blockIdx.x - cq * tx) * BK_TW;
+  if (2 * a0 + rp >= H || 2 * c0 + cq >= W) return;  // (the odd phases can be a tile shorter; block-uniform)
+  const int kh0 = (rp + p) & 1, kw0 = (cq + p) & 1, nkh = (K - kh0 + 1) / 2, nkw = (K - kw0 + 1) / 2;
+  const int LH = BK_TH + nkh - 1, LW = BK_TW + nkw - 1;
+  // LDS row lr holds dy row a0 + lr + rofs: tap j (kh = kh0 + 2j) of output row a reads lr = a - a0 + nkh - 1 - j
+  const int rofs = (rp + p - kh0) / 2 - (nkh - 1), cofs = (cq + p - kw0) / 2 - (nkw - 1);
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, h = lane >> 5, i = lane & 31;
+  f32x16 acc[2][NT];
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
+  const int groups = cop / 16, chunks = (nkh && nkw) ? cop / 32 : 0;
+  for (int ch = 0; ch < chunks; ++ch) {
+    __syncthreads();
+    for (int idx = tid; idx < LH * LW * 8; idx += 256) {
+      const int pix = idx >> 3, q = idx & 7;
+      const int hh = a0 + pix / LW + rofs, ww = c0 + pix % LW + cofs;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (hh >= 0 && hh < Ho && ww >= 0 && ww < Wo) {
+        const long o = (((long)b * Ho + hh) * Wo + ww) * cop + ch * 32 + q * 4;
+        v = *reinterpret_cast<const f32x4*>(dy + o);
+        if (dymask) {
+          const f32x4 m = *reinterpret_cast<const f32x4*>(dymask + o);
+          v.x = m.x > 0.f ? v.x : slope * v.x; v.y = m.y > 0.f ? v.y : slope * v.y;
+          v.z = m.z > 0.f ? v.z : slope * v.z; v.w = m.w > 0.f ? v.w : slope * v.w;
+        }
+      }
+      *reinterpret_cast<f32x4*>(lds + pix * BK_XS + q * 4) = v;
+    }
+    __syncthreads();
+    for (int j = 0; j < nkh; ++j)
+      for (int l = 0; l < nkw; ++l) {
+        const int tap = K * K - 1 - ((kh0 + 2 * j) * K + kw0 + 2 * l);  // the flipped packing's index of (kh, kw)
+        f32x4 bf[NT][4], af[2][4];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+          const f32x4* bp = reinterpret_cast<const f32x4*>(wp + (((long)tap * groups + ch * 2 + h) * cip + nt * 32 + i) * 16);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) bf[nt][q] = bp[q];
+        }
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+          const f32x4* ap = reinterpret_cast<const f32x4*>(
+              lds + ((wave * 2 + mt + nkh - 1 - j) * LW + i + nkw - 1 - l) * BK_XS + h * 16);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) af[mt][q] = ap[q];
+        }
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk)
+#pragma unroll
+          for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+              acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[mt][kk >> 2][kk & 3], bf[nt][kk >> 2][kk & 3],
+                                                                 acc[mt][nt], 0, 0, 0);
+      }
+  }
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt) {
+    const int hx = 2 * (a0 + wave * 2 + mt) + rp;
+    if (hx >= H) continue;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const int ci = nt * 32 + i;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int wx = 2 * (c0 + (r & 3) + 8 * (r >> 2) + 4 * h) + cq;
+        if (wx >= W) continue;
+        dx[(((long)b * H + hx) * W + wx) * cip + ci] = acc[mt][nt][r];
+      }
+    }
+  }
+}
+
+static size_t bk_s2_dgrad_lds(int K) { return sizeof(float) * (size_t)(BK_TH + K / 2) * (BK_TW + K / 2) * BK_XS; }
+
+// H, W: the size of dx (odd and even sizes share Ho); dymask (optional): the layer's saved output
+extern "C" int sisr_dgradk_s2_mfma_leaky(const float* dy, const float* dymask, const float* packed_dgrad, float* dx, int B,
+                                         int H, int W, int K, int cout_p, int cin_p, float slope, void* stream) {
+  if (!dy || !packed_dgrad || !dx || !bk_dims_ok(B, H, W) || !bk_slope_ok(slope)) return SISR_ERR_ARG;
+  if (!bk_k_ok(K) || !bk_cp_ok(cin_p) || !bk_cp_ok(cout_p)) return SISR_ERR_UNSUPPORTED;
+  if (!sisr_aligned16(dy) || !sisr_aligned16(dymask) || !sisr_aligned16(packed_dgrad)) return SISR_ERR_ALIGN;
+  const int Ho = bk_s2_out(H), Wo = bk_s2_out(W);  // = the even phase's pixel count, the larger of the two
+  const dim3 grid(2 * ((Wo + BK_TW - 1) / BK_TW), 2 * ((Ho + BK_TH - 1) / BK_TH), B);
+  const size_t lds = bk_s2_dgrad_lds(K);  // 9 x 9: 62 KB
+  if (cin_p == 64)
+    hipLaunchKernelGGL(bk_dgradk_s2_kernel<2>, grid, dim3(256), lds, (hipStream_t)stream, dy, dymask, packed_dgrad, dx, H, W,
+                       Ho, Wo, K, cout_p, slope);
+  else
+    hipLaunchKernelGGL(bk_dgradk_s2_kernel<1>, grid, dim3(256), lds, (hipStream_t)stream, dy, dymask, packed_dgrad, dx, H, W,
+                       Ho, Wo, K, cout_p, slope);
+  return sisr_check_launch();
+}
+
+// Weight / bias gradient: bk_wgradk_mfma_kernel with the strided x index, slices over dy's B * Ho rows.  H, W: the size of x.
+// dymask (the layer's saved output) is optional: without it the layer had no activation.
+extern "C" size_t sisr_wgradk_s2_mfma_workspace_bytes(int B, int H, int W, int K, int cin_p, int cout_p) {
+  return bk_wgradk_ws_bytes(B, H, W, K, cin_p, cout_p, 2);
+}
+
+extern "C" int sisr_wgradk_s2_mfma_leaky(const float* x, const float* dy, const float* dymask, float* dw, float* db, int B,
+                                         int H, int W, int K, int cout, int cin, int cop, int cip, float* workspace,
+                                         size_t workspace_bytes, float slope, void* stream) {
+  if (!bk_slope_ok(slope)) return SISR_ERR_ARG;
+  return bk_wgradk_mfma<true, 2>(x, dy, dymask, dw, db, B, H, W, K, cout, cin, cop, cip, workspace, workspace_bytes, slope,
+                                 stream);
+}
+
+// ------------------------------------------------------------------------------------------------ pointwise (1 x 1) layers
+// y[b,pix,:] = act(bias + ibias[b] + W x[b,pix,:]) between channels-last maps of 32 / 64 / 128 channels: the same implicit
+// GEMM with no halo, so the A operand goes from global memory to registers (16 bytes at a time, the lane layout of the LDS
+// reads above) and there is no LDS and no barrier.  A workgroup takes 256 pixels of ONE image (blockIdx.z): the per-image
+// bias is a vector per workgroup.  A workgroup makes NT * 32 <= 64 output channels; at 128 outputs blockIdx.y names the
+// 64-channel half (all four N-tiles in one wave, NT = 4, compile to 168 VGPRs + 128 AGPRs, one wave per SIMD, with nothing
+// but occupancy to hide the loads behind; the halves are 105 + 64, two waves per SIMD, and the second read of x comes
+// from L2).  With the 'dgrad' packing and in_mask it is the input gradient.  Packing: sisr_pack_conv1 = bk_pack_kernel at
+// one tap.
+static inline bool bk_pw_cp_ok(int cp) { return cp == 32 || cp == 64 || cp == 128; }
+
+template <int NT>
+__global__ __launch_bounds__(256) void bk_pw_kernel(const float* __restrict__ x, const float* __restrict__ in_mask,
+                                                    const float* __restrict__ wp, const float* __restrict__ bias,
+                                                    const float* __restrict__ ibias, int nbias, float* __restrict__ y, int HW,
+                                                    int cin_p, int cout_p, int act, float slope) {
+  const int n0 = blockIdx.y * NT * 32;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, h = lane >> 5, i = lane & 31;
+  const int b = blockIdx.z, p0 = blockIdx.x * 256 + wave * 64;
+  const long base = (long)b * HW;
+  f32x16 acc[2][NT];
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
+  for (int ch = 0; ch < cin_p / 32; ++ch) {
+    f32x4 bf[NT][4], af[2][4];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+      const int pix = p0 + mt * 32 + i;  // (a pixel past the image reads pixel 0: its row of D is never stored)
+      const long o = (base + (pix < HW ? pix : 0)) * cin_p + ch * 32 + h * 16;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        f32x4 v = *reinterpret_cast<const f32x4*>(x + o + q * 4);
+        if (in_mask) {
+          const f32x4 m = *reinterpret_cast<const f32x4*>(in_mask + o + q * 4);
+          v.x = m.x > 0.f ? v.x : slope * v.x; v.y = m.y > 0.f ? v.y : slope * v.y;
+          v.z = m.z > 0.f ? v.z : slope * v.z; v.w = m.w > 0.f ? v.w : slope * v.w;
+        }
+        af[mt][q] = v;
+      }
+    }
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const f32x4* bp = reinterpret_cast<const f32x4*>(wp + ((long)(ch * 2 + h) * cout_p + n0 + nt * 32 + i) * 16);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) bf[nt][q] = bp[q];
+    }
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk)
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+          acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[mt][kk >> 2][kk & 3], bf[nt][kk >> 2][kk & 3], acc[mt][nt],
+                                                             0, 0, 0);
+  }
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int co = n0 + nt * 32 + i;
+    float bv = 0.f;
+    if (co < nbias) {
+      if (bias) bv = bias[co];
+      if (ibias) bv += ibias[(long)b * nbias + co];
+    }
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int pix = p0 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        if (pix >= HW) continue;
+        float v = acc[mt][nt][r] + bv;
+        if (act) v = v > 0.f ? v : slope * v;
+        y[(base + pix) * cout_p + co] = v;
+      }
+  }
+}
+
+extern "C" int sisr_pack_conv1(const float* w, float* fwd, float* dgrad, int cout, int cin, int cop, int cip, void* stream) {
+  if (!w || !fwd || cout < 1 || cin < 1) return SISR_ERR_ARG;
+  if (!bk_pw_cp_ok(cop) || !bk_pw_cp_ok(cip) || cout > cop || cin > cip) return SISR_ERR_UNSUPPORTED;
+  const long n = (long)cop * cip;
+  hipLaunchKernelGGL(bk_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, fwd, dgrad, 1,
+                     cout, cin, cop, cip);
+  return sisr_check_launch();
+}
+
+// bias (nbias values) and ibias (B x nbias, one row per image) are optional and added before the activation
+extern "C" int sisr_conv1_mfma_leaky(const float* x, const float* in_mask, const float* packed, const float* bias,
+                                     const float* ibias, int nbias, float* y, int B, int H, int W, int cin_p, int cout_p,
+                                     int act, float slope, void* stream) {
+  if (!x || !packed || !y || !bk_dims_ok(B, H, W) || nbias < 0 || !bk_slope_ok(slope)) return SISR_ERR_ARG;
+  if (!bk_pw_cp_ok(cin_p) || !bk_pw_cp_ok(cout_p) || nbias > cout_p) return SISR_ERR_UNSUPPORTED;
+  if (!sisr_aligned16(x) || !sisr_aligned16(in_mask) || !sisr_aligned16(packed)) return SISR_ERR_ALIGN;
+  const int HW = H * W;
+  const dim3 grid((HW + 255) / 256, cout_p == 128 ? 2 : 1, B);
+  hipStream_t s = (hipStream_t)stream;
+  if (cout_p == 32)
+    hipLaunchKernelGGL(bk_pw_kernel<1>, grid, dim3(256), 0, s, x, in_mask, packed, bias, ibias, nbias, y, HW, cin_p, cout_p,
+                       act, slope);
+  else
+    hipLaunchKernelGGL(bk_pw_kernel<2>, grid, dim3(256), 0, s, x, in_mask, packed, bias, ibias, nbias, y, HW, cin_p, cout_p,
+                       act, slope);
+  return sisr_check_launch();
+}
+
+// Per-image column sums of the (masked) dy: part (b, k) sums every gridDim.x-th group of G pixels of image b, the groups in
+// order through LDS; bk_pw_colsum_final_kernel sums an image's parts in order (d ibias), bk_pw_bias_kernel the images (db).
+template <int CP>
+__global__ __launch_bounds__(256) void bk_pw_colsum_kernel(const float* __restrict__ dy, const float* __restrict__ dymask,
+                                                           int HW, float* __restrict__ part, float slope) {
+  constexpr int G = 256 / CP;
+  __shared__ float red[256];
+  const int c = threadIdx.x % CP, g = threadIdx.x / CP;
+  const long base = (long)blockIdx.y * HW;
+  float s = 0.f;
+  for (int pix = blockIdx.x * G + g; pix < HW; pix += gridDim.x * G) {
+    float v = dy[(base + pix) * CP + c];
+    if (dymask) v = dymask[(base + pix) * CP + c] > 0.f ? v : slope * v;
+    s += v;
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  if (g == 0) {
+    float t = red[c];
+    for (int k = 1; k < G; ++k) t += red[k * CP + c];
+    part[((long)blockIdx.y * gridDim.x + blockIdx.x) * CP + c] = t;
+  }
+}
+
+__global__ __launch_bounds__(128) void bk_pw_colsum_final_kernel(const float* __restrict__ part, int nparts, int cp, int cout,
+                                                                 float* __restrict__ isum, float* __restrict__ dib) {
+  const int c = threadIdx.x, b = blockIdx.x;
+  if (c >= cp) return;
+  float s = 0.f;
+  for (int k = 0; k < nparts; ++k) s += part[((long)b * nparts + k) * cp + c];
+  isum[(long)b * cp + c] = s;
+  if (dib && c < cout) dib[(long)b * cout + c] = s;
+}
+
+__global__ __launch_bounds__(128) void bk_pw_bias_kernel(const float* __restrict__ isum, int B, int cp, int cout,
+                                                         float* __restrict__ db) {
+  const int c = threadIdx.x;
+  if (c >= cout) return;
+  float s = 0.f;
+  for (int b = 0; b < B; ++b) s += isum[(long)b * cp + c];
+  db[c] = s;
+}
+
+static int bk_pw_colsum_parts(int B, int HW, int cp) {
+  const int G = 256 / cp, want = (HW + G - 1) / G, cap = BK_PARTS / B > 0 ? BK_PARTS / B : 1;
+  return want < cap ? want : cap;
+}
+
+extern "C" size_t sisr_wgrad1_mfma_workspace_bytes(int B, int H, int W, int cin_p, int cout_p) {
+  if (!bk_dims_ok(B, H, W) || !bk_pw_cp_ok(cin_p) || !bk_pw_cp_ok(cout_p)) return 0;
+  return sizeof(float) * ((size_t)bk_wgrad_slices(B, H, 1, cin_p) * cout_p * cin_p +
+                          ((size_t)bk_pw_colsum_parts(B, H * W, cout_p) + 1) * B * cout_p);
+}
+
+// dw (cout, cin) from x and dy' = dymask > 0 ? dy : slope * dy (dymask optional: no activation), by bk_wgradk_mfma_kernel at
+// one tap; db (cout) and dib (B x cout, the gradient of the per-image bias), both optional, from the per-image column sums.
+extern "C" int sisr_wgrad1_mfma_leaky(const float* x, const float* dy, const float* dymask, float* dw, float* db, float* dib,
+                                      int B, int H, int W, int cout, int cin, int cop, int cip, float* workspace,
+                                      size_t workspace_bytes, float slope, void* stream) {
+  if (!x || !dy || !dw || !workspace || !bk_dims_ok(B, H, W) || cout < 1 || cin < 1 || !bk_slope_ok(slope)) return SISR_ERR_ARG;
+  if (!bk_pw_cp_ok(cop) || !bk_pw_cp_ok(cip) || cout > cop || cin > cip) return SISR_ERR_UNSUPPORTED;
+  if (workspace_bytes < sisr_wgrad1_mfma_workspace_bytes(B, H, W, cip, cop)) return SISR_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const int S = bk_wgrad_slices(B, H, 1, cip);
+  const dim3 grid(1, cip / 32, S);
+  switch (cop) {
+    case 128: hipLaunchKernelGGL((bk_wgradk_mfma_kernel<4, true>), grid, dim3(256), 0, s, x, dy, dymask, workspace, B, H, W, 1, cip, S, slope, H, W); break;
+    case 64: hipLaunchKernelGGL((bk_wgradk_mfma_kernel<2, true>), grid, dim3(256), 0, s, x, dy, dymask, workspace, B, H, W, 1, cip, S, slope, H, W); break;
+    default: hipLaunchKernelGGL((bk_wgradk_mfma_kernel<1, true>), grid, dim3(256), 0, s, x, dy, dymask, workspace, B, H, W, 1, cip, S, slope, H, W); break;
+  }
+  int rc = sisr_check_launch();
+  if (rc) return rc;
+  const long n = (long)cout * cin;
+  hipLaunchKernelGGL(bk_wgradk_final_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, workspace, S, 1, cout, cin,
+                     cop, cip, dw);
+  rc = sisr_check_launch();
+  if (rc || (!db && !dib)) return rc;
+  const int HW = H * W, parts = bk_pw_colsum_parts(B, HW, cop);
+  float* part = workspace + (size_t)S * cop * cip;
+  float* isum = part + (size_t)parts * B * cop;
+  const dim3 cgrid(parts, B);
+  switch (cop) {
+    case 128: hipLaunchKernelGGL(bk_pw_colsum_kernel<128>, cgrid, dim3(256), 0, s, dy, dymask, HW, part, slope); break;
+    case 64: hipLaunchKernelGGL(bk_pw_colsum_kernel<64>, cgrid, dim3(256), 0, s, dy, dymask, HW, part, slope); break;
+    default: hipLaunchKernelGGL(bk_pw_colsum_kernel<32>, cgrid, dim3(256), 0, s, dy, dymask, HW, part, slope); break;
+  }
+  rc = sisr_check_launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL(bk_pw_colsum_final_kernel, dim3(B), dim3(128), 0, s, part, parts, cop, cout, isum, dib);
+  rc = sisr_check_launch();
+  if (rc || !db) return rc;
+  hipLaunchKernelGGL(bk_pw_bias_kernel, dim3(1), dim3(128), 0, s, isum, B, cop, cout, db);
+  return sisr_check_launch();
 }
 
 // ------------------------------------------------------------------------------------------------ global mean of a map

@@ -715,6 +715,11 @@ try:  # degradation predictor (predictor.py)
     HANDLERS += [PredictorHandler]
 except ImportError:
     pass
+try:  # IKC's corrector (corrector.py)
+    from .corrector import CorrectorHandler
+    HANDLERS += [CorrectorHandler]
+except ImportError:
+    pass
 # registry key = class name minus 'Handler', lower-cased (ref: models/__init__.py:26-30)
 available_models = {h.__name__.split('Handler')[0].lower(): h for h in HANDLERS}
 

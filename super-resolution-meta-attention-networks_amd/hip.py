@@ -211,6 +211,23 @@ _SIGS.update({  # degradation predictor: LeakyReLU forms of the K x K conv and i
     "sisr_map_mean_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
 })
 
+_SIGS.update({  # stride-2 K x K conv on the fp32 matrix cores and its two gradients (csrc/basic.hip)
+    "sisr_convk_s2_out_size": (c_int, [c_int]),
+    "sisr_convk_s2_mfma_leaky": (c_int, [P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
+    "sisr_dgradk_s2_mfma_leaky": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
+    "sisr_wgradk_s2_mfma_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "sisr_wgradk_s2_mfma_leaky": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t,
+                                          c_float, P]),
+})
+
+_SIGS.update({  # pointwise (1 x 1) layers up to 128 channels wide with a per-image bias (csrc/basic.hip)
+    "sisr_pack_conv1": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
+    "sisr_conv1_mfma_leaky": (c_int, [P, P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
+    "sisr_wgrad1_mfma_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "sisr_wgrad1_mfma_leaky": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, c_float,
+                                       P]),
+})
+
 _SIGS.update({  # geometric self-ensemble: the eight flips / transposes of a batch and the mean of eight outputs (csrc/ensemble.hip)
     "sisr_dihedral_fan": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
     "sisr_dihedral_merge": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P]),

@@ -3855,15 +3855,26 @@ def convk_mfma_leaky(x, packed, bias, nbias, y, B, H, W, K, cin_p, cout_p, slope
               "sisr_convk_mfma_leaky")
 
 
-def conv_kxk(x, weight, bias=None, relu=False, slope=None):
-    """slope: LeakyReLU(slope) after the conv, through the leaky entry points (the ReLU path keeps its own selects)."""
+def conv_kxk(x, weight, bias=None, relu=False, slope=None, stride=1):
+    """slope: LeakyReLU(slope) after the conv, through the leaky entry points (the ReLU path keeps its own selects).
+    stride: 1, or 2 (output (H - 1) // 2 + 1 rows; LeakyReLU or no activation -- there is no ReLU form at stride 2)."""
+    if stride not in (1, 2):
+        raise ValueError(f"conv_kxk: strides 1 and 2 only, got {stride!r}")
     if slope is not None:
         if relu:
             raise ValueError("conv_kxk: relu and slope are two activations; give one of them")
         slope = float(slope)
         if not (math.isfinite(slope) and slope >= 0):  # (the backward reads the sign of the pre-activation off the saved output)
             raise ValueError(f"conv_kxk: the LeakyReLU slope must be finite and >= 0, got {slope}")
+    if stride == 2:
+        if relu:
+            raise ValueError("conv_kxk: stride 2 is built for the LeakyReLU family only; relu=True needs stride 1")
+        return conv_kxk_s2(x, weight, bias, slope)
     return _ConvKxK.apply(x, weight, bias, bool(relu), slope)
+
+
+# ----------------------------------------------------------------------------- stride-2 K x K conv, pointwise layers
+from .convs import conv_1x1, conv_kxk_s2, conv_s2_out_size  # noqa: E402,F401  (convs.py: the operators and their nodes)
 
 
 # ----------------------------------------------------------------------------- global mean of a map (csrc/basic.hip)

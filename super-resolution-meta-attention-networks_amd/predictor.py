@@ -1,11 +1,12 @@
 """Degradation predictor: a small regression CNN that estimates a degradation code from an LR image, so the meta-attention
 networks can run on images that come with no metadata file.
 
-It is the Predictor of IKC (Gu et al., "Blind Super-Resolution With Iterative Kernel Correction", CVPR 2019) without its one
-stride-2 layer (the K x K kernels are stride 1): `num_layers` K x K convolutions, each followed by LeakyReLU(slope) -- the last
-one included, as in IKC -- and a global mean over the map.  The reference tree has no counterpart.  Routing of the layers:
+It is the Predictor of IKC (Gu et al., "Blind Super-Resolution With Iterative Kernel Correction", CVPR 2019): `num_layers`
+K x K convolutions, each followed by LeakyReLU(slope) -- the last one included, as in IKC -- and a global mean over the map.
+`strides` gives each layer's stride, 1 or 2: None is all ones (the net without IKC's one stride-2 layer),
+[1, 1, 1, 2, 1, 1] is IKC's.  The reference tree has no counterpart.  Routing of the layers:
   input (B, in_channels, H, W)     ops.nchw_to_nhwc_pad(cp=32)   planar image -> channels-last map, channels zero-padded
-  every layer                      ops.conv_kxk(slope=...)       K x K implicit GEMM on the fp32 matrix cores, leaky forms
+  every layer                      ops.conv_kxk(slope, stride)   K x K implicit GEMM on the fp32 matrix cores, leaky forms
   output                           ops.map_mean                  (B, num_outputs) means of the last map's real channels
 `layer_dict` names the layers conv_<i> as basic.SRCNN does, so state-dict keys are layer_dict.conv_<i>.weight / .bias (OIHW).
 """
@@ -20,7 +21,8 @@ MAX_KERNEL, MAX_WIDTH, MAX_INPUT = 9, 64, 32
 
 
 class DegradationPredictor(nn.Module):
-    def __init__(self, in_channels=3, num_outputs=1, num_features=64, num_layers=6, kernel_size=5, slope=0.2):
+    def __init__(self, in_channels=3, num_outputs=1, num_features=64, num_layers=6, kernel_size=5, slope=0.2,
+                 strides=None):
         super().__init__()
         if not 1 <= num_outputs <= MAX_WIDTH:
             raise NotImplementedError("num_outputs: the predictor estimates 1 to %d code entries (got %r); "
@@ -33,12 +35,16 @@ class DegradationPredictor(nn.Module):
             raise NotImplementedError("num_layers: at least two layers (got %r)" % (num_layers,))
         if not 1 <= in_channels <= MAX_INPUT:
             raise NotImplementedError("in_channels: images of 1 to %d channels only (got %r)" % (MAX_INPUT, in_channels))
+        strides = [1] * num_layers if strides is None else [int(s) for s in strides]
+        if len(strides) != num_layers or any(s not in (1, 2) for s in strides):
+            raise NotImplementedError("strides: one stride of 1 or 2 per layer, %d of them (got %r)" % (num_layers, strides))
         self.in_channels, self.num_outputs, self.depth, self.slope = in_channels, num_outputs, num_layers, float(slope)
+        self.strides = strides
         widths = [in_channels] + [num_features] * (num_layers - 1) + [num_outputs]
         self.layer_dict = nn.ModuleDict()
         for index in range(num_layers):
             self.layer_dict['conv_{}'.format(index)] = nn.Conv2d(widths[index], widths[index + 1], kernel_size=kernel_size,
-                                                                 padding=kernel_size // 2)
+                                                                 stride=strides[index], padding=kernel_size // 2)
 
     def forward(self, x):
         if not x.is_cuda:
@@ -50,7 +56,7 @@ class DegradationPredictor(nn.Module):
         t = ops.nchw_to_nhwc_pad(x.detach(), cp=32)
         for index in range(self.depth):
             m = self.layer_dict['conv_{}'.format(index)]
-            t = ops.conv_kxk(t, m.weight, m.bias, slope=self.slope)
+            t = ops.conv_kxk(t, m.weight, m.bias, slope=self.slope, stride=self.strides[index])
         return ops.map_mean(t, self.num_outputs)
 
     def reset_parameters(self):
@@ -64,12 +70,13 @@ class PredictorHandler(QModel):
     predicts_metadata = True
 
     def __init__(self, device, model_save_dir, eval_mode=False, lr=1e-4, scale=None, in_features=3, num_features=64,
-                 num_layers=6, kernel_size=5, slope=0.2, scheduler=None, scheduler_params=None, perceptual=None, **kwargs):
+                 num_layers=6, kernel_size=5, slope=0.2, strides=None, scheduler=None, scheduler_params=None, perceptual=None,
+                 **kwargs):
         super().__init__(device=device, model_save_dir=model_save_dir, eval_mode=eval_mode, **kwargs)
         if perceptual is not None:
             raise NotImplementedError("predictor: the output is a degradation code, a perceptual loss has nothing to read")
         self.net = DegradationPredictor(in_channels=in_features, num_outputs=self.num_metadata, num_features=num_features,
-                                        num_layers=num_layers, kernel_size=kernel_size, slope=slope)
+                                        num_layers=num_layers, kernel_size=kernel_size, slope=slope, strides=strides)
         self.colorspace = 'rgb'
         self.im_input = 'unmodified'
         self.criterion = MSELoss()
