@@ -10,29 +10,11 @@ The pyramid drops a trailing odd row or column (F.avg_pool2d(t, 2)); pytorch_mss
 values differ on such images.  A handler builds the term when its model parameter `ms_ssim_loss` is set
 (handlers.BaseModel.training_setup), with the scale weights of `ms_ssim_weights`; unset, nothing changes.
 """
-import ctypes
 import math
 
-import torch
 from torch import nn
-from torch.autograd import Function
 
 from . import ops
-
-
-class _MsSsimMean(Function):
-    """the node of ops.ms_ssim_mean: ops._SsimMean bound to sisr_ms_ssim, with the scale weights and no per-plane output"""
-
-    @staticmethod
-    def forward(ctx, sr, y, data_range, weights, want_grad):
-        wv = (ctypes.c_double * len(weights))(*weights)  # host memory, read by the call and not kept
-        return ops._value_and_grad(ctx, sr, y, data_range, want_grad, "sisr_ms_ssim", (len(weights),),
-                                   (wv, len(weights), None))
-
-    @staticmethod
-    def backward(ctx, go):
-        (grad,) = ctx.saved_tensors
-        return grad * go, None, None, None, None
 
 
 class MultiScaleStructuralMechanism(nn.Module):

@@ -1,10 +1,10 @@
 """Global mean of a channels-last map, both ways (csrc/basic.hip: sisr_map_mean, sisr_map_mean_bwd): the pooling at the end of
 the degradation predictor (predictor.py).  ops.map_mean is this module's map_mean.  The attention gates' global_avg_pool
-(64-multiples, fused into their conv launches) is another operator and stays in ops.py."""
+(64-multiples, fused into their conv launches) is another operator, in ops_attention.py."""
 import torch
 from torch.autograd import Function
 
-from . import hip, ops
+from . import convs, hip, ops
 
 
 class _MapMean(Function):
@@ -16,7 +16,7 @@ class _MapMean(Function):
     def forward(ctx, x, channels):
         ops._fp32_only("map_mean")
         B, cp, H, W = x.shape
-        x = ops._check_map(x, "map_mean")
+        x = convs._check_map(x, "map_mean")
         if not 1 <= channels <= cp:
             raise RuntimeError(f"map_mean: {channels} real channels in a map of {cp}")
         L = hip.lib()

@@ -15,6 +15,8 @@ Two kinds of data:
 tests/test_autograd_contract_cpu.py checks the table against ops.py (every Function has a case or an exclusion reason) and
 runs every builder, restatement and budget on the host; tests/test_autograd_contract_gpu.py runs the contract.
 """
+import importlib
+
 import torch
 import torch.nn.functional as F
 
@@ -222,6 +224,11 @@ SEED = {"res_block_ca": 303, "res_block_ca_meta": 303, "gated_group_meta": 521, 
         "sftmd_head": 1238, "sftmd_tail": 1302}
 
 CASES = []
+
+
+def family(ops, name):
+    """the module `name` beside ops.py (ops_sftmd, ...): private nodes are not re-exported by ops"""
+    return importlib.import_module("." + name, ops.__package__)
 
 
 def case(*a, **k):
@@ -625,7 +632,7 @@ def _nl(name, quadrants):
     # phi's bias shifts every logit of a row alike: its exact gradient is 0, so it is compared on the scale of phi's weight
     # gradient, as the cited test does
     return case(name, ["_NonLocalBlock"], build,
-                lambda ops, t: ops._NonLocalBlock.apply(t["x"], quadrants, *[t[n] for n in _NLP]), ref, ("x",) + _NLP,
+                lambda ops, t: family(ops, "ops_attention")._NonLocalBlock.apply(t["x"], quadrants, *[t[n] for n in _NLP]), ref, ("x",) + _NLP,
                 params=_NLP, maps=("x",), crit=NL_BLOCK, sizes=SIZES2, rel_scale={"bp": "wp"})
 
 
@@ -655,12 +662,12 @@ def _sft_ref(t):  # StandardSft as the reference writes it (test_sft_layer_match
 
 
 case("sft_layer", ["_SftLayer"], _sft_build,
-     lambda ops, t: ops._SftLayer.apply(t["x"], ops.nchw_to_nhwc_pad(t["md"], 64), True, MD, *[t[n] for n in _SFT]), _sft_ref,
+     lambda ops, t: family(ops, "ops_sftmd")._SftLayer.apply(t["x"], ops.nchw_to_nhwc_pad(t["md"], 64), True, MD, *[t[n] for n in _SFT]), _sft_ref,
      ("x",) + _SFT, params=_SFT, maps=("x",), crit=SFT_LAYER, sizes=SIZES2)
 case("concat_sft", ["_ConcatSft"],
      lambda H, W, k: dict(x=xi((B, 64, H, W), 1210 + 17 * k), md=xi((B, MD, H, W), 1211 + 17 * k),
                           w=wq((64, 64 + MD, 3, 3), 230), b=bi(64, 231), cot=xi((B, 64, H, W), 1212 + 17 * k)),
-     lambda ops, t: ops._ConcatSft.apply(t["x"], ops.nchw_to_nhwc_pad(t["md"], 64), t["w"], t["b"]),
+     lambda ops, t: family(ops, "ops_sftmd")._ConcatSft.apply(t["x"], ops.nchw_to_nhwc_pad(t["md"], 64), t["w"], t["b"]),
      lambda t: X.conv_ref(torch.cat((t["x"], t["md"]), 1), t["w"], t["b"]), ("x", "w", "b"), params=("w", "b"), maps=("x",))
 _HEAD = ("w1", "b1", "w2", "b2", "w3", "b3")
 
@@ -674,7 +681,7 @@ case("sftmd_head", ["_SftmdHead"],
      lambda H, W, k: dict(x=ru((B, 3, H, W), SEED["sftmd_head"] + 17 * k), w1=rn((64, 3, 3, 3), 240, 0.2), b1=rn((64,), 241, 0.1),
                           w2=rn((64, 64, 3, 3), 242, 0.05), b2=rn((64,), 243, 0.1), w3=rn((64, 64, 3, 3), 244, 0.05),
                           b3=rn((64,), 245, 0.1), cot=rn((B, 64, H, W), SEED["sftmd_head"] + 1 + 17 * k)),
-     lambda ops, t: ops._SftmdHead.apply(t["x"], *[t[n] for n in _HEAD]), _head_ref, _HEAD, params=_HEAD, sink=("w2", "w3"),
+     lambda ops, t: family(ops, "ops_sftmd")._SftmdHead.apply(t["x"], *[t[n] for n in _HEAD]), _head_ref, _HEAD, params=_HEAD, sink=("w2", "w3"),
      crit=SFTMD_NET, sizes=RSIZES[:2])  # (at 37 x 70 two convs rectify 660 000 sums: no seed keeps them all off zero)
 _TAIL = ("wm", "bm", "wu", "bu", "wo", "bo")
 
@@ -689,7 +696,7 @@ case("sftmd_tail", ["_SftmdTail"],
      lambda H, W, k: dict(fea=rn((B, 64, H, W), SEED["sftmd_tail"] + 17 * k, 0.5), wm=rn((64, 64, 3, 3), 250, 0.05), bm=rn((64,), 251, 0.1),
                           wu=rn((256, 64, 3, 3), 252, 0.05), bu=rn((256,), 253, 0.1), wo=rn((3, 64, 9, 9), 254, 0.01),
                           bo=torch.full((3,), 0.5), cot=rn((B, 3, 2 * H, 2 * W), SEED["sftmd_tail"] + 1 + 17 * k)),
-     lambda ops, t: ops._SftmdTail.apply(t["fea"], 1, *[t[n] for n in _TAIL]), _tail_ref, ("fea",) + _TAIL, params=_TAIL,
+     lambda ops, t: family(ops, "ops_sftmd")._SftmdTail.apply(t["fea"], 1, *[t[n] for n in _TAIL]), _tail_ref, ("fea",) + _TAIL, params=_TAIL,
      sink=("wm", "wu"), maps=("fea",), cot_map=False, crit=SFTMD_NET, sizes=SIZES2)
 
 
@@ -700,7 +707,7 @@ def _affine(seed):
 
 case("batch_norm_act", ["_BatchNormAct"],
      lambda H, W, k: dict(x=rn((B, 64, H, W), 1300 + 17 * k, 1.7) + 0.4, cot=rn((B, 64, H, W), 1301 + 17 * k), **_affine(260)),
-     lambda ops, t: ops._BatchNormAct.apply(t["x"], t["gamma"], t["beta"], None, None, True, 0.0, 1e-5, 0.2),
+     lambda ops, t: family(ops, "ops_sparnet")._BatchNormAct.apply(t["x"], t["gamma"], t["beta"], None, None, True, 0.0, 1e-5, 0.2),
      lambda t: F.leaky_relu(F.batch_norm(t["x"], None, None, t["gamma"], t["beta"], True, 0.0, 1e-5), 0.2),
      ("x", "gamma", "beta"), params=("gamma", "beta"), maps=("x",), crit=BN_F64, sizes=SIZES2)
 # group statistics are the batch-norm kernels' arithmetic over another index set; the per-kernel bounds of
@@ -742,6 +749,9 @@ EXCLUDED = {
     "_L1Loss": "no parameters and one differentiable input (the target takes no gradient), scalar output",
     "_MSELoss": "no parameters and one differentiable input (the target takes no gradient), scalar output",
     "_SsimMean": "no parameters and one differentiable input (the target is refused if it requires grad), scalar output",
+    "_MsSsimMean": "no parameters and one differentiable input (the target is refused if it requires grad), scalar output",
+    "_ConvKxKS2": "convs.py's stride-2 node: its contract is held by tests/test_convs_contract_gpu.py",
+    "_Conv1x1": "convs.py's pointwise node: its contract is held by tests/test_convs_contract_gpu.py",
     "_SpectralL1": "no parameters and one differentiable input (the target is refused if it requires grad), scalar output",
 }
 

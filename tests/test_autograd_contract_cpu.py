@@ -1,4 +1,4 @@
-"""The case table of the autograd contract (tests/_contract.py) against ops.py, on the host: every `Function` subclass
+"""The case table of the autograd contract (tests/_contract.py) against ops.py and its family modules, on the host: every `Function` subclass
 defined in ops has a case or a stated exclusion, every builder / float64 restatement runs, and every exact-data case fits
 the significand budget at every size it is run at (so a budget failure can never be met on the GPU first).  The policy of
 ops._grad_buf / ops._side_ok for a tensor that gets two gradients in one backward pass is host code and is pinned here too."""
@@ -11,11 +11,18 @@ import _contract as C
 import sisr_amd
 
 ops = sisr_amd.ops
+# ops.py and the family modules whose operators it re-exports
+MODULES = (ops, sisr_amd.ops_chain, sisr_amd.ops_sparnet, sisr_amd.ops_sftmd, sisr_amd.ops_attention, sisr_amd.ops_losses,
+           sisr_amd.convs)
+
+
+def _nodes():
+    return {n: o for m in MODULES for n, o in vars(m).items()
+            if inspect.isclass(o) and issubclass(o, torch.autograd.Function) and o.__module__ == m.__name__}
 
 
 def _functions():
-    return sorted(n for n, o in vars(ops).items()
-                  if inspect.isclass(o) and issubclass(o, torch.autograd.Function) and o.__module__ == ops.__name__)
+    return sorted(_nodes())
 
 
 def test_every_function_of_ops_has_a_case_or_an_exclusion_reason():
@@ -35,9 +42,11 @@ def test_every_user_of_grad_buf_is_in_the_table():
     """the shared-weight test runs every case with a `sink`; that list must keep up with the callers of _grad_buf"""
     src = inspect.getsource(ops)
     users = set()
-    for name in _functions():
-        body = inspect.getsource(getattr(ops, name))
-        if "_grad_buf(" in body or "_grad_buf_or(" in body:
+    for name, node in _nodes().items():
+        body = inspect.getsource(node)
+        if name in C.EXCLUDED:  # (convs.py's two nodes take buffers too; test_convs_contract_gpu.py runs their shared-weight cases)
+            continue
+        if "_grad_buf(" in body or "_grad_buf_or(" in body or "_wb_grad_bufs(" in body:
             users.add(name)
     assert "_grad_buf" in src and users == set(C.GRAD_BUF_USERS), sorted(users ^ set(C.GRAD_BUF_USERS))
     with_sink = {f for c in C.CASES if c.sink for f in c.functions}
@@ -206,8 +215,8 @@ def test_side_stream_answer_for_first_and_second_contributions(clean_sink, monke
 
 
 def test_every_node_of_ops_asks_side_ok_before_it_takes_buffers():
-    for name in _functions():
-        body = inspect.getsource(getattr(ops, name))
+    for name, node in _nodes().items():
+        body = inspect.getsource(node)
         if "_side_ok(" in body:
             first_buf = min(i for i in (body.find("_grad_buf("), body.find("_grad_buf_or(")) if i >= 0)
             assert body.find("_side_ok(") < first_buf, f"{name} requests a gradient buffer before it asks _side_ok"

@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from sisr_amd import architectures as A
-from sisr_amd import basic, frequency, handlers, hip, ops, structural
+from sisr_amd import basic, frequency, handlers, hip, ops, ops_losses, structural
 
 import _freq_loss as S
 
@@ -152,8 +152,8 @@ def test_device_tables_are_the_helper_tables(n):
 def test_a_table_miss_during_capture_raises_and_a_hit_does_not():
     shape = (1, 1, 12, 20)
     a, b = torch.rand(shape, device=DEV), torch.rand(shape, device=DEV)
-    ops._spectral_tables.get(DEV.index, {}).pop((12, 20), None)
-    ops._spectral_held.get(DEV.index, {}).pop((12, 20), None)
+    ops_losses._spectral_tables.get(DEV.index, {}).pop((12, 20), None)
+    ops_losses._spectral_held.get(DEV.index, {}).pop((12, 20), None)
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
     with torch.no_grad(), torch.cuda.graph(graph):
@@ -169,7 +169,7 @@ def test_a_table_miss_during_capture_raises_and_a_hit_does_not():
     graph.replay()
     torch.cuda.synchronize()
     assert torch.equal(got, want)
-    assert (12, 20) in ops._spectral_held[DEV.index]  # a captured graph reads them: out of the LRU list for good
+    assert (12, 20) in ops_losses._spectral_held[DEV.index]  # a captured graph reads them: out of the LRU list for good
 
 
 def test_nine_shapes_in_a_row_evict_and_stay_correct():
@@ -182,7 +182,7 @@ def test_nine_shapes_in_a_row_evict_and_stay_correct():
             with torch.no_grad():
                 v = float(ops.spectral_l1(a.to(DEV), b.to(DEV)))
             assert abs(v - w_) <= 1e-6 * w_, (a.shape, v, w_)
-        cache = ops._spectral_tables[DEV.index]
+        cache = ops_losses._spectral_tables[DEV.index]
         assert len(cache) <= ops.SPECTRAL_TABLE_SLOTS
         assert tuple(shapes[0][2:]) not in cache and tuple(shapes[-1][2:]) in cache
 
@@ -247,8 +247,8 @@ def test_handler_trains_with_the_frequency_loss_eager_and_graphed(tmp_path, monk
         h.use_graph = mode
         assert isinstance(h.criterion, frequency.FrequencyMechanism) and type(h.criterion.base) is handlers.L1Loss
         if mode:  # the graphed step must find the tables through its own eager warm-up pass, not through earlier tests
-            ops._spectral_tables.get(0, {}).pop((64, 64), None)
-            ops._spectral_held.get(0, {}).pop((64, 64), None)
+            ops_losses._spectral_tables.get(0, {}).pop((64, 64), None)
+            ops_losses._spectral_held.get(0, {}).pop((64, 64), None)
         g = torch.Generator().manual_seed(5)
         ls, first = [], None
         for step in range(3):
@@ -265,7 +265,7 @@ def test_handler_trains_with_the_frequency_loss_eager_and_graphed(tmp_path, monk
         assert set(state["network"]) == set(h.net.state_dict())
         runs[mode] = (ls, float(sum(p.detach().double().sum() for p in h.net.parameters())))
         if mode:
-            assert (64, 64) in ops._spectral_held[0]
+            assert (64, 64) in ops_losses._spectral_held[0]
             x, y = torch.rand(2, 3, 16, 16, generator=g), torch.rand(2, 3, 64, 64, generator=g)
             out, eval_loss, _ = h.run_eval(x, y, request_loss=True, keep_on_device=True)
             ref = _float64_criterion(out, y, "l1", 0.0, 0.1)

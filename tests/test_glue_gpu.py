@@ -877,7 +877,7 @@ def test_nchw_to_nhwc_pad_refusals():
     assert bool((y[:8] == 0).all()) and R.untouched(y[8:])
 
 
-# (co, ci, cop, cip, taps): the SRMD head / tail weights, one real row or column, 1 x 1, nothing to pad, and ops._PadAxis'
+# (co, ci, cop, cip, taps): the SRMD head / tail weights, one real row or column, 1 x 1, nothing to pad, and ops_chain._PadAxis'
 # (outer, n, outer, P, inner) with an inner extent that is no tap count
 PAD_CASES = [(42, 84, 64, 128, 9), (3, 64, 64, 64, 9), (64, 13, 64, 64, 9), (5, 7, 5, 12, 1), (1, 1, 1, 1, 81), (3, 5, 3, 8, 37),
              (1, 19, 1, 64, 37), (64, 2, 64, 3, 1)]
