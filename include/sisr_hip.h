@@ -952,6 +952,23 @@ size_t sisr_eval_output_workspace_bytes(int n, int h, int w);
 int sisr_eval_output(const float* sr, int sr_planes, const float* chroma, const float* hr, int hr_form, int hr_planes, int n, int h,
                      int w, int shave, double* mse, unsigned char* rgb8, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the degradation as a differentiable float operator (csrc/consistency.hip): blur + bicubic down-sampling and its adjoint --
+ * Away from the image border, blur + Pillow's bicubic down-sampling by scale = 2, 3, 4 is one per-sample stride-`scale`
+ * cross-correlation with a composed kernel K (B, n, n) float64 (degrade.compose_degradation):
+ *   fwd   y[b][c][i][j]  = sum_ef K[b][e][f] x[b][c][scale i + off + e][scale j + off + f]     y (B, C, ho, wo), x (B, C, H, W)
+ *   bwd   dx[b][c][p][q] = sum_ij K[b][p - off - scale i][q - off - scale j] g[b][c][i][j]     dx (B, C, H, W), g (B, C, ho, wo)
+ * fp32 maps, float64 accumulation in a fixed order, rounded once.  bwd writes every element of dx exactly once (zeros where no
+ * footprint reaches).  No atomics, no workspace, no allocation, no host synchronisation: bit-identical repeats, capturable.
+ * sisr_degrade_valid_tile(backward): the edge of a workgroup's tile, in outputs (0) or in pixels of dx (1).
+ * -1: a null pointer; B, C, H, W, n, ho or wo < 1; off < 0; a footprint that leaves the image (scale (ho - 1) + off + n > H, or
+ *     the same along W);  -2: x, y, g or dx not 4-byte or K not 8-byte aligned;  -4: scale outside 2..4, n > 36, B * C > 65535,
+ *     more than 65535 tile rows. */
+int sisr_degrade_valid_tile(int backward);
+int sisr_degrade_valid_fwd(const float* x, const double* K, float* y, int B, int C, int H, int W, int n, int scale, int off, int ho,
+                           int wo, void* stream);
+int sisr_degrade_valid_bwd(const float* g, const double* K, float* dx, int B, int C, int H, int W, int n, int scale, int off, int ho,
+                           int wo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,8 +54,9 @@ def center_crop(image, height, width):
     return image.crop((left, top, left + width, top + height))
 
 
-def random_flip_rotate(lr, hr):
-    """Three draws from `random` in the reference's order (hflip, vflip, rot90)."""
+def random_flip_rotate(lr, hr, want_flags=False):
+    """Three draws from `random` in the reference's order (hflip, vflip, rot90).  want_flags: also the draws, as the
+    (hflip, vflip, transpose) row of a batch's 'flips'."""
     hflip = random.random() < 0.5
     vflip = random.random() < 0.5
     rot90 = random.random() < 0.5
@@ -68,6 +69,8 @@ def random_flip_rotate(lr, hr):
         if rot90:
             img = torch.transpose(img, 1, 2)
         return img
+    if want_flags:
+        return aug(lr), aug(hr), (int(hflip), int(vflip), int(rot90))
     return aug(lr), aug(hr)
 
 
@@ -145,15 +148,18 @@ class DeviceTileSampler:
         """-> (lr [B][C][crop][crop], hr [B][C][s*crop][s*crop]) fp32 tensors on the device."""
         return self.sample_pairs([(self.lr[i], self.hr[i]) for i in indices], rng)
 
-    def sample_pairs(self, pairs, rng=random):
+    def sample_pairs(self, pairs, rng=random, draws=None):
         """The same for explicit (LR, HR) device image pairs (contiguous planar fp32, HR = scale x LR): one gather per side.
         Each side has the channel count of the pairs' images on that side (a Y-only LR image has one plane next to an RGB
-        HR image), not that of the resident images."""
+        HR image), not that of the resident images.  draws: a list that receives each pair's (top, left, hflip, vflip,
+        transpose)."""
         hip, s = self.hip, self.scale
         B = len(pairs)
         rec_lr, rec_hr = [], []
         for lr_im, _ in pairs:
             top, left, hf, vf, rot = self.draw_for(lr_im, rng)
+            if draws is not None:
+                draws.append((top, left, hf, vf, rot))
             _, h, w = lr_im.shape
             rec_lr.append([h, w, top, left, int(hf), int(vf), int(rot), 0])
             rec_hr.append([h * s, w * s, top * s, left * s, int(hf), int(vf), int(rot), 0])
@@ -288,14 +294,15 @@ class DeviceTileLoader:
                     pairs.append((lr_dev.contiguous(), hr_c))
                     codes.append(code.numpy() if self.metadata[i] is None else np.concatenate((self.metadata[i], code.numpy())))
                     kernels.append(kernel.numpy().squeeze())
-                lr, hr = self.sampler.sample_pairs(pairs)  # lr: the degrader's final form (interpolated, YCbCr / Y)
+                crops = []
+                lr, hr = self.sampler.sample_pairs(pairs, draws=crops)  # lr: the degrader's final form (interpolated, YCbCr / Y)
                 if self.ycbcr:  # element-wise, so converting the gathered RGB tiles is converting the image first
                     from . import degrade
                     hr = degrade.rgb_to_ycbcr(hr, self.y_only)
                 yield {'lr': lr, 'hr': hr, 'tag': [self.tags[i] for i in idx], 'hr_tag': [self.hr_tags[i] for i in idx],
                        'mask': zeros.clone(), 'halfway_data': zeros.clone(), 'metadata': torch.from_numpy(np.stack(codes)),
                        'metadata_keys': _collate_keys(self.metadata_keys, B),
-                       'blur_kernels': torch.from_numpy(np.stack(kernels))}
+                       'blur_kernels': torch.from_numpy(np.stack(kernels)), 'flips': _flip_table(crops)}
                 continue
             lr, hr = self.sampler.sample(idx)
             if self.metadata[idx[0]] is not None:
@@ -359,7 +366,14 @@ class DeviceTileLoader:
         return {'lr': lr, 'hr': hr, 'tag': [self.tags[i] for i in idx], 'hr_tag': [self.hr_tags[i] for i in idx],
                 'mask': zeros.clone(), 'halfway_data': zeros.clone(), 'metadata': torch.from_numpy(np.stack(codes)),
                 'metadata_keys': _collate_keys(self.metadata_keys, B),
-                'blur_kernels': torch.from_numpy(np.stack([d.kernel.numpy().squeeze() for d in draws]))}
+                'blur_kernels': torch.from_numpy(np.stack([d.kernel.numpy().squeeze() for d in draws])),
+                'flips': _flip_table(crops)}
+
+
+def _flip_table(crops):
+    """'flips' of an online batch: (B, 3) int64 (hflip, vflip, transpose) from the samples' (top, left, hflip, vflip, transpose)
+    draws -- with 'blur_kernels', what the degradation-consistency term needs to redo each tile's degradation"""
+    return torch.tensor([[int(f) for f in cr[2:]] for cr in crops], dtype=torch.int64).reshape(len(crops), 3)
 
 
 def _collate_keys(keys, B):
@@ -530,8 +544,9 @@ class SuperResImages(Dataset):
         lr_dev, code, kernel, (top, left, rh, rw) = self.degrader(hr_im.cuda())
         lr_im = lr_dev.cpu()  # interpolated / colour-converted by the degrader, as the data set asked for
         hr_im = self._colorspace(hr_im[:, top:top + rh, left:left + rw])  # center_crop to LR size x scale (ref :470-476)
+        flips = (0, 0, 0)
         if self.random_augment is not None:
-            lr_im, hr_im = random_flip_rotate(lr_im, hr_im)
+            lr_im, hr_im, flips = random_flip_rotate(lr_im, hr_im, want_flags=True)
         if self.patch_crop is not None:
             lr_im, hr_im = random_matched_crop(lr_im, hr_im, crop_size=self.patch_crop, scale=self.scale)
         metadata = code.numpy()
@@ -539,7 +554,7 @@ class SuperResImages(Dataset):
             metadata = np.concatenate((self.metadata[index], metadata))
         return {'lr': lr_im, 'hr': hr_im, 'tag': base_name, 'hr_tag': base_name, 'mask': np.array(0),
                 'halfway_data': np.array(0), 'metadata': metadata, 'metadata_keys': self.metadata_keys,
-                'blur_kernels': kernel.numpy().squeeze()}
+                'blur_kernels': kernel.numpy().squeeze(), 'flips': np.array(flips, np.int64)}
 
 
 def sisr_data_setup(training_sets, eval_sets, batch_size=16, eval_batch_size=1, dataloader_threads=8,

@@ -189,6 +189,124 @@ def interp_window(size, scale, crop, origin):
     return min(int(bounds[origin, 0]), size - edge), edge
 
 
+# ----------------------------------------------------------------------------- the degradation as one linear operator (host, float64)
+# Away from the image border Pillow's bicubic down-sampling by an integer factor is shift-invariant: every output row from
+# index 2 to out - 3 has the same taps relative to s * i, and they are mirror-symmetric (first + last = s - 1).  Blur and both
+# tap passes are then ONE stride-s cross-correlation with a composed kernel; csrc/consistency.hip applies it
+# and its adjoint to float images -- the differentiable form of the 8-bit pipeline above (ops.degrade_valid).
+CONSISTENCY_SCALES = (2, 3, 4)
+
+
+def bicubic_interior_taps(scale):
+    """-> (first, weights): the non-zero taps of an interior output i of Pillow's bicubic down-sampling by `scale`, at input
+    indices scale * i + first ..., float64, normalised as precompute_coeffs does (w / ww) BEFORE the fixed-point rounding of
+    normalize_coeffs_8bpc.  Scale 4: 16 taps from -6; 3: 11 taps from -4; 2: 8 taps from -3."""
+    if isinstance(scale, bool) or scale not in CONSISTENCY_SCALES:
+        raise ValueError(f"bicubic_interior_taps: scale must be one of {CONSISTENCY_SCALES}; got {scale!r}")
+    s, xx = int(scale), 8  # any interior row: precompute_coeffs' own arithmetic at row 8 of a 64-row output
+    support = 2.0 * s
+    center = (xx + 0.5) * s
+    xmin = int(center - support + 0.5)
+    xmax = int(center + support + 0.5) - xmin
+    w = [_bicubic_filter((x + xmin - center + 0.5) * (1.0 / s)) for x in range(xmax)]
+    ww = 0.0
+    for v in w:
+        ww += v
+    w = np.array([v / ww for v in w], np.float64)
+    keep = np.flatnonzero(w)
+    return xmin + int(keep[0]) - s * xx, w[keep[0]:keep[-1] + 1].copy()
+
+
+def flip_kernels(kernels, flips):
+    """(B, l, l) kernels under each sample's (hflip, vflip, transpose) flags, applied as random_flip_rotate applies them to an
+    image: T D_k(x) = D_{T k}(T x) (the taps are mirror-symmetric and centred on the s-pixel cell)."""
+    out = np.array(kernels, np.float64, copy=True)
+    if flips is None:
+        return out
+    flips = np.asarray(flips)
+    if flips.shape != (out.shape[0], 3):
+        raise ValueError(f"flips must be a (B, 3) table of (hflip, vflip, transpose) flags; got shape {flips.shape}")
+    for b, (hf, vf, tr) in enumerate(flips):
+        k = out[b]
+        if hf:
+            k = k[:, ::-1]
+        if vf:
+            k = k[::-1, :]
+        if tr:
+            k = k.T
+        out[b] = k
+    return out
+
+
+def compose_degradation(kernels, scale, flips=None):
+    """-> (K, first): K (B, n, n) float64, n = taps + l - 1, with D_k(x)[i, j] = sum_ef K[e, f] x[s i + first + e, s j + first + f]
+    for every output whose footprint lies inside x: K = (w w^T) * k, BatchBlur's cross-correlation (blurred[p, q] = sum_uv
+    k[u, v] x[p - l // 2 + u, q - l // 2 + v]) followed by the two tap passes.  kernels: (B, l, l), l odd and at most 21
+    ([[1]]: bicubic alone); flips: (B, 3) flags of the augmentation the tiles went through, or None."""
+    k = np.asarray(kernels, np.float64)
+    if k.ndim != 3 or k.shape[1] != k.shape[2] or k.shape[1] % 2 != 1 or k.shape[1] > 21 or k.shape[0] < 1:
+        raise ValueError(f"compose_degradation takes (B, l, l) blur kernels with l odd and at most 21; got shape {k.shape}")
+    first, w = bicubic_interior_taps(scale)
+    k = flip_kernels(k, flips)
+    l, taps = k.shape[1], len(w)
+    n = taps + l - 1
+    full = np.zeros((n, l), np.float64)  # full[e, u] = w[e - u]: the full convolution with w as a matrix
+    for u in range(l):
+        full[u:u + taps, u] = w
+    return np.matmul(np.matmul(full, k), full.T), first - l // 2
+
+
+def consistency_margin(scale, l):
+    """LR rows / columns cut at each side of a tile: output i of an h-row tile is kept when its whole footprint (taps plus blur
+    radius) lies inside the s h HR rows of the tile, i.e. m <= i < h - m.  4, 5, 7 for s = 4, 3, 2 at l = 21; 2 at s = 4, l = 1."""
+    first, _ = bicubic_interior_taps(scale)
+    l = int(l)
+    if l < 1 or l % 2 != 1 or l > 21:
+        raise ValueError(f"consistency_margin: the blur kernel edge must be odd and at most 21; got {l}")
+    return -((first - l // 2) // int(scale))  # ceil((l // 2 - first) / s), the same at both sides by the taps' symmetry
+
+
+def consistency_geometry(scale, n):
+    """From the edge n of a composed kernel: (l, m, off) -- the blur edge, the margin and the HR index s m + first - l // 2 >= 0
+    of the first input of kept output 0."""
+    first, w = bicubic_interior_taps(scale)
+    l = int(n) - len(w) + 1
+    if l < 1 or l % 2 != 1 or l > 21:
+        raise ValueError(f"a composed kernel of edge {n} belongs to no odd blur edge 1..21 at scale {scale}")
+    m = consistency_margin(scale, l)
+    return l, m, int(scale) * m + first - l // 2
+
+
+class DegradeValid(torch.autograd.Function):
+    """The node behind ops.degrade_valid (which checks the operands and derives the geometry): y = D_K(x) by
+    sisr_degrade_valid_fwd, dx = D_K^T(g) by sisr_degrade_valid_bwd.  One differentiable input, no parameter and no gradient
+    buffer of its own; K (B, n, n) float64 on x's device takes no gradient; an x that needs none costs no backward launch."""
+
+    @staticmethod
+    def forward(ctx, x, K, scale, off, ho, wo):
+        x = x.contiguous()
+        B, C, H, W = x.shape
+        n = K.shape[1]
+        y = torch.empty((B, C, ho, wo), device=x.device, dtype=torch.float32)
+        hip.check(hip.lib().sisr_degrade_valid_fwd(hip.ptr(x), K.data_ptr(), hip.ptr(y), B, C, H, W, n, scale, off, ho, wo,
+                                                   hip.stream()), "sisr_degrade_valid_fwd")
+        ctx.save_for_backward(K)
+        ctx.geometry = (B, C, H, W, n, scale, off, ho, wo)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        (K,) = ctx.saved_tensors
+        B, C, H, W, n, scale, off, ho, wo = ctx.geometry
+        g = g.contiguous()
+        dx = torch.empty((B, C, H, W), device=g.device, dtype=torch.float32)  # the kernel writes every element
+        hip.check(hip.lib().sisr_degrade_valid_bwd(hip.ptr(g), K.data_ptr(), hip.ptr(dx), B, C, H, W, n, scale, off, ho, wo,
+                                                   hip.stream()), "sisr_degrade_valid_bwd")
+        return dx, None, None, None, None, None
+
+
 # ----------------------------------------------------------------------------- device pipeline
 def blur_quant(hr, kernel, want_float=False, want_u8=True):
     """(C, H, W) fp32 on the device, (l, l) kernel -> uint8 (C, H, W) = byte(255 * BatchBlur(hr)); want_float: also

@@ -86,6 +86,12 @@ class BaseModel(nn.Module):
         if self.freq_loss is not None and not (self.freq_loss >= 0 and math.isfinite(self.freq_loss)):
             raise ValueError("freq_loss: the weight of the frequency-domain term must be a finite number >= 0; got %r"
                              % (self.freq_loss,))
+        # weight of the degradation-consistency term gamma * mean |D_k(sr) - lr| added last (None / 0: no such term): the output,
+        # degraded again by the blur kernel the batch carries, against the LR input (consistency.py; no counterpart in the
+        # reference); a model parameter as well
+        from .consistency import check_weight
+        self.consistency_loss = check_weight(kwargs.get('consistency_loss'))
+        self._consistency = None  # the ConsistencyMechanism training_setup wrapped the criterion in
         # the optional parts of the update step, all carried out by optim.FlatAdam in its one pass over the arenas (no
         # counterpart in the reference; model parameters, so a config's internal_params can hold them):
         #   weight_decay  decoupled (AdamW) weight decay;   ema_decay  an exponential moving average of the weights,
@@ -209,6 +215,59 @@ class BaseModel(nn.Module):
             # outermost: pixel or perceptual base -> StructuralMechanism -> MultiScaleStructuralMechanism -> FrequencyMechanism
             from . import frequency
             self.criterion = frequency.FrequencyMechanism(self.criterion, self.freq_loss)
+        if self.consistency_loss:
+            self._check_consistency_support()
+            if self.eval_mode is False:
+                # outermost: ... -> FrequencyMechanism -> ConsistencyMechanism; the SR factor is read off the tiles
+                from . import consistency
+                self.criterion = self._consistency = consistency.ConsistencyMechanism(self.criterion, self.consistency_loss)
+
+    def _check_consistency_support(self):
+        """consistency_loss compares D_k(output) with the network's input: that input must be the LR image in RGB"""
+        name = type(self).__name__
+        if getattr(self, 'predicts_metadata', False):
+            raise NotImplementedError("consistency_loss: %s estimates a degradation code, not an image: there is no output to "
+                                      "degrade again" % name)
+        if self.im_input != 'unmodified':
+            raise NotImplementedError("consistency_loss: the input of %s is the interpolated image (im_input = %r), not the LR "
+                                      "image the degraded output is compared with" % (name, self.im_input))
+        if 'rgb' not in (self.colorspace or ''):
+            raise NotImplementedError("consistency_loss: %s works in the %r colorspace; the term degrades an RGB output with the "
+                                      "kernel that made the RGB LR image" % (name, self.colorspace))
+
+    def _consistency_operands(self, x, y, kwargs):
+        """None without the term; with it (lr, K): the LR tiles -- the first y.shape[1] planes of x (SRMD's x carries its metadata
+        planes behind them) -- and the batch's composed kernels (B, n, n), float64 on the device, from kwargs['blur_kernels']
+        (B, l, l) under kwargs['flips'] (B, 3) (absent: tiles that were not augmented)."""
+        if self._consistency is None:
+            return None
+        from . import degrade
+        kernels = kwargs.get('blur_kernels')
+        k = None if kernels is None else torch.as_tensor(kernels).detach().cpu()
+        if k is None or k.dim() != 3 or k.shape[0] != x.shape[0]:
+            raise RuntimeError("consistency_loss: the batch carries no blur kernels ('blur_kernels' is %s): the term needs the "
+                               "kernel that made each LR tile, which the online degradation loaders supply; sets degraded "
+                               "offline are not supported" % ('missing' if k is None else 'of shape %s' % (tuple(k.shape),)))
+        if y.shape[2] % x.shape[2] or y.shape[3] != x.shape[3] * (y.shape[2] // x.shape[2]):
+            raise RuntimeError("consistency_loss: HR tiles %s are no integer multiple of the LR tiles %s"
+                               % (tuple(y.shape), tuple(x.shape)))
+        flips = kwargs.get('flips')
+        flips = None if flips is None else torch.as_tensor(flips).detach().cpu().numpy()
+        K, _ = degrade.compose_degradation(k.numpy(), y.shape[2] // x.shape[2], flips)
+        K = torch.from_numpy(K)
+        if x.is_cuda:  # from pinned memory, without a host synchronisation: consecutive steps keep queueing back to back
+            K = K.pin_memory().to(self.device, non_blocking=True)
+        return x[:, :y.shape[1]], K
+
+    def _criterion(self, out, y, cons):
+        """self.criterion(out, y) with the consistency operands bound for exactly this call"""
+        if cons is None:
+            return self.criterion(out, y)
+        self._consistency.bind(*cons)
+        try:
+            return self.criterion(out, y)
+        finally:
+            self._consistency.clear()
 
     def _perceptual_criterion(self, lambda_per):
         """ref: models/__init__.py:341-342 PerceptualMechanism(lambda_per=perceptual, device=device), with the extractor's weights
@@ -332,10 +391,11 @@ class BaseModel(nn.Module):
             return nan, x.new_zeros((0,) + tuple(y.shape[1:]))
         if self.use_graph and x.is_cuda and loss_scale == 1.0:
             return self._graphed_step(x, y, kwargs)
+        cons = self._consistency_operands(x, y, kwargs)
         try:
             ops.pack_all(self.net, A.conv_weights)  # every conv weight repacked by one launch
             out = self.run_model(x, image_names=tag, **kwargs)
-            loss = self.criterion(out, y)
+            loss = self._criterion(out, y, cons)
             scale = loss_scale * self._dp_scale()
             self.standard_update(loss if scale == 1.0 else loss * scale)
         finally:
@@ -360,7 +420,9 @@ class BaseModel(nn.Module):
         exchange overlaps the rest of the replayed backward as it does in eager mode.  SISR_GRAPH_OVERLAP=0 (or a CPU
         reducer): all buckets are all-reduced at the join."""
         extra = kwargs.get('extra_channels')
-        key = (tuple(x.shape), tuple(y.shape), None if extra is None else tuple(extra.shape))
+        cons = self._consistency_operands(x, y, kwargs)  # (LR view of x, this batch's composed kernels) or None
+        key = (tuple(x.shape), tuple(y.shape), None if extra is None else tuple(extra.shape),
+               None if cons is None else tuple(cons[1].shape))
         entry = self._graphs.get(key)
         red = self.reducer
         signal = red is not None and red.can_signal()
@@ -370,6 +432,10 @@ class BaseModel(nn.Module):
             if entry is None:
                 sx, sy = x.clone(), y.clone()
                 se = None if extra is None else extra.to(self.device).clone()
+                # the composed kernels live in a static buffer like sx / sy / se, refilled before every replay; the LR tiles the
+                # term reads are a view of sx
+                sk = None if cons is None else cons[1].clone()
+                scons = None if cons is None else (sx[:, :y.shape[1]], sk)
                 kw = dict(kwargs)
                 if se is not None:
                     kw['extra_channels'] = se
@@ -382,7 +448,7 @@ class BaseModel(nn.Module):
                     self.optimizer.zero_grad(set_to_none=True)
                     ops.pack_all(self.net, A.conv_weights)
                     with ops.deferred_wgrads():
-                        (self.criterion(self.run_model(sx, **kw), sy) * self._dp_scale()).backward()
+                        (self._criterion(self.run_model(sx, **kw), sy, scons) * self._dp_scale()).backward()
                 torch.cuda.current_stream().wait_stream(side)
                 self.optimizer.zero_grad(set_to_none=True)
                 with torch.no_grad():
@@ -396,7 +462,7 @@ class BaseModel(nn.Module):
                 with torch.cuda.graph(graph):
                     ops.pack_all(self.net, A.conv_weights)  # first node of the graph: the replay repacks
                     out = self.run_model(sx, **kw)
-                    loss = self.criterion(out, sy)
+                    loss = self._criterion(out, sy, scons)
                     if signal:
                         red.begin_capture()
                     try:
@@ -410,13 +476,15 @@ class BaseModel(nn.Module):
                 if dump:
                     graph.debug_dump(dump)
                 grads = [(p, p.grad) for p in self.net.parameters()]
-                entry = (graph, sx, sy, se, loss, out, grads, order)
+                entry = (graph, sx, sy, se, loss, out, grads, order, sk)
                 self._graphs[key] = entry
-            graph, sx, sy, se, loss, out, grads, order = entry
+            graph, sx, sy, se, loss, out, grads, order, sk = entry
             sx.copy_(x)
             sy.copy_(y)
             if se is not None:
                 se.copy_(extra)
+            if sk is not None:
+                sk.copy_(cons[1])
             graph.replay()
             for p, g in grads:  # this replay's gradients live in this entry's capture-time tensors
                 p.grad = g

@@ -291,6 +291,12 @@ _SIGS.update({  # output stage of evaluation: Y-MSE against the HR batch and 8-b
     "sisr_eval_output": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
 })
 
+_SIGS.update({  # the degradation as a float operator and its adjoint: one strided correlation per sample (csrc/consistency.hip)
+    "sisr_degrade_valid_tile": (c_int, [c_int]),
+    "sisr_degrade_valid_fwd": (c_int, [P, P, P] + [c_int] * 9 + [P]),
+    "sisr_degrade_valid_bwd": (c_int, [P, P, P] + [c_int] * 9 + [P]),
+})
+
 GM_MAXL = 4
 
 

@@ -33,7 +33,7 @@ Operators (ops.py unless a module is named)
                  lam / csam / conv3x3_stack / stack_maps        HAN (ref: advanced/HAN_blocks.py, advanced/architectures.py:314-377)
                  soca / nonlocal_block / nonlocal_attention     SAN (ref: advanced/SAN_blocks.py, advanced/mpncov.py)
                  pixel_shuffle  nn.PixelShuffle on channels-last maps wider than 64 channels (64-wide: fused into the conv's store)
-  ops_losses.py:  l1_loss (ref: SISR/models/__init__.py:268) / mse_loss (ref: basic/handlers.py:14) / ssim_mean / ms_ssim_mean / spectral_l1
+  ops_losses.py:  l1_loss (ref: SISR/models/__init__.py:268) / mse_loss (ref: basic/handlers.py:14) / ssim_mean / ms_ssim_mean / spectral_l1 / degrade_valid
   convs.py:      conv_y2f / conv_f2y / conv_kxk / conv_1x1      SRCNN, VDSR, IKC: K x K convs, the Y-channel ends, pointwise
                  layers (ref: basic/architectures.py:6-77)
   pool.py:       map_mean
@@ -179,7 +179,10 @@ def _grad_buf(w, gid=None):
             _flush_deferred()
             return torch.empty_like(w)
         _PASS_BUFS.add(key)
-    sink = GRAD_SINK.get(key)
+    # a sink belongs to a leaf parameter.  A non-leaf weight -- the zero-padded copy a ChannelPadded network makes of a
+    # parameter every forward -- is a temporary: its address may be the one a parameter of a handler long gone had when it
+    # registered its sink, and its gradient must reach autograd (the crop), not that handler's arena
+    sink = GRAD_SINK.get(key) if w.is_leaf else None
     if sink is not None and sink.shape == w.shape and w.grad is None:
         return sink.detach()  # a fresh alias: autograd adopts a gradient it holds the only reference to
     return torch.empty_like(w)
@@ -596,8 +599,10 @@ def wgrad_c64(x, xview, dy, dyview, dw, db, B, H, W, cin, cout, alpha=1.0, dy_sc
               active_units=0, owner=None, storage=0):
     """active_units (fp32 kernel): bit mask of the 32 x 32-channel blocks of the gradient to compute (0 = all).
     owner: the weight Parameter -- with it, inside a deferred_wgrads() block, an eligible launch is queued instead."""
+    # (a non-leaf owner -- a ChannelPadded network's padded weight -- is never queued: autograd crops its gradient as soon as
+    # this node returns, long before the block's flush would have written it)
     if (_DEFERRED is not None and hip.stream() == _DEFERRED_STREAM and owner is not None and owner.requires_grad and
-            owner.grad is None and owner.data_ptr() not in _PASS_SHARED and cin == 64 and cout == 64 and shuffle == 1 and
+            owner.is_leaf and owner.grad is None and owner.data_ptr() not in _PASS_SHARED and cin == 64 and cout == 64 and shuffle == 1 and
             alpha == 1.0 and not active_units and WgradQueue.wanted(B, H, W) and xview is hip.view_plain(H, W, 64) and
             dyview is hip.view_plain(H, W, 64)):
         if id(owner) in _DEFERRED_OWNERS:
@@ -1680,8 +1685,8 @@ from .ops_attention import (SOCA_ITERS, SOCA_LIMIT, add_residual, ca_layer, conv
                             global_avg_pool, lam, nonlocal_attention, nonlocal_block, pa_layer, pixel_shuffle, scale_add, soca,
                             soca_window, stack_maps)
 from .ops_chain import FrozenChain, conv_chain, frozen_features, nchw_to_nhwc_pad, pad_param  # noqa: E402,F401
-from .ops_losses import (SPECTRAL_MAX_SIDE, SPECTRAL_MIN_SIDE, SPECTRAL_TABLE_SLOTS, SSIM_WINDOW, l1_loss,  # noqa: E402,F401
-                         ms_ssim_mean, mse_loss, spectral_l1, spectral_tables, ssim_mean)
+from .ops_losses import (SPECTRAL_MAX_SIDE, SPECTRAL_MIN_SIDE, SPECTRAL_TABLE_SLOTS, SSIM_WINDOW, degrade_valid,  # noqa: E402,F401
+                         degrade_valid_tile, l1_loss, ms_ssim_mean, mse_loss, spectral_l1, spectral_tables, ssim_mean)
 from .ops_sftmd import sft_apply, sft_layer, sftmd_forward  # noqa: E402,F401
 from .ops_sparnet import (batch_norm_act, group_norm, instance_norm_act, leaky_relu, nearest_up, pixel_norm,  # noqa: E402,F401
                           prelu, refl_conv, selu, shuffle_rgb, spar_combine, spar_combine3d)

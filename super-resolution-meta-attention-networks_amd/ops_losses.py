@@ -1,5 +1,7 @@
 """Loss terms on the HIP path: L1, MSE, mean SSIM (csrc/ssim_loss.hip), multi-scale SSIM (csrc/ms_ssim.hip) and the
 spectral L1 (csrc/freq_loss.hip).  Each node computes its value and, in the same call, the gradient it will return.
+degrade_valid (csrc/consistency.hip) is the one operator here that returns a map: the degradation of a float image; its node,
+with the adjoint kernel as its backward, is degrade.DegradeValid, beside the host mathematics it depends on.
 The nodes have one differentiable input and no gradient buffers of their own, so they use nothing of ops.py's core; ops
 re-exports the operators."""
 import collections
@@ -8,7 +10,7 @@ import ctypes
 import torch
 from torch.autograd import Function
 
-from . import hip
+from . import degrade, hip
 # the default weights (Wang et al. 2003, as given: they sum to 1.0001) and the checks of the weights and of the image size,
 # shared with the host form
 from .metrics import MS_SSIM_WEIGHTS, ms_ssim_check_size, ms_ssim_weights
@@ -211,6 +213,39 @@ def spectral_l1(sr, y):
         raise RuntimeError("spectral_l1: the target takes no gradient; detach it")
     # needs_input_grad is set under no_grad as well (run_eval(request_loss=True)): the gradient launches and the sign map are skipped there
     return _SpectralL1.apply(sr, y, torch.is_grad_enabled())
+
+
+# ----------------------------------------------------------------------------- blur + bicubic down-sampling of a float image
+def degrade_valid_tile(backward=False):
+    """Edge of a workgroup's tile of sisr_degrade_valid_fwd (LR outputs) or, backward, of sisr_degrade_valid_bwd (HR pixels)."""
+    return hip.lib().sisr_degrade_valid_tile(int(bool(backward)))
+
+
+def degrade_valid(x, K, scale):
+    """The LR image the degradation pipeline would make of the float HR tiles x (B, C, s h, s w) -- blur with each sample's
+    kernel, then Pillow's bicubic down-sampling by s = `scale` -- without its 8-bit roundings, at the outputs whose whole
+    footprint lies inside the tile: (B, C, h - 2m, w - 2m), m = degrade.consistency_margin(scale, l), the map to compare with
+    lr[:, :, m:h - m, m:w - m].  K: the composed kernels (B, n, n) of degrade.compose_degradation, float64 on x's device
+    (a tensor elsewhere or of another float type is converted); it takes no gradient.  One launch forward, one (the adjoint, a
+    gather) backward; float64 accumulation, so both are the fp32 numbers nearest the exact sums."""
+    if x.dim() != 4 or K.dim() != 3 or K.shape[1] != K.shape[2] or K.shape[0] != x.shape[0]:
+        raise RuntimeError(f"degrade_valid takes x (B, C, H, W) and K (B, n, n); got {tuple(x.shape)} and {tuple(K.shape)}")
+    if x.numel() == 0:
+        raise ValueError(f"degrade_valid: empty batch {tuple(x.shape)}")
+    scale = int(scale)
+    l, m, off = degrade.consistency_geometry(scale, K.shape[1])
+    H, W = x.shape[2:]
+    if H % scale or W % scale:
+        raise ValueError(f"degrade_valid: the image extent {(H, W)} is not a multiple of the scale {scale}")
+    h, w = H // scale, W // scale
+    if h <= 2 * m or w <= 2 * m:
+        raise ValueError(f"degrade_valid: no output of a {h} x {w} LR tile keeps its footprint inside the {H} x {W} HR tile at "
+                         f"scale {scale} with a {l} x {l} blur kernel: both LR sides must exceed 2 m = {2 * m}")
+    hip.ptr(x)  # raises on CPU or non-fp32 tensors: there is no CPU path
+    if K.requires_grad:
+        raise RuntimeError("degrade_valid: the composed kernel takes no gradient; detach it")
+    K = K.to(device=x.device, dtype=torch.float64).contiguous()
+    return degrade.DegradeValid.apply(x, K, scale, off, h - 2 * m, w - 2 * m)
 
 
 # ----------------------------------------------------------------------------- MSE loss
