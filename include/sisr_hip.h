@@ -969,6 +969,42 @@ int sisr_degrade_valid_fwd(const float* x, const double* K, float* y, int B, int
 int sisr_degrade_valid_bwd(const float* g, const double* K, float* dx, int B, int C, int H, int W, int n, int scale, int off, int ho,
                            int wo, void* stream);
 
+/* ---- dense-block growth convs (csrc/dense.hip): 3 x 3, cin -> 32, in place in a channel stack ---------------------------------
+ * ref: ESRGAN's Residual Dense Block, x_j = lrelu(conv_j(cat(x, x_1 .. x_{j-1}))).  A block works on ONE channels-last stack
+ * S[B][H][W][192] fp32: channels 0..63 the block input, slot j = channels 64 + 32 (j - 1) .. 64 + 32 j - 1 the output of layer j.
+ * Layer j reads channels [0, cin_j), cin_j = 64 + 32 (j - 1), and writes slot j of the same pixel records: no concatenation.
+ * Every map is {pointer to its first channel, pitch = floats per pixel}; zero padding 1; fp32 on v_mfma_f32_32x32x2_f32.
+ * cout is always 32; cin in {64, 96, 128, 160}.  Pointers 16-byte aligned, pitches multiples of 32 (<= 4096) that hold the
+ * range; slope is any finite float (0.2: ESRGAN; 0: ReLU).  Channels outside the ranges named are neither read nor written.
+ *   pack   w (32, cin, 3, 3) OIHW -> packed_fwd and packed_dgrad (32 * cin * 9 floats each; either may be NULL), one launch.
+ *   fwd    y[..., 0:32] = act ? (v > 0 ? v : slope * v) : v,  v = conv(x[..., 0:cin]) + bias (nullable).  x and y may lie in the
+ *          same pixel records (y = x + cin, equal pitches); ranges that overlap are refused.
+ *   dgrad  dx[..., 0:cin] (+)= conv^T(dy'),  dy' = dymask > 0 ? dy : slope * dy (dymask: the layer's saved output, own pitch;
+ *          NULL: dy' = dy; zero takes the slope branch as in PyTorch).  accumulate = 1: dx += ..., every element read and
+ *          written once by the lane that owns it (the running gradient of a stack, summed in place, deterministic).  dy and
+ *          dymask may share pixel records with dx outside [0, cin).
+ *   wgrad  dw (32, cin, 3, 3) = sum_pixels dy' (x) x,  db (32, nullable) = sum_pixels dy'.  Ordered two-stage sum, no atomics:
+ *          a repeat call is bit-identical.  workspace: sisr_dense3x3_wgrad_workspace_bytes (0 for a shape that is refused).
+ * No allocation, no host synchronisation: capturable.  Every check is made before the first device call:
+ * -1: a null pointer; B, H or W < 1, B > 65535, H or W > 65536, B * H * W > 2^28; cin <= 0 or no multiple of 32; a pitch that is
+ *     no multiple of 32, above 4096 or below its range; a NaN or infinite slope; overlapping read and write ranges; a workspace
+ *     that is too small;  -2: a misaligned pointer;  -4: a multiple of 32 other than 64, 96, 128, 160 as cin. */
+int sisr_pack_dense3x3(const float* w, float* packed_fwd, float* packed_dgrad, int cin, void* stream);
+int sisr_dense3x3_fwd(const float* x, int x_pitch, int cin, const float* packed, const float* bias, int act, float slope,
+                      float* y, int y_pitch, int B, int H, int W, void* stream);
+int sisr_dense3x3_dgrad(const float* dy, int dy_pitch, const float* dymask, int mask_pitch, float slope,
+                        const float* packed_dgrad, float* dx, int dx_pitch, int cin, int accumulate, int B, int H, int W,
+                        void* stream);
+size_t sisr_dense3x3_wgrad_workspace_bytes(int B, int H, int W, int cin);
+int sisr_dense3x3_wgrad(const float* x, int x_pitch, int cin, const float* dy, int dy_pitch, const float* dymask, int mask_pitch,
+                        float slope, float* dw, float* db, float* workspace, size_t workspace_bytes, int B, int H, int W,
+                        void* stream);
+/* The RRDB's skip between two stacks: y[..., 0:64] = t[..., 0:64] * g[b][c] + x[..., 0:64] (x nullable), every map with its own
+ * pitch (a multiple of 32 from 64 up), g (B, 64), hw pixels per image; the product is rounded before the sum.  y may be t or x
+ * itself.  -1: a null t, g or y; B or hw < 1, B * hw > 2^28; a bad pitch; y overlapping t or x otherwise;  -2: misaligned. */
+int sisr_dense_skip(const float* t, int t_pitch, const float* g, const float* x, int x_pitch, float* y, int y_pitch, int B,
+                    long hw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@ set -euo pipefail
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 SRCS=(conv3x3_mfma.hip wgrad3x3_mfma.hip conv3x3_small.hip attention.hip misc.hip han.hip san.hip degrade.hip sft.hip nonlocal.hip sparnet.hip
-      metrics.hip basic.hip interp.hip ensemble.hip perceptual.hip ssim_loss.hip jpeg.hip update.hip freq_loss.hip degrade_tiles.hip ms_ssim.hip interp_tiles.hip eval_output.hip consistency.hip)
+      metrics.hip basic.hip interp.hip ensemble.hip perceptual.hip ssim_loss.hip jpeg.hip update.hip freq_loss.hip degrade_tiles.hip ms_ssim.hip interp_tiles.hip eval_output.hip consistency.hip dense.hip)
 HDRS=(sisr_common.h conv_tiles.h ssim_window.h ca_gate.h conv_rgb_out.h degrade_common.h jpeg_block.h noise_field.h pil_upsample.h)
 
 build() {  # $1 = output, $2 = object dir, $3... = extra flags / sources

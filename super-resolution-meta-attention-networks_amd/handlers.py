@@ -788,6 +788,11 @@ try:  # IKC's corrector (corrector.py)
     HANDLERS += [CorrectorHandler]
 except ImportError:
     pass
+try:  # RRDBNet / QRRDBNet: ESRGAN's generator and its meta-attention form (rrdb.py)
+    from .rrdb import RRDBHandler, QRRDBHandler
+    HANDLERS += [RRDBHandler, QRRDBHandler]
+except ImportError:
+    pass
 # registry key = class name minus 'Handler', lower-cased (ref: models/__init__.py:26-30)
 available_models = {h.__name__.split('Handler')[0].lower(): h for h in HANDLERS}
 

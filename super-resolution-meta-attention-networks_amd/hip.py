@@ -297,6 +297,15 @@ _SIGS.update({  # the degradation as a float operator and its adjoint: one strid
     "sisr_degrade_valid_bwd": (c_int, [P, P, P] + [c_int] * 9 + [P]),
 })
 
+_SIGS.update({  # dense-block growth convs, cin -> 32 in place in a 192-channel stack: RRDBNet (csrc/dense.hip)
+    "sisr_pack_dense3x3": (c_int, [P, P, P, c_int, P]),
+    "sisr_dense3x3_fwd": (c_int, [P, c_int, c_int, P, P, c_int, c_float, P, c_int, c_int, c_int, c_int, P]),
+    "sisr_dense3x3_dgrad": (c_int, [P, c_int, P, c_int, c_float, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "sisr_dense3x3_wgrad_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "sisr_dense3x3_wgrad": (c_int, [P, c_int, c_int, P, c_int, P, c_int, c_float, P, P, P, c_size_t, c_int, c_int, c_int, P]),
+    "sisr_dense_skip": (c_int, [P, c_int, P, P, c_int, P, c_int, c_int, c_long, P]),
+})
+
 GM_MAXL = 4
 
 

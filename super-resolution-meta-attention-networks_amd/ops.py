@@ -37,6 +37,7 @@ Operators (ops.py unless a module is named)
   convs.py:      conv_y2f / conv_f2y / conv_kxk / conv_1x1      SRCNN, VDSR, IKC: K x K convs, the Y-channel ends, pointwise
                  layers (ref: basic/architectures.py:6-77)
   pool.py:       map_mean
+  ops_dense.py:  dense_block / dense_skip / dense_conv          RRDBNet: Residual Dense Blocks in place in a 192-channel stack
 """
 import functools
 import os
@@ -1685,6 +1686,7 @@ from .ops_attention import (SOCA_ITERS, SOCA_LIMIT, add_residual, ca_layer, conv
                             global_avg_pool, lam, nonlocal_attention, nonlocal_block, pa_layer, pixel_shuffle, scale_add, soca,
                             soca_window, stack_maps)
 from .ops_chain import FrozenChain, conv_chain, frozen_features, nchw_to_nhwc_pad, pad_param  # noqa: E402,F401
+from .ops_dense import dense_block, dense_conv, dense_pack, dense_skip  # noqa: E402,F401
 from .ops_losses import (SPECTRAL_MAX_SIDE, SPECTRAL_MIN_SIDE, SPECTRAL_TABLE_SLOTS, SSIM_WINDOW, degrade_valid,  # noqa: E402,F401
                          degrade_valid_tile, l1_loss, ms_ssim_mean, mse_loss, spectral_l1, spectral_tables, ssim_mean)
 from .ops_sftmd import sft_apply, sft_layer, sftmd_forward  # noqa: E402,F401
