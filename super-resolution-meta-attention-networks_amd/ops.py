@@ -170,23 +170,44 @@ def _grad_buf(w, gid=None):
       * a further gradient of the same `w` in one pass (a weight applied twice): a private buffer as well -- the sink holds
         the first contribution until autograd has added the two -- handed out only after the side stream has been joined
         and every deferred queue flushed, either of which may still hold the launch of the first one; the launch that fills
-        this buffer is never queued itself (wgrad_c64, _ReflConv).
+        this buffer is never queued itself (wgrad_c64, _ReflConv).  The sum of the two ends in the sink (_sum_into_sink).
     gid: _pass_id(), from a node that asked already."""
     key = w.data_ptr()
-    if (gid if gid is not None else _pass_id()) >= 0:
+    gid = gid if gid is not None else _pass_id()
+    # a sink belongs to a leaf parameter.  A non-leaf weight -- the zero-padded copy a ChannelPadded network makes of a
+    # parameter every forward -- is a temporary: its address may be the one a parameter of a handler long gone had when it
+    # registered its sink, and its gradient must reach autograd (the crop), not that handler's arena
+    sink = GRAD_SINK.get(key) if w.is_leaf else None
+    if sink is not None and (sink.shape != w.shape or w.grad is not None):
+        sink = None
+    if gid >= 0:
         if key in _PASS_BUFS:
+            if sink is not None and key not in _PASS_SHARED:  # (.grad is still None: the first contribution went to the sink)
+                _sum_into_sink(w, sink, gid)
             _PASS_SHARED.add(key)
             _join_side_now(w.device)
             _flush_deferred()
             return torch.empty_like(w)
         _PASS_BUFS.add(key)
-    # a sink belongs to a leaf parameter.  A non-leaf weight -- the zero-padded copy a ChannelPadded network makes of a
-    # parameter every forward -- is a temporary: its address may be the one a parameter of a handler long gone had when it
-    # registered its sink, and its gradient must reach autograd (the crop), not that handler's arena
-    sink = GRAD_SINK.get(key) if w.is_leaf else None
-    if sink is not None and sink.shape == w.shape and w.grad is None:
+    if sink is not None:
         return sink.detach()  # a fresh alias: autograd adopts a gradient it holds the only reference to
     return torch.empty_like(w)
+
+
+def _sum_into_sink(w, sink, gid):
+    """A leaf with two gradients in one pass, the first of them in its sink: the engine adds the two into a tensor of its own
+    (it adds in place only into a tensor whose storage nobody else holds, and the sink's alias shares the arena's), so .grad
+    would end OUTSIDE the sink and the optimiser / reducer would copy it in later.  A one-shot hook on the leaf moves the sum
+    into the sink as soon as the engine has it and hands autograd the alias instead: .grad ends in the sink, as it does for a
+    weight applied once.  Nothing is done in a later pass (one that died before the hook ran leaves it behind) or into a
+    .grad that exists."""
+    def hook(g):
+        handle.remove()
+        if _PASS_ID != gid or torch._C._current_graph_task_id() != gid or w.grad is not None or g.data_ptr() == sink.data_ptr():
+            return None
+        sink.copy_(g)
+        return sink.detach()
+    handle = w.register_hook(hook)
 
 
 def _grad_buf_or(p, n, device, gid=None):

@@ -8,7 +8,9 @@ writes x5 * alpha + x into channels 0..63 of a NEW stack, which it returns as a 
 dense_block (or dense_skip's successor) recognises such a view and fills the rest of that stack: torch.cat never runs, and the
 stack is the one activation a block keeps for its backward pass.
 """
+import functools
 import math
+import weakref
 
 import torch
 from torch.autograd import Function
@@ -20,10 +22,21 @@ GROW = 32     # output channels of a growth conv
 LAYERS = 4    # growth convs per block
 CINS = tuple(64 + GROW * j for j in range(LAYERS))  # (64, 96, 128, 160)
 
-# Stacks whose channels 64.. nobody has written yet: storage -> address of channel 0.  A block CLAIMS the stack behind its input
-# (one claim per stack: a map fed to two blocks is copied for the second), so an entry lives from the launch that wrote the
-# stack's first 64 channels to the first block that reads them.
+# Stacks whose channels 64.. nobody has written yet: address of the storage -> (weak reference to the storage object, address
+# of channel 0).  A block CLAIMS the stack behind its input (one claim per stack: a map fed to two blocks is copied for the
+# second), so an entry lives from the launch that wrote the stack's first 64 channels to the first block that reads them -- or,
+# for a stack nobody claims (the trunk's last dense_skip), to the death of its storage: the weak reference's callback removes
+# it then, so an entry never outlives the storage it names.  torch keeps ONE Python object per live storage, so a claim also
+# checks that the view's storage IS the recorded object: an unrelated tensor that the allocator gives the same addresses
+# afterwards can never pass for an open stack.
 _OPEN_STACKS = {}
+
+
+def _forget_stack(key, ref):
+    """callback of an entry's weak reference: the storage is gone, and so is the entry (unless the key is another stack's by now)"""
+    entry = _OPEN_STACKS.get(key)
+    if entry is not None and entry[0] is ref:
+        del _OPEN_STACKS[key]
 
 
 def _stack_strides(t, H, W):
@@ -35,9 +48,9 @@ def _stack_strides(t, H, W):
 def _new_stack(B, H, W, device, open_=True):
     S = ops._empty_cl(B, STACK, H, W, device)
     if open_:
-        if len(_OPEN_STACKS) > 4096:
-            _OPEN_STACKS.clear()
-        _OPEN_STACKS[S.untyped_storage()._cdata] = S.data_ptr()
+        st = S.untyped_storage()
+        key = st._cdata
+        _OPEN_STACKS[key] = (weakref.ref(st, functools.partial(_forget_stack, key)), S.data_ptr())
     return S
 
 
@@ -45,7 +58,8 @@ def _claim_stack(x):
     """the (B, 192, H, W) stack x is the first 64 channels of, if x is an unclaimed output of dense_block / dense_skip"""
     B, _, H, W = x.shape
     st = x.untyped_storage()
-    if _OPEN_STACKS.get(st._cdata) != x.data_ptr() or not _stack_strides(x, H, W) or x.storage_offset() != 0:
+    entry = _OPEN_STACKS.get(st._cdata)
+    if entry is None or entry[0]() is not st or entry[1] != x.data_ptr() or not _stack_strides(x, H, W) or x.storage_offset() != 0:
         return None
     if st.nbytes() < B * H * W * STACK * 4:
         return None

@@ -753,8 +753,15 @@ EXCLUDED = {
     "_ConvKxKS2": "convs.py's stride-2 node: its contract is held by tests/test_convs_contract_gpu.py",
     "_Conv1x1": "convs.py's pointwise node: its contract is held by tests/test_convs_contract_gpu.py",
     "_SpectralL1": "no parameters and one differentiable input (the target is refused if it requires grad), scalar output",
+    "_DenseBlock": "ops_dense.py's block node, ten parameters on one stack: its contract is held by tests/test_dense_contract_gpu.py",
+    "_DenseSkip": "ops_dense.py's skip between stacks: its contract is held by tests/test_dense_contract_gpu.py",
+    "_MapMean": "no parameters and one input (pool.py's global mean; pinned against float64 by test_predictor_gpu)",
+    "DegradeValid": "no parameters and one differentiable input (K is refused if it requires grad); held by test_consistency_gpu.py",
 }
 
 # the operators whose weight-gradient buffers come from ops._grad_buf: each must have a case with a `sink`
 GRAD_BUF_USERS = ("_Conv3x3", "_ResBlock", "_GatedGroup", "_ConvReluConv", "_ConvChain", "_ReflConv", "_SftmdHead",
                   "_SftmdTail", "_ConvY2F", "_ConvF2Y", "_ConvKxK")
+# ... and the EXCLUDED ones that take such buffers too: the file that runs their sink and shared-weight cases
+GRAD_BUF_USERS_ELSEWHERE = {"_ConvKxKS2": "tests/test_convs_contract_gpu.py", "_Conv1x1": "tests/test_convs_contract_gpu.py",
+                            "_DenseBlock": "tests/test_dense_contract_gpu.py"}

@@ -1,8 +1,12 @@
-"""The case table of the autograd contract (tests/_contract.py) against ops.py and its family modules, on the host: every `Function` subclass
-defined in ops has a case or a stated exclusion, every builder / float64 restatement runs, and every exact-data case fits
+"""The case table of the autograd contract (tests/_contract.py) against the package, on the host: every `Function` subclass
+defined in any of its modules (found by walking the package, not listed by hand) has a case or a stated exclusion, every builder / float64 restatement runs, and every exact-data case fits
 the significand budget at every size it is run at (so a budget failure can never be met on the GPU first).  The policy of
 ops._grad_buf / ops._side_ok for a tensor that gets two gradients in one backward pass is host code and is pinned here too."""
+import importlib
+import importlib.machinery
 import inspect
+import os
+import pkgutil
 
 import pytest
 import torch
@@ -11,24 +15,54 @@ import _contract as C
 import sisr_amd
 
 ops = sisr_amd.ops
-# ops.py and the family modules whose operators it re-exports
-MODULES = (ops, sisr_amd.ops_chain, sisr_amd.ops_sparnet, sisr_amd.ops_sftmd, sisr_amd.ops_attention, sisr_amd.ops_losses,
-           sisr_amd.convs)
+
+
+def _defined_nodes(m):
+    return {n: o for n, o in vars(m).items()
+            if inspect.isclass(o) and issubclass(o, torch.autograd.Function) and o.__module__ == m.__name__}
+
+
+def _discover():
+    """every module of the package, imported on the host, that defines a torch.autograd.Function subclass: a new family module
+    is seen without anybody listing it (the built HIP libraries lie in the package directory and are no Python modules)"""
+    found = []
+    for info in pkgutil.walk_packages(sisr_amd.__path__, sisr_amd.__name__ + "."):
+        spec = info.module_finder.find_spec(info.name)
+        if not isinstance(spec.loader, importlib.machinery.SourceFileLoader):
+            continue
+        m = importlib.import_module(info.name)
+        if _defined_nodes(m):
+            found.append(m)
+    return tuple(found)
+
+
+MODULES = _discover()
+FLOOR = 52  # the nodes the package defines today: a discovery that went blind (an import that stopped finding modules) shows
 
 
 def _nodes():
-    return {n: o for m in MODULES for n, o in vars(m).items()
-            if inspect.isclass(o) and issubclass(o, torch.autograd.Function) and o.__module__ == m.__name__}
+    nodes = {}
+    for m in MODULES:
+        for n, o in _defined_nodes(m).items():
+            assert n not in nodes, f"two autograd nodes named {n}: {nodes[n].__module__} and {m.__name__} (the table goes by name)"
+            nodes[n] = o
+    return nodes
 
 
 def _functions():
     return sorted(_nodes())
 
 
+def test_discovery_finds_the_family_modules_and_those_beside_them():
+    short = {m.__name__.rsplit(".", 1)[-1] for m in MODULES}
+    assert {"ops", "ops_chain", "ops_sparnet", "ops_sftmd", "ops_attention", "ops_losses", "convs"} <= short, "the former hand-written list"
+    assert {"ops_dense", "pool", "degrade"} <= short, short
+
+
 def test_every_function_of_ops_has_a_case_or_an_exclusion_reason():
     covered = {f for c in C.CASES for f in c.functions}
     names = _functions()
-    assert len(names) >= 45
+    assert len(names) >= FLOOR
     missing = [n for n in names if n not in covered and n not in C.EXCLUDED]
     assert not missing, f"autograd operators without a contract case (tests/_contract.py) or an exclusion reason: {missing}"
     stale = sorted((covered | set(C.EXCLUDED)) - set(names))
@@ -41,14 +75,20 @@ def test_every_function_of_ops_has_a_case_or_an_exclusion_reason():
 def test_every_user_of_grad_buf_is_in_the_table():
     """the shared-weight test runs every case with a `sink`; that list must keep up with the callers of _grad_buf"""
     src = inspect.getsource(ops)
-    users = set()
+    users, elsewhere = set(), set()
     for name, node in _nodes().items():
         body = inspect.getsource(node)
-        if name in C.EXCLUDED:  # (convs.py's two nodes take buffers too; test_convs_contract_gpu.py runs their shared-weight cases)
-            continue
         if "_grad_buf(" in body or "_grad_buf_or(" in body or "_wb_grad_bufs(" in body:
-            users.add(name)
+            (elsewhere if name in C.EXCLUDED else users).add(name)
     assert "_grad_buf" in src and users == set(C.GRAD_BUF_USERS), sorted(users ^ set(C.GRAD_BUF_USERS))
+    # an excluded node that takes buffers is named with the file that runs its sink and shared-weight cases; that file exists,
+    # registers sinks, and the node's exclusion reason points to it
+    assert elsewhere == set(C.GRAD_BUF_USERS_ELSEWHERE), sorted(elsewhere ^ set(C.GRAD_BUF_USERS_ELSEWHERE))
+    for name, path in C.GRAD_BUF_USERS_ELSEWHERE.items():
+        assert path in C.EXCLUDED[name], (name, path)
+        with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), path)) as f:
+            text = f.read()
+        assert "GRAD_SINK" in text and "applied_twice" in text, path
     with_sink = {f for c in C.CASES if c.sink for f in c.functions}
     assert set(C.GRAD_BUF_USERS) | {"_MetaGateMany"} == with_sink, sorted(with_sink ^ set(C.GRAD_BUF_USERS))
 
@@ -129,6 +169,7 @@ def test_second_gradient_of_a_parameter_does_not_get_the_sink_again(clean_sink):
     assert torch.equal(w.grad, torch.tensor([101.0, 1010.0]))
     ptrs = [p for _, p in _TwoBuffers.log]
     assert ptrs.count(sink.data_ptr()) == 1 and len(set(ptrs)) == 2, "first request: the sink; second: a private buffer"
+    assert w.grad.data_ptr() == sink.data_ptr() and torch.equal(sink, torch.tensor([101.0, 1010.0])), "the sum ends in the sink"
     # the next pass starts afresh: one use, the zero-copy path
     w.grad = None
     _TwoBuffers.log = []
@@ -162,6 +203,37 @@ def test_a_pass_that_died_leaves_no_claim_behind(clean_sink):
     _TwoBuffers.log = []
     _TwoBuffers.apply(torch.ones(2), w).sum().backward()
     assert _TwoBuffers.log[0][1] == sink.data_ptr() and w.grad.data_ptr() == sink.data_ptr()
+
+
+def test_a_pass_that_died_with_the_sum_pending_does_not_touch_a_later_pass(clean_sink):
+    """the hook that moves the sum of two contributions into the sink belongs to ONE pass: left behind by a pass that died
+    between the second request and the sum, it must not overwrite a .grad that lives in the sink in a later pass"""
+    w = torch.tensor([1.0, 10.0], requires_grad=True)
+    sink = torch.zeros(2)
+    ops.GRAD_SINK[w.data_ptr()] = sink
+
+    class DiesWithItsBuffer(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, v):
+            ctx.v = v
+            return x * v
+
+        @staticmethod
+        def backward(ctx, g):
+            ops._grad_buf(ctx.v)
+            raise KeyError("the pass dies after the second buffer was handed out")
+
+    x1, x2 = torch.tensor([1.0, 1.0]), torch.tensor([100.0, 100.0])
+    with pytest.raises(KeyError):  # (the engine runs the later node first: the stand-in takes the sink, then the other dies)
+        (DiesWithItsBuffer.apply(x2, w) + _TwoBuffers.apply(x1, w)).sum().backward()
+    assert w.grad is None and [s for s, _ in _TwoBuffers.log] == [False] and _TwoBuffers.log[0][1] == sink.data_ptr()
+    sink.copy_(torch.tensor([5.0, 5.0]))
+    w.grad = sink.detach()
+    _TwoBuffers.apply(x2, w).sum().backward()
+    assert w.grad.data_ptr() == sink.data_ptr() and torch.equal(w.grad, torch.tensor([105.0, 105.0]))
+    w.grad = None
+    _TwoBuffers.apply(x1, w).backward(torch.tensor([1.0, 10.0]))
+    assert w.grad.data_ptr() == sink.data_ptr() and torch.equal(w.grad, torch.tensor([1.0, 10.0]))
 
 
 def test_outside_a_backward_pass_nothing_is_recorded(clean_sink):

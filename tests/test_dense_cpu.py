@@ -103,3 +103,94 @@ def test_ops_offers_the_dense_operators_and_they_are_fp32_only():
         ops.dense_block(torch.zeros(1, 32, 4, 4), convs)
     with pytest.raises(RuntimeError, match="no CPU fallback|HIP device"):
         ops.dense_block(x, convs)
+
+
+# ----------------------------------------------------------------------------- the registry of open stacks (plain host logic)
+# ops_dense._new_stack / _claim_stack only allocate and compare: host tensors take the same path as device ones.
+OD = sisr_amd.ops_dense
+SHAPE = (2, 9, 21)  # (B, H, W)
+
+
+def _open(shape=SHAPE):
+    B, H, W = shape
+    return OD._new_stack(B, H, W, "cpu")
+
+
+def test_an_unclaimed_stack_leaves_the_registry_with_its_storage():
+    """an entry never outlives the storage it names: dropped unclaimed, a stack takes its entry with it -- once, and ten
+    thousand times over without the registry growing or a live open stack losing its claim to the pile of dead ones"""
+    import gc
+    gc.collect()
+    start = len(OD._OPEN_STACKS)
+    S = _open()
+    y = S[:, :64]
+    assert len(OD._OPEN_STACKS) == start + 1
+    del S
+    assert len(OD._OPEN_STACKS) == start + 1, "the 64-channel view keeps the storage, and with it the entry, alive"
+    del y
+    gc.collect()
+    assert len(OD._OPEN_STACKS) == start
+    live = _open()
+    keep = live[:, :64]
+    del live
+    start = len(OD._OPEN_STACKS)
+    worst = start
+    for _ in range(10000):
+        S = _open()
+        y = S[:, :64]
+        worst = max(worst, len(OD._OPEN_STACKS))
+        del S, y
+        worst = max(worst, len(OD._OPEN_STACKS))
+    assert worst <= start + 1, (start, worst)
+    gc.collect()
+    assert len(OD._OPEN_STACKS) == start
+    full = OD._claim_stack(keep)
+    assert full is not None and tuple(full.shape) == (2, 192, 9, 21) and full.data_ptr() == keep.data_ptr()
+    assert len(OD._OPEN_STACKS) == start - 1
+
+
+def test_a_foreign_tensor_at_a_dead_stacks_address_is_not_claimed():
+    """the allocator may hand an unrelated (B, 192, H, W) tensor the storage-object address AND the block of a stack that died
+    unclaimed; its first 64 channels must not pass for an open stack, or dense_block would fill the caller's channels 64.."""
+    B, H, W = SHAPE
+    reused = []
+    for _ in range(8):
+        S = _open()
+        y = S[:, :64]
+        was = (S.untyped_storage()._cdata, S.data_ptr())
+        del S, y
+        Z = ops._empty_cl(B, 192, H, W, "cpu")
+        reused.append((Z.untyped_storage()._cdata, Z.data_ptr()) == was)
+        assert OD._claim_stack(Z[:, :64]) is None, "claimed a tensor that _new_stack never made (addresses reused: %s)" % reused[-1]
+    print("storage address and block reused in %d of 8 rounds" % sum(reused))
+
+
+def test_claims_are_single_and_only_for_the_view_new_stack_made(monkeypatch):
+    import torch
+    B, H, W = SHAPE
+    S = _open()
+    y = S[:, :64]
+    full = OD._claim_stack(y)
+    assert full is not None and full.data_ptr() == S.data_ptr() and full.stride() == S.stride() and full.shape == S.shape
+    assert OD._claim_stack(y) is None, "a stack is claimed once"
+    # a nonzero storage offset: channels 32..95 of an open stack, and the second image of one
+    S = _open()
+    assert OD._claim_stack(S[:, 32:96]) is None
+    assert OD._claim_stack(S[1:, :64]) is None
+    assert OD._claim_stack(S[:, :64]) is not None, "the refusals above must not have consumed the entry"
+    # a storage too small for the stack: a registered 64-channel map of pitch 192 whose storage ends with its own last pixel,
+    # 128 floats short of the stack (everything else about it matches: the size check alone refuses it)
+    strides = (H * W * 192, 1, W * 192, 192)
+    short = torch.as_strided(torch.empty(B * H * W * 192 - 128), (B, 64, H, W), strides)
+    monkeypatch.setattr(ops, "_empty_cl", lambda *a: short)
+    y = _open()
+    monkeypatch.undo()
+    assert y is short and y.untyped_storage()._cdata in OD._OPEN_STACKS and y.storage_offset() == 0
+    assert OD._claim_stack(y) is None
+    # pitch 192, offset 0, room enough -- but not from _new_stack
+    Z = ops._empty_cl(B, 192, H, W, "cpu")
+    assert OD._claim_stack(Z[:, :64]) is None
+    closed = OD._new_stack(B, H, W, "cpu", open_=False)
+    assert OD._claim_stack(closed[:, :64]) is None
+    # ... nor a contiguous 64-channel map
+    assert OD._claim_stack(ops._empty_cl(B, 64, H, W, "cpu")) is None
